@@ -27,6 +27,33 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs stays under 64 MB
+
+
+def dump_outputs(h, flat, out_dir):
+    """--dump-outputs: the residuals (2n,) and the Jacobian (2n, P) of the last Mode A pass, in the layout a caller of
+    cba_reproj_eval_fetch receives (observation order, u row then v row).  Whole views are taken in a fixed order (seed 0) while
+    they fit the budget and are written in ascending view order, so with the same arguments every run writes the same rows; a
+    single view over the budget is cut to a fixed sample of its observations (seed 1)."""
+    P = h.local_columns
+    counts = np.diff(flat.blk_offset).astype(np.int64)
+    obs_bytes = 8 * 2 * (1 + P)
+    pick, total = [], 0
+    for b in np.random.default_rng(0).permutation(len(counts)):
+        if pick and (total + counts[b]) * obs_bytes > DUMP_BUDGET_BYTES:
+            break
+        pick.append(int(b))
+        total += int(counts[b])
+    parts = [h.eval_fetch_blocks(b, b + 1) for b in sorted(pick)]
+    r = np.concatenate([p[0] for p in parts])
+    J = np.concatenate([p[1] for p in parts])
+    if total * obs_bytes > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(1).choice(total, DUMP_BUDGET_BYTES // obs_bytes, replace=False))
+        rows = np.stack([2 * keep, 2 * keep + 1], axis=1).reshape(-1)
+        r, J = r[rows], J[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "residuals.npy"), np.ascontiguousarray(r, dtype=np.float64))
+    np.save(os.path.join(out_dir, "jacobian.npy"), np.ascontiguousarray(J, dtype=np.float64))
 
 
 def main():
@@ -41,7 +68,12 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--lm-timeout", type=float, default=240.0, help="watchdog for the LM section, seconds")
     ap.add_argument("--c3-views", type=int, default=4000, help="views of the strong-scaling problem (BASELINE configs[2]: 4000), split over the ranks; 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's residuals and Jacobian of the last step as DIR/<name>.npy (fp64; a fixed, "
+                         "seeded sample of views when the whole output exceeds 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -103,6 +135,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * n_obs * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # before anything else runs on the handle's buffers
+        dump_outputs(h, flat, args.dump_outputs)
 
     bytes_per_obs = 8 * (4 + 2 + 2 * P)  # 4 loads + 2 residual + 2P Jacobian stores, fp64
     achieved = bytes_per_obs * n_obs / (ms_kernel * 1e-3) / 1e9
