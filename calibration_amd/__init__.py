@@ -28,5 +28,17 @@ from .optim import (  # noqa: F401
     optimize_planar_pose_batch,
     PlanarPoseOptions,
 )
+from .linescan import (  # noqa: F401
+    LinescanCalibrationFacade,
+    LineScanPlaneFitOptions,
+    LineScanView,
+    RansacOptions,
+    calibrate_laser_plane,
+    fit_plane_ransac,
+    fit_plane_svd,
+    invert_brown_conrady,
+    plane_rms,
+    points_from_view,
+)
 
 __version__ = "0.1.0"

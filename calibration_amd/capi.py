@@ -24,6 +24,7 @@ RCCL_UNIQUE_ID_BYTES = 128
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
+c_uint8_p = C.POINTER(C.c_uint8)
 
 
 class CbaOptions(C.Structure):
@@ -84,6 +85,35 @@ class CbaReprojProblem(C.Structure):
     ]
 
 
+class CbaPlaneFitOptions(C.Structure):
+    """``cba_plane_fit_options`` — LineScanPlaneFitOptions (linescan.h:30-33) with RansacOptions (ransac.h:23-30) inlined."""
+
+    _fields_ = [
+        ("use_ransac", C.c_int32),
+        ("max_iters", C.c_int32),
+        ("thresh", C.c_double),
+        ("min_inliers", C.c_int32),
+        ("refit_on_inliers", C.c_int32),
+        ("confidence", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+class CbaLaserPlaneResult(C.Structure):
+    """``cba_laser_plane_result`` — LineScanCalibrationResult (linescan.h) without the (zero) covariance."""
+
+    _fields_ = [
+        ("plane", C.c_double * 4),
+        ("homography", C.c_double * 9),
+        ("rms_error", C.c_double),
+        ("inlier_count", C.c_int64),
+        ("n_points", C.c_int64),
+        ("n_views_used", C.c_int32),
+        ("iters", C.c_int32),
+        ("summary", C.c_char * 16),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, c_double_p, C.c_int64, C.c_void_p)
 
 
@@ -110,6 +140,13 @@ def i32ptr(a: Optional[np.ndarray]):
         return C.cast(None, c_int32_p)
     assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(c_int32_p)
+
+
+def u8ptr(a: Optional[np.ndarray]):
+    if a is None:
+        return C.cast(None, c_uint8_p)
+    assert a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(c_uint8_p)
 
 
 def i64ptr(a: Optional[np.ndarray]):
@@ -237,6 +274,15 @@ PROTOTYPES = {
         C.c_int32,
         [C.c_int32, c_double_p, c_double_p, c_double_p, C.POINTER(CbaOptions), C.POINTER(CbaSummary), c_double_p],
     ),
+    "cba_plane_fit_options_default": (None, [C.POINTER(CbaPlaneFitOptions)]),
+    "cba_calibrate_laser_plane": (
+        C.c_int32,
+        [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p,
+         c_double_p, c_double_p, C.POINTER(CbaPlaneFitOptions), C.POINTER(CbaLaserPlaneResult), c_double_p, c_uint8_p],
+    ),
+    "cba_fit_plane": (
+        C.c_int32, [C.c_int64, c_double_p, C.POINTER(CbaPlaneFitOptions), c_double_p, c_double_p, c_int64_p, c_uint8_p]),
+    "cba_invert_brown_conrady": (C.c_int32, [C.c_int32, c_double_p, c_double_p]),
 }
 
 

@@ -16,9 +16,11 @@
 #include <memory>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "engine.hpp"
 #include "structure.hpp"
+#include "linescan_math.hpp"
 
 using namespace cba;
 
@@ -1139,6 +1141,152 @@ cba_status cba_estimate_planar_pose_batch(int32_t n_views, const int64_t* view_o
                 throw std::invalid_argument("bad view offsets");
         if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
         planar_seed_batch(n_views, view_offset, X, Y, u, v, kmtx5, pose7, default_device());
+    });
+}
+
+// ---- laser-plane calibration (linescan.hip) --------------------------------------------------------------------------------
+void cba_plane_fit_options_default(cba_plane_fit_options* o) {
+    if (!o) return;
+    o->use_ransac = 0;  // LineScanPlaneFitOptions (linescan.h:30-33), RansacOptions (ransac.h:23-30)
+    o->max_iters = 1000;
+    o->thresh = 2.0;
+    o->min_inliers = 12;
+    o->refit_on_inliers = 1;
+    o->confidence = 0.99;
+    o->seed = 1234567;
+}
+
+static void check_plane_fit_options(const cba_plane_fit_options* o) {
+    if (!o) throw std::invalid_argument("null options");
+    // max_iters: one lane and 10 partial sums per chunk for each hypothesis (the scoring grid is max_iters / 256 workgroups wide)
+    if (o->use_ransac && (o->max_iters <= 0 || o->max_iters > CBA_PLANE_FIT_MAX_ITERS || !(o->thresh >= 0.0)))
+        throw std::invalid_argument("bad RANSAC options (max_iters must be in [1, CBA_PLANE_FIT_MAX_ITERS], thresh >= 0)");
+}
+
+static cba_status laser_plane_impl(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                   int32_t n_views, const int64_t* target_offset, const double* X, const double* Y, const double* u,
+                                   const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
+                                   const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* points_xyz,
+                                   uint8_t* inlier_mask, double* stage_ms) {
+    return guarded([&] {
+        if (camera_model != CBA_CAMERA_PINHOLE_BC && camera_model != CBA_CAMERA_SCHEIMPFLUG) throw std::invalid_argument("bad camera model");
+        if (!intr || !target_offset || !laser_offset || !result || (n_views > 0 && (!X || !Y || !u || !v)))
+            throw std::invalid_argument("null argument");
+        if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV)) throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
+        check_plane_fit_options(opts);
+        // validate_observations (linescan.h:39-47)
+        if (n_views < 2) throw std::invalid_argument("At least 2 views are required");
+        if (target_offset[0] != 0 || laser_offset[0] != 0) throw std::invalid_argument("offsets must start at 0");
+        for (int i = 0; i < n_views; ++i) {
+            if (target_offset[i + 1] < target_offset[i] || target_offset[i + 1] - target_offset[i] > 0x7fffffff ||
+                laser_offset[i + 1] < laser_offset[i])
+                throw std::invalid_argument("bad view offsets");
+            if (target_offset[i + 1] - target_offset[i] < 4) throw std::invalid_argument("Each view requires >=4 target correspondences");
+        }
+        if (laser_offset[n_views] > 0 && (!laser_u || !laser_v)) throw std::invalid_argument("null argument");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        laser_plane_calibrate(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
+                              laser_v, *opts, result, points_xyz, inlier_mask, stage_ms, default_device());
+    });
+}
+
+cba_status cba_calibrate_laser_plane(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                     int32_t n_views, const int64_t* target_offset, const double* X, const double* Y, const double* u,
+                                     const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
+                                     const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* points_xyz,
+                                     uint8_t* inlier_mask) {
+    return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
+                            laser_v, opts, result, points_xyz, inlier_mask, nullptr);
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_linescan.py): cba_calibrate_laser_plane without the optional outputs, timing its stages on
+// the device: stage_ms [5] = per-view geometry, laser-point back-projection, the whole plane fit, RANSAC scoring pass 1
+// (moments), RANSAC scoring pass 2 (recount).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_calibrate_laser_plane_timed(
+    int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int32_t n_views, const int64_t* target_offset,
+    const double* X, const double* Y, const double* u, const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
+    const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
+                            laser_v, opts, result, nullptr, nullptr, stage_ms);
+}
+#endif
+
+cba_status cba_fit_plane(int64_t n, const double* xyz, const cba_plane_fit_options* opts, double* plane, double* inlier_rms,
+                         int64_t* inlier_count, uint8_t* inlier_mask) {
+    return guarded([&] {
+        if (!xyz || !plane || !inlier_rms || !inlier_count) throw std::invalid_argument("null argument");
+        check_plane_fit_options(opts);
+        if (n < 3) throw std::invalid_argument("Not enough points to fit a plane");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        plane_fit(n, xyz, *opts, plane, inlier_rms, inlier_count, inlier_mask, default_device());
+    });
+}
+
+// invert_brown_conrady (distortion.h:165-195) -> fit_distortion_full (:231-291) with K = identity: the 882 x n least-squares
+// problem, solved by Householder QR (the reference's JacobiSVD solve; the design has full column rank).
+cba_status cba_invert_brown_conrady(int32_t n, const double* forward, double* inverse) {
+    return guarded([&] {
+        if (!forward || !inverse) throw std::invalid_argument("null argument");
+        if (n < 2) throw std::runtime_error("Insufficient distortion coefficients");
+        const int nr = n - 2, grid = 21, m = 2 * grid * grid;
+        std::vector<double> A(static_cast<size_t>(m) * n), b(m);
+        auto distort = [&](double x, double y, double* xd, double* yd) {
+            const double r2 = x * x + y * y;
+            double radial = 1.0, rpow = r2;
+            for (int i = 0; i < nr; ++i) { radial += forward[i] * rpow; rpow *= r2; }
+            *xd = x * radial + 2.0 * forward[nr] * x * y + forward[nr + 1] * (r2 + 2.0 * x * x);
+            *yd = y * radial + forward[nr] * (r2 + 2.0 * y * y) + 2.0 * forward[nr + 1] * x * y;
+        };
+        int row = 0;
+        for (int i = 0; i < grid; ++i) {
+            const double xu = -1.0 + 2.0 * static_cast<double>(i) / static_cast<double>(grid - 1);
+            for (int j = 0; j < grid; ++j) {
+                const double yu = -1.0 + 2.0 * static_cast<double>(j) / static_cast<double>(grid - 1);
+                double x, y;  // observation: (x, y) = distorted, (u, v) = undistorted
+                distort(xu, yu, &x, &y);
+                const double r2 = x * x + y * y;
+                double* au = &A[static_cast<size_t>(row) * n];
+                double* av = &A[static_cast<size_t>(row + 1) * n];
+                double rpow = r2;
+                for (int k = 0; k < nr; ++k) { au[k] = x * rpow; av[k] = y * rpow; rpow *= r2; }
+                au[nr] = 2.0 * x * y; au[nr + 1] = r2 + 2.0 * x * x;
+                av[nr] = r2 + 2.0 * y * y; av[nr + 1] = 2.0 * x * y;
+                b[row] = xu - x;
+                b[row + 1] = yu - y;
+                row += 2;
+            }
+        }
+        // Householder QR of A (m x n, row-major), applied to b as it goes
+        for (int k = 0; k < n; ++k) {
+            double nrm = 0.0;
+            for (int i = k; i < m; ++i) nrm += A[static_cast<size_t>(i) * n + k] * A[static_cast<size_t>(i) * n + k];
+            nrm = std::sqrt(nrm);
+            if (nrm == 0.0) throw std::runtime_error("rank-deficient distortion fit");
+            const double akk = A[static_cast<size_t>(k) * n + k];
+            const double alpha = akk > 0.0 ? -nrm : nrm;
+            std::vector<double> w(m - k);
+            for (int i = k; i < m; ++i) w[i - k] = A[static_cast<size_t>(i) * n + k];
+            w[0] -= alpha;
+            double ww = 0.0;
+            for (double t : w) ww += t * t;
+            for (int j = k; j < n; ++j) {
+                double d = 0.0;
+                for (int i = k; i < m; ++i) d += w[i - k] * A[static_cast<size_t>(i) * n + j];
+                d = 2.0 * d / ww;
+                for (int i = k; i < m; ++i) A[static_cast<size_t>(i) * n + j] -= d * w[i - k];
+            }
+            double d = 0.0;
+            for (int i = k; i < m; ++i) d += w[i - k] * b[i];
+            d = 2.0 * d / ww;
+            for (int i = k; i < m; ++i) b[i] -= d * w[i - k];
+        }
+        for (int k = n - 1; k >= 0; --k) {
+            double s = b[k];
+            for (int j = k + 1; j < n; ++j) s -= A[static_cast<size_t>(k) * n + j] * inverse[j];
+            inverse[k] = s / A[static_cast<size_t>(k) * n + k];
+        }
     });
 }
 

@@ -301,6 +301,14 @@ void dlt_homography_batch(int n_views, const int64_t* view_offset, const double*
                           double* H9, int32_t* ok, int device);
 void planar_seed_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
                        const double* kmtx5, double* pose7, int device);
+// linescan.hip: calibrate_laser_plane (camera: model, intr, optional inverse coefficients; stage_ms [5] optional timing) and
+// fit_plane_svd / fit_plane_ransac on caller points
+void laser_plane_calibrate(int model, const double* intr, int n_inv, const double* inv, int n_views, const int64_t* toff, const double* X,
+                           const double* Y, const double* u, const double* v, const int64_t* loff, const double* lu, const double* lv,
+                           const cba_plane_fit_options& o, cba_laser_plane_result* res, double* points_xyz, uint8_t* inlier_mask,
+                           double* stage_ms, int device);
+void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, double* plane, double* rms, int64_t* count, uint8_t* mask,
+               int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -427,6 +427,80 @@ cba_status cba_estimate_homography_batch(int32_t n_views, const int64_t* view_of
 cba_status cba_estimate_planar_pose_batch(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y,
                                           const double* u, const double* v, const double* kmtx5, double* pose7);
 
+/* ---- laser-plane calibration of a line-scan rig (include/calib/estimation/linear/linescan.h:39-144, planefit.h/.cpp,
+ * common/ransac.h; facade src/pipeline/linescan.cpp) ------------------------------------------------------------------
+ *
+ * cba_plane_fit_options = LineScanPlaneFitOptions (linescan.h:30-33) with its RansacOptions (ransac.h:23-30) inlined.
+ * Defaults (cba_plane_fit_options_default): use_ransac 0, max_iters 1000, thresh 2.0, min_inliers 12, confidence 0.99,
+ * seed 1234567, refit_on_inliers 1.
+ *
+ * RANSAC here is data-parallel: all max_iters hypotheses are scored (the reference's adaptive calculate_iterations only ever
+ * lowers its iteration count, so this is a superset of its search); iters reports max_iters.  Hypothesis k draws three
+ * distinct point indices from splitmix64 of (seed, 3k + j) (linescan_math.hpp), not from std::mt19937_64: the same seed
+ * gives a different (equally valid) sample sequence than the reference.  confidence is accepted and unused.
+ * The best model has the most inliers, ties broken by lower inlier RMS, then by lower k.  The winner's plane is refit on
+ * its inliers exactly (two-pass centred scatter), as the reference's refit_model does, and its inliers recounted.
+ *
+ * Deliberate departures from the reference:
+ *   - Scheimpflug unprojection.  The reference's ScheimpflugCamera::unproject (scheimpflug.h:198-230) cannot be
+ *     instantiated (it calls CameraTraits<...>::apply_intrinsics_linear; the trait defines apply_linear_intrinsics,
+ *     pinhole.h:149) and would return sensor-plane rather than normalised coordinates.  Here unproject is the exact
+ *     inverse of the projection this library implements (scheimpflug.h:139-181): normalise by K, subtract the sensor
+ *     offset m0, undistort, add m0, and map the tilted-sensor ray mx a + my b + n back to (x/z, y/z).
+ *   - Plane sign.  The reference returns whatever sign its SVD gives.  Every plane returned here has d > 0, or, when
+ *     |d| <= 1e-12 max|p|, its largest-magnitude normal component positive.
+ */
+#define CBA_PLANE_FIT_MAX_ITERS (1 << 20) /* most RANSAC hypotheses of one call (max_iters beyond it: CBA_ERR_INVALID_ARGUMENT) */
+
+typedef struct cba_plane_fit_options {
+    int32_t use_ransac;       /* 0: fit_plane_svd ("linear_svd"); 1: fit_plane_ransac ("ransac") */
+    int32_t max_iters;        /* 1000; at most CBA_PLANE_FIT_MAX_ITERS */
+    double thresh;            /* 2.0: a point is an inlier when |n.p + d| <= thresh */
+    int32_t min_inliers;      /* 12 */
+    int32_t refit_on_inliers; /* 1 */
+    double confidence;        /* 0.99 (unused: every hypothesis is scored) */
+    uint64_t seed;            /* 1234567 */
+} cba_plane_fit_options;
+
+typedef struct cba_laser_plane_result {
+    double plane[4];        /* n (unit), d: n.p + d = 0 in the camera frame */
+    double homography[9];   /* build_plane_homography(plane) (linescan.h:49-61), row-major */
+    double rms_error;       /* plane_rms over all points (linear_svd) or over the inliers (ransac) */
+    int64_t inlier_count;   /* n_points (linear_svd) or the number of inliers (ransac) */
+    int64_t n_points;       /* points produced by points_from_view over all views */
+    int32_t n_views_used;   /* views whose homography succeeded */
+    int32_t iters;          /* ransac: hypotheses scored (= max_iters); linear_svd: 0 */
+    char summary[16];       /* "linear_svd" | "ransac" */
+} cba_laser_plane_result;
+
+void cba_plane_fit_options_default(cba_plane_fit_options* opts);
+
+/* calibrate_laser_plane (linescan.h:101-144).  The camera: camera_model + intr[10 | 12]; inverse_coeffs == NULL undistorts with
+ * the 5-step fixed point of BrownConrady (distortion.h:119-134), non-NULL (n_inverse_coeffs in [2, 16], [k1..k_nr, p1, p2]) with
+ * one evaluation of DualDistortion's inverse polynomial (distortion.h:213-217; see cba_invert_brown_conrady).  View i has target
+ * correspondences [target_offset[i], target_offset[i+1]) of (X, Y) -> (u, v) and laser pixels [laser_offset[i], laser_offset[i+1]).
+ * A view whose homography fails contributes no points (not an error).  Errors: fewer than 2 views, a view with fewer than 4
+ * target correspondences, or fewer than 3 points in total -> CBA_ERR_INVALID_ARGUMENT; RANSAC finding no model -> CBA_ERR_RUNTIME.
+ * Optional outputs: points_xyz [n_laser][3] = points_from_view of every laser pixel (NaN rows for views whose homography failed);
+ * inlier_mask [n_laser] (1 = inlier; every point of a used view for linear_svd, 0 for the pixels of failed views).
+ * The result is bitwise reproducible: every reduction runs in a fixed order. */
+cba_status cba_calibrate_laser_plane(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                     int32_t n_views, const int64_t* target_offset, const double* X, const double* Y, const double* u,
+                                     const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
+                                     const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* points_xyz,
+                                     uint8_t* inlier_mask);
+
+/* fit_plane_svd / fit_plane_ransac (planefit.cpp:68-114) on caller points xyz [n][3] (n >= 3, else CBA_ERR_INVALID_ARGUMENT).
+ * opts->use_ransac selects the form; plane [4]; inlier_rms = plane_rms over the inliers (all points for the SVD form);
+ * inlier_count; inlier_mask [n] optional.  RANSAC finding no model -> CBA_ERR_RUNTIME. */
+cba_status cba_fit_plane(int64_t n, const double* xyz, const cba_plane_fit_options* opts, double* plane, double* inlier_rms,
+                         int64_t* inlier_count, uint8_t* inlier_mask);
+
+/* invert_brown_conrady (distortion.h:165-195): least-squares inverse coefficients of forward [k1..k_nr, p1, p2] (n >= 2) on the
+ * 21 x 21 grid over [-1, 1]^2 (fit_distortion_full with K = identity, distortion.h:231-291).  inverse [n] out.  Host-only: the one
+ * entry point of this group that needs no GPU.  n < 2 -> CBA_ERR_RUNTIME, as the reference throws std::runtime_error. */
+cba_status cba_invert_brown_conrady(int32_t n, const double* forward, double* inverse);
+
 #ifdef __cplusplus
 }
 #endif
