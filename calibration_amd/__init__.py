@@ -40,5 +40,18 @@ from .linescan import (  # noqa: F401
     plane_rms,
     points_from_view,
 )
+from .linear import (  # noqa: F401
+    HomographyResult,
+    IntrinsicsEstimOptions,
+    IntrinsicsEstimateResult,
+    ViewEstimateData,
+    calibrate_planar_intrinsics,
+    estimate_homography,
+    estimate_homography_batch,
+    estimate_intrinsics,
+    pose_from_homography,
+    sanitize_intrinsics,
+    zhang_intrinsics_from_hs,
+)
 
 __version__ = "0.1.0"

@@ -99,6 +99,19 @@ class CbaPlaneFitOptions(C.Structure):
     ]
 
 
+class CbaRansacOptions(C.Structure):
+    """``cba_ransac_options`` — RansacOptions (ransac.h:23-30)."""
+
+    _fields_ = [
+        ("max_iters", C.c_int32),
+        ("thresh", C.c_double),
+        ("min_inliers", C.c_int32),
+        ("refit_on_inliers", C.c_int32),
+        ("confidence", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
 class CbaLaserPlaneResult(C.Structure):
     """``cba_laser_plane_result`` — LineScanCalibrationResult (linescan.h) without the (zero) covariance."""
 
@@ -283,6 +296,17 @@ PROTOTYPES = {
     "cba_fit_plane": (
         C.c_int32, [C.c_int64, c_double_p, C.POINTER(CbaPlaneFitOptions), c_double_p, c_double_p, c_int64_p, c_uint8_p]),
     "cba_invert_brown_conrady": (C.c_int32, [C.c_int32, c_double_p, c_double_p]),
+    "cba_ransac_options_default": (None, [C.POINTER(CbaRansacOptions)]),
+    "cba_estimate_homography_ransac_batch": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(CbaRansacOptions), c_double_p,
+                    c_int32_p, c_int32_p, c_double_p, c_uint8_p]),
+    "cba_estimate_intrinsics": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.POINTER(CbaRansacOptions),
+                    c_double_p, c_double_p, C.c_int32, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p,
+                    c_int32_p, c_uint8_p]),
+    "cba_zhang_intrinsics_from_hs": (C.c_int32, [C.c_int32, c_double_p, c_double_p, c_int32_p]),
+    "cba_pose_from_homography": (C.c_int32, [c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p]),
+    "cba_sanitize_intrinsics": (C.c_int32, [c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
 }
 
 

@@ -21,6 +21,7 @@
 #include "engine.hpp"
 #include "structure.hpp"
 #include "linescan_math.hpp"
+#include "hom_ransac_math.hpp"
 
 using namespace cba;
 
@@ -1287,6 +1288,135 @@ cba_status cba_invert_brown_conrady(int32_t n, const double* forward, double* in
             for (int j = k + 1; j < n; ++j) s -= A[static_cast<size_t>(k) * n + j] * inverse[j];
             inverse[k] = s / A[static_cast<size_t>(k) * n + k];
         }
+    });
+}
+
+// ---- linear seed of planar intrinsic calibration (hom_ransac.hip, hom_ransac_math.hpp) ----------------------------------------
+void cba_ransac_options_default(cba_ransac_options* o) {
+    if (!o) return;
+    o->max_iters = 1000;  // RansacOptions (ransac.h:23-30)
+    o->thresh = 2.0;
+    o->min_inliers = 12;
+    o->refit_on_inliers = 1;
+    o->confidence = 0.99;
+    o->seed = 1234567;
+}
+
+static void check_views(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v) {
+    if (n_views < 0 || !view_offset) throw std::invalid_argument("null argument");
+    if (n_views > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
+    if (view_offset[0] != 0) throw std::invalid_argument("view offsets must start at 0");
+    for (int i = 0; i < n_views; ++i)
+        if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff)
+            throw std::invalid_argument("bad view offsets");
+}
+
+static void check_ransac_options(const cba_ransac_options* o) {
+    // max_iters: one lane per hypothesis; the scoring grid is max_iters / 256 workgroups per view, each writing one candidate record
+    if (o->max_iters < 0 || o->max_iters > CBA_RANSAC_MAX_ITERS || !(o->thresh >= 0.0))
+        throw std::invalid_argument("bad RANSAC options (max_iters must be in [0, CBA_RANSAC_MAX_ITERS], thresh >= 0)");
+}
+
+// estimate_homography (optim/homography.cpp:45-60 with RansacOptions, :31-43 without)
+cba_status cba_estimate_homography_ransac_batch(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y,
+                                                const double* u, const double* v, const cba_ransac_options* opts, double* h9,
+                                                int32_t* success, int32_t* inlier_count, double* symmetric_rms, uint8_t* inlier_mask) {
+    return guarded([&] {
+        check_views(n_views, view_offset, X, Y, u, v);
+        if (!h9 || !success || !inlier_count || !symmetric_rms) throw std::invalid_argument("null argument");
+        if (opts) check_ransac_options(opts);
+        if (n_views == 0) return;
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        homography_ransac_batch(n_views, view_offset, X, Y, u, v, opts, h9, success, inlier_count, symmetric_rms, inlier_mask,
+                                default_device());
+    });
+}
+
+static cba_status estimate_intrinsics_impl(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u,
+                                           const double* v, int32_t use_ransac, const cba_ransac_options* ransac, const double* bounds_lo5,
+                                           const double* bounds_hi5, int32_t* success, double* kmtx5, int32_t* sanitized,
+                                           int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12, int32_t* pose_ok,
+                                           uint8_t* inlier_mask, double* stage_ms) {
+    return guarded([&] {
+        check_views(n_views, view_offset, X, Y, u, v);
+        if (!success || !kmtx5 || !sanitized) throw std::invalid_argument("null argument");
+        if (n_views > 0 && (!view_ok || !h9 || !forward_rms_px || !rt12 || !pose_ok)) throw std::invalid_argument("null argument");
+        if (!bounds_lo5 != !bounds_hi5) throw std::invalid_argument("bounds_lo5 and bounds_hi5 must both be given or both be NULL");
+        if (use_ransac) {
+            if (!ransac) throw std::invalid_argument("null argument");
+            check_ransac_options(ransac);
+        }
+        *success = 0;
+        *sanitized = 0;
+        for (int k = 0; k < 5; ++k) kmtx5[k] = 0.0;
+        if (n_views == 0) return;  // intrinsicsdlt.cpp:104-106
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        estimate_intrinsics_gpu(n_views, view_offset, X, Y, u, v, use_ransac ? ransac : nullptr, bounds_lo5, bounds_hi5, success, kmtx5,
+                                sanitized, view_ok, h9, forward_rms_px, rt12, pose_ok, inlier_mask, stage_ms, default_device());
+    });
+}
+
+cba_status cba_estimate_intrinsics(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u,
+                                   const double* v, int32_t use_ransac, const cba_ransac_options* ransac, const double* bounds_lo5,
+                                   const double* bounds_hi5, int32_t use_skew, int32_t* success, double* kmtx5, int32_t* sanitized,
+                                   int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12, int32_t* pose_ok,
+                                   uint8_t* inlier_mask) {
+    (void)use_skew;  // IntrinsicsEstimOptions::use_skew is not read by estimate_intrinsics
+    return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, bounds_lo5, bounds_hi5, success, kmtx5, sanitized,
+                                    view_ok, h9, forward_rms_px, rt12, pose_ok, inlier_mask, nullptr);
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_intrinsics_seed.py): cba_estimate_intrinsics timing its stages on the device: stage_ms [5] =
+// homographies (the scoring kernel, or the DLT), homographies (selection, h22 rescale, symmetric rms), Zhang + sanitize, poses,
+// total.  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_timed(
+    int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v, int32_t use_ransac,
+    const cba_ransac_options* ransac, int32_t* success, double* kmtx5, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
+    int32_t* pose_ok, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    int32_t sanitized = 0;
+    return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, nullptr, nullptr, success, kmtx5, &sanitized,
+                                    view_ok, h9, forward_rms_px, rt12, pose_ok, nullptr, stage_ms);
+}
+#endif
+
+// zhang_intrinsics_from_hs (zhang.cpp:174-206), compiled for the host from the device header
+cba_status cba_zhang_intrinsics_from_hs(int32_t n, const double* h9, double* kmtx5, int32_t* success) {
+    return guarded([&] {
+        if (n < 0 || (n > 0 && !h9) || !kmtx5 || !success) throw std::invalid_argument("null argument");
+        double G[36] = {};
+        for (int i = 0; i < n; ++i) hr_zhang_accumulate(h9 + 9 * static_cast<int64_t>(i), G);
+        double k5[5];
+        *success = hr_zhang_solve(n, G, k5) ? 1 : 0;
+        if (*success)
+            for (int k = 0; k < 5; ++k) kmtx5[k] = k5[k];
+    });
+}
+
+cba_status cba_pose_from_homography(const double* kmtx5, const double* h9, double* rt12, int32_t* success, double* scale,
+                                    double* cond_check) {
+    return guarded([&] {
+        if (!kmtx5 || !h9 || !rt12 || !success) throw std::invalid_argument("null argument");
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 0.0, c = 0.0;
+        *success = hr_pose_from_homography(kmtx5, h9, R, t, &s, &c) ? 1 : 0;
+        if (!*success) {
+            const double id[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            for (int a = 0; a < 9; ++a) R[a] = id[a];
+            t[0] = t[1] = t[2] = 0.0;
+        }
+        for (int a = 0; a < 9; ++a) rt12[a] = R[a];
+        for (int k = 0; k < 3; ++k) rt12[9 + k] = t[k];
+        if (scale) *scale = s;
+        if (cond_check) *cond_check = c;
+    });
+}
+
+cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5, const double* bounds_hi5, double* out5,
+                                   int32_t* modified) {
+    return guarded([&] {
+        if (!kmtx5 || !bounds_lo5 || !bounds_hi5 || !out5 || !modified) throw std::invalid_argument("null argument");
+        *modified = hr_sanitize(kmtx5, bounds_lo5, bounds_hi5, out5) ? 1 : 0;
     });
 }
 

@@ -309,6 +309,15 @@ void laser_plane_calibrate(int model, const double* intr, int n_inv, const doubl
                            double* stage_ms, int device);
 void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, double* plane, double* rms, int64_t* count, uint8_t* mask,
                int device);
+// hom_ransac.hip: estimate_homography (RANSAC when o != nullptr, else DLT) of a batch of views, and estimate_intrinsics as one device
+// pipeline (o: RANSAC options or nullptr; bounds optional; inlier_mask, stage_ms [5] optional)
+void homography_ransac_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                             const cba_ransac_options* o, double* h9, int32_t* success, int32_t* inlier_count, double* symmetric_rms,
+                             uint8_t* inlier_mask, int device);
+void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                             const cba_ransac_options* o, const double* bounds_lo5, const double* bounds_hi5, int32_t* success,
+                             double* kmtx5, int32_t* sanitized, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
+                             int32_t* pose_ok, uint8_t* inlier_mask, double* stage_ms, int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -501,6 +501,85 @@ cba_status cba_fit_plane(int64_t n, const double* xyz, const cba_plane_fit_optio
  * entry point of this group that needs no GPU.  n < 2 -> CBA_ERR_RUNTIME, as the reference throws std::runtime_error. */
 cba_status cba_invert_brown_conrady(int32_t n, const double* forward, double* inverse);
 
+/* ---- linear seed of planar intrinsic calibration (include/calib/estimation/linear/homography.h, intrinsics.h, zhang.h,
+ * posefromhomography.h; src/estimation/linear/intrinsicsdlt.cpp:101-145, common/ransac.h, common/intrinsics_utils.h) ----------
+ *
+ * cba_ransac_options = RansacOptions (ransac.h:23-30).  Defaults (cba_ransac_options_default): max_iters 1000, thresh 2.0,
+ * min_inliers 12, confidence 0.99, seed 1234567, refit_on_inliers 1.
+ *
+ * RANSAC over the homography of one view (ransac<HomographyEstimator>, ransac.h:121-194) is data-parallel, with the same two
+ * departures as the laser-plane RANSAC above:
+ *   - Every one of max_iters hypotheses is scored (the reference's adaptive calculate_iterations only ever lowers its count, so
+ *     this is a superset of its search); confidence is accepted and unused.
+ *   - Hypothesis k draws four distinct point indices from splitmix64 of (seed, 4k + j) (hom_ransac_math.hpp), not from
+ *     std::mt19937_64 + std::sample: the same seed gives a different (equally valid) sample sequence than the reference.  As in
+ *     the reference, which runs ransac per view with the same options, a view's samples depend only on its own point count and
+ *     the options, never on its position in a batch.
+ * A sample whose object points hold a near-collinear triplet (twice the area < 1e-6, homographyestimator.cpp:100-119) is skipped;
+ * a model is kept when it has at least min_inliers inliers (symmetric transfer error <= thresh, :80-94); with refit_on_inliers it
+ * is refit on those inliers by the Hartley-normalised DLT (refit_model, ransac.h:98-111; a failed refit keeps the raw model and
+ * its inliers) and its inliers recounted.  The best model has the most inliers, ties broken by lower inlier RMS, then by lower k.
+ * Every reduction runs in a fixed order: two identical calls are bitwise identical, and a view's result does not depend on the
+ * other views of the batch.
+ *
+ * symmetric_rms reproduces the reference's symmetric_rms_px (intrinsicsdlt.cpp:21-30, optim/homography.cpp:19-28), which sums
+ * the residuals r_i, not r_i^2: sqrt(sum_i r_i / 2n) over the n inliers (infinity when there are none). */
+#define CBA_RANSAC_MAX_ITERS (1 << 16) /* most RANSAC hypotheses per view (max_iters beyond it: CBA_ERR_INVALID_ARGUMENT) */
+
+typedef struct cba_ransac_options {
+    int32_t max_iters;        /* 1000; in [0, CBA_RANSAC_MAX_ITERS] (0: no hypothesis, every view fails) */
+    double thresh;            /* 2.0: a correspondence is an inlier when its symmetric transfer error is <= thresh (pixels) */
+    int32_t min_inliers;      /* 12 */
+    int32_t refit_on_inliers; /* 1 */
+    double confidence;        /* 0.99 (unused: every hypothesis is scored) */
+    uint64_t seed;            /* 1234567 */
+} cba_ransac_options;
+
+void cba_ransac_options_default(cba_ransac_options* opts);
+
+/* estimate_homography (include/calib/estimation/linear/homography.h:22-24, src/estimation/optim/homography.cpp:31-60) of every
+ * view: view i has correspondences [view_offset[i], view_offset[i+1]) of target (X, Y) -> pixel (u, v).  opts != NULL: RANSAC
+ * with those options (estimate_homography_ransac, :45-60); opts == NULL: the all-points Hartley-normalised DLT
+ * (estimate_homography_dlt, :31-43).  Per view: h9 [9] row-major, returned WITHOUT an h22 rescale as the reference returns it
+ * (the identity where the view fails); success (0 for fewer than 4 points, a failed fit, or RANSAC finding no model);
+ * inlier_count; symmetric_rms (see above; 0 where the view fails).  inlier_mask [view_offset[n_views]] optional (1 = inlier; every
+ * point of a successful view on the DLT path).  n_views == 0 is no work.  Errors: null pointers, bad offsets, max_iters outside
+ * [0, CBA_RANSAC_MAX_ITERS] or thresh < 0 -> CBA_ERR_INVALID_ARGUMENT. */
+cba_status cba_estimate_homography_ransac_batch(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y,
+                                                const double* u, const double* v, const cba_ransac_options* opts, double* h9,
+                                                int32_t* success, int32_t* inlier_count, double* symmetric_rms, uint8_t* inlier_mask);
+
+/* estimate_intrinsics (include/calib/estimation/linear/intrinsics.h:56-58, intrinsicsdlt.cpp:101-145) as one device pipeline:
+ * the homography of every view (RANSAC with *ransac when use_ransac, else the all-points DLT), rescaled by h22 where
+ * |h22| > 1e-15 (:56-58, 69-71); zhang_intrinsics_from_hs over the successful views in view order; sanitize_intrinsics with the
+ * optional bounds (bounds_lo5 / bounds_hi5 = [fx, fy, cx, cy, skew], both NULL: no bounds); pose_from_homography of every
+ * successful view with the sanitised K.  use_skew is accepted and unused, as in the reference.
+ * Outputs: success (0: no views, or fewer than 4 views with a homography -- not an error); kmtx5 [fx, fy, cx, cy, skew] (zeros when
+ * unsuccessful); sanitized (1 when the bounds changed K); and per INPUT view: view_ok (the homography succeeded: the view is one of
+ * the reference's result.views, in input order), h9 (rescaled), forward_rms_px (symmetric_rms_px), rt12 = c_T_t as [R (9, row-major) | t (3)]
+ * (the identity where it fails) and pose_ok (pose_from_homography succeeded).  Poses are [R | t], not quaternions: where t_z <= 0
+ * the reference negates R and t together (posefromhomography.cpp:49-54), which leaves det R = -1, and that is returned as is.  inlier_mask [view_offset[n_views]] optional.
+ * A view with fewer than 4 points fails (not an error).  Errors: as cba_estimate_homography_ransac_batch. */
+cba_status cba_estimate_intrinsics(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u,
+                                   const double* v, int32_t use_ransac, const cba_ransac_options* ransac, const double* bounds_lo5,
+                                   const double* bounds_hi5, int32_t use_skew, int32_t* success, double* kmtx5, int32_t* sanitized,
+                                   int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12, int32_t* pose_ok,
+                                   uint8_t* inlier_mask);
+
+/* zhang_intrinsics_from_hs (zhang.h, zhang.cpp:174-206) on n homographies h9 [n][9] (row-major): kmtx5 = [fx, fy, cx, cy, skew],
+ * success = 0 (kmtx5 untouched) where the reference returns nullopt (n < 4, B factors with neither sign).  Host-only. */
+cba_status cba_zhang_intrinsics_from_hs(int32_t n, const double* h9, double* kmtx5, int32_t* success);
+
+/* pose_from_homography (posefromhomography.h, posefromhomography.cpp:11-62) with K = kmtx5: rt12 = c_T_t as [R (9, row-major) | t (3)]
+ * (see cba_estimate_intrinsics on det R), success, and the reference's diagnostics scale and cond_check (either may be NULL).  Host-only. */
+cba_status cba_pose_from_homography(const double* kmtx5, const double* h9, double* rt12, int32_t* success, double* scale,
+                                    double* cond_check);
+
+/* sanitize_intrinsics (common/intrinsics_utils.h) with bounds lo5 / hi5 ([fx, fy, cx, cy, skew]; fx_max, fy_max unused, as in the
+ * reference): out5, modified.  Host-only. */
+cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5, const double* bounds_hi5, double* out5,
+                                   int32_t* modified);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,2 @@
+#pragma once
+#include "../../../hr_min.h"  // test-only stand-in, see hr_min.h
