@@ -53,5 +53,11 @@ from .linear import (  # noqa: F401
     sanitize_intrinsics,
     zhang_intrinsics_from_hs,
 )
+from .rig import (  # noqa: F401
+    ExtrinsicPoses,
+    RigCalibrationResult,
+    calibrate_rig,
+    estimate_extrinsic_dlt,
+)
 
 __version__ = "0.1.0"

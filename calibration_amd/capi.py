@@ -307,6 +307,9 @@ PROTOTYPES = {
     "cba_zhang_intrinsics_from_hs": (C.c_int32, [C.c_int32, c_double_p, c_double_p, c_int32_p]),
     "cba_pose_from_homography": (C.c_int32, [c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p]),
     "cba_sanitize_intrinsics": (C.c_int32, [c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    "cba_estimate_extrinsic_dlt": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_int64_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                    c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
 }
 
 

@@ -1420,4 +1420,64 @@ cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5
     });
 }
 
+
+// ---- linear seed of a multi-camera rig (extrinsic_dlt.hip, extrinsic_dlt_math.hpp) -------------------------------------------
+static cba_status extrinsic_dlt_impl(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
+                                     const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
+                                     const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok,
+                                     double* stage_ms) {
+    return guarded([&] {
+        if (n_cams < 1 || n_views < 1) throw std::runtime_error("Empty views or cameras provided");  // extrinsics.h:31-33
+        if (n_blocks < 0) throw std::invalid_argument("n_blocks must be >= 0");
+        if (!blk_offset || !kmtx5 || !c_T_r || !r_T_t || (n_blocks > 0 && (!blk_view || !blk_cam))) throw std::invalid_argument("null argument");
+        if (blk_offset[0] != 0) throw std::invalid_argument("block offsets must start at 0");
+        for (int b = 0; b < n_blocks; ++b)
+            if (blk_offset[b + 1] < blk_offset[b] || blk_offset[b + 1] - blk_offset[b] > 0x7fffffff)
+                throw std::invalid_argument("bad block offsets");
+        if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
+        // the (view, camera) -> block table: the averaging order of the device stages comes from it, never from the block order
+        std::vector<int32_t> table(static_cast<size_t>(n_views) * static_cast<size_t>(n_cams), -1);
+        for (int b = 0; b < n_blocks; ++b) {
+            if (blk_view[b] < 0 || blk_view[b] >= n_views) throw std::invalid_argument("block " + std::to_string(b) + ": view index out of range");
+            if (blk_cam[b] < 0 || blk_cam[b] >= n_cams) throw std::invalid_argument("block " + std::to_string(b) + ": camera index out of range");
+            int32_t& slot = table[static_cast<size_t>(blk_view[b]) * static_cast<size_t>(n_cams) + static_cast<size_t>(blk_cam[b])];
+            if (slot >= 0)
+                throw std::invalid_argument("blocks " + std::to_string(slot) + " and " + std::to_string(b) + " share view " +
+                                            std::to_string(blk_view[b]) + " and camera " + std::to_string(blk_cam[b]));
+            slot = b;
+        }
+        if (n_blocks == 0) {  // every pose is the identity (extrinsics.h:55, 65)
+            for (int64_t i = 0; i < n_cams; ++i)
+                for (int k = 0; k < 7; ++k) c_T_r[7 * i + k] = k == 0 ? 1.0 : 0.0;
+            for (int64_t i = 0; i < n_views; ++i)
+                for (int k = 0; k < 7; ++k) r_T_t[7 * i + k] = k == 0 ? 1.0 : 0.0;
+            if (stage_ms)
+                for (int k = 0; k < 4; ++k) stage_ms[k] = 0.0;
+            return;
+        }
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        extrinsic_dlt_gpu(n_cams, n_views, n_blocks, blk_offset, blk_cam, table.data(), X, Y, u, v, kmtx5, c_T_r, r_T_t, blk_c_T_t, blk_ok,
+                          stage_ms, default_device());
+    });
+}
+
+cba_status cba_estimate_extrinsic_dlt(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
+                                      const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
+                                      const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok) {
+    return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, blk_c_T_t, blk_ok,
+                              nullptr);
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_extrinsic_seed.py): cba_estimate_extrinsic_dlt timing its stages on the device: stage_ms [4] =
+// block poses, camera averages, target averages, total (uploads excluded).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_estimate_extrinsic_dlt_timed(
+    int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view, const int32_t* blk_cam,
+    const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r, double* r_T_t, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, nullptr, nullptr,
+                              stage_ms);
+}
+#endif
+
 }  // extern "C"

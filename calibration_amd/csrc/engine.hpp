@@ -318,6 +318,11 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
                              const cba_ransac_options* o, const double* bounds_lo5, const double* bounds_hi5, int32_t* success,
                              double* kmtx5, int32_t* sanitized, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
                              int32_t* pose_ok, uint8_t* inlier_mask, double* stage_ms, int device);
+// extrinsic_dlt.hip: estimate_extrinsic_dlt on the blocked layout of cba_optimize_extrinsics; table [n_views][n_cams] = block index or
+// -1 (built and checked by the caller); blk_pose, blk_ok, stage_ms [4] optional
+void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const int32_t* table,
+                       const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r,
+                       double* r_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

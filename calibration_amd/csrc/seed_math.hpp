@@ -186,13 +186,14 @@ CBA_HD bool dlt_homography_view(int n, const double* X, const double* Y, const d
 }
 
 // The whole seed of one view.  pose7 = [qw qx qy qz tx ty tz] (identity for < 4 points, planarpose_linear.cpp:55-57).
+// Returns false where the pose is that identity (< 4 points or a failed homography fit).
 template <class Coop>
-CBA_HD void planar_seed_view(int n, const double* X, const double* Y, const double* u, const double* v, const double* K, Coop& co,
+CBA_HD bool planar_seed_view(int n, const double* X, const double* Y, const double* u, const double* v, const double* K, Coop& co,
                              double* pose7) {
     pose7[0] = 1.0;
     for (int k = 1; k < 7; ++k) pose7[k] = 0.0;
     double H[9];
-    if (!dlt_homography_view(n, X, Y, u, v, K, co, H)) return;
+    if (!dlt_homography_view(n, X, Y, u, v, K, co, H)) return false;
     if (fabs(H[8]) > 1e-15) {  // planarpose_linear.cpp:72-74
         const double inv = 1.0 / H[8];
         for (int a = 0; a < 9; ++a) H[a] *= inv;
@@ -201,6 +202,7 @@ CBA_HD void planar_seed_view(int n, const double* X, const double* Y, const doub
     seed_pose_from_h(H, R, t);
     seed_rotmat_to_quat(R, pose7);
     for (int k = 0; k < 3; ++k) pose7[4 + k] = t[k];
+    return true;
 }
 
 }  // namespace cba

@@ -25,6 +25,7 @@
  *                               (src/estimation/optim/intrinsicssemidlt.cpp:155-191)
  *   cba_optimize_homography     include/calib/estimation/optim/homography.h:17-18
  *                               (src/estimation/optim/homography.cpp:144-175)
+ *   cba_estimate_extrinsic_dlt  include/calib/estimation/linear/extrinsics.h:27-78
  *   cba_reproj_* (handle API)   the ceres::Problem the reference builds and solves inside those
  *                               functions (intrinsics.cpp:63-90, extrinsics.cpp:86-160,
  *                               bundle.cpp:83-133, detail/ceresutils.h:27-43,69-126); exposed so
@@ -579,6 +580,37 @@ cba_status cba_pose_from_homography(const double* kmtx5, const double* h9, doubl
  * reference): out5, modified.  Host-only. */
 cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5, const double* bounds_hi5, double* out5,
                                    int32_t* modified);
+
+/* ---- linear seed of a multi-camera rig (include/calib/estimation/linear/extrinsics.h:27-78, estimation/common/se3_utils.h:75-95;
+ * the seed of the stereo and multi-camera facades, src/pipeline/facades/extrinsics.cpp:91-131, 184-229) --------------------------
+ *
+ * estimate_extrinsic_dlt on the blocked layout of cba_optimize_extrinsics: block b holds the points [blk_offset[b], blk_offset[b+1])
+ * of view blk_view[b] seen by camera blk_cam[b]; an absent (view, camera) pair has no block.  kmtx5 [n_cams][5] = [fx, fy, cx, cy,
+ * skew] of each camera.  Outputs feed cba_optimize_extrinsics directly: c_T_r [n_cams][7], r_T_t [n_views][7] (pose7, unit
+ * quaternions), and optionally blk_c_T_t [n_blocks][7] (each block's planar pose) and blk_ok [n_blocks].
+ *   1. Every block's pose is estimate_planar_pose (planarpose.h:38-110) with its camera's K: pixels normalised by K only, so
+ *      DISTORTION IS IGNORED, as in the reference (the facades' dual-distortion cameras are only read for K); then the
+ *      Hartley-normalised DLT and pose_from_homography_normalized.  A block's pose is bitwise what cba_estimate_planar_pose_batch
+ *      returns for it with the same K.
+ *   2. c_T_r[0] = I; c_T_r[c] averages T[v][c] T[v][0]^-1 over the views v, in increasing v, where both blocks exist and have at
+ *      least 4 points (the identity when there is none).
+ *   3. r_T_t[v] averages c_T_r[c]^-1 T[v][c] over the cameras c, in increasing c, whose block exists and has at least 4 points (the
+ *      identity when there is none).
+ *   Averaging is average_isometries: the mean translation and a running quaternion sum in which each new quaternion is negated when
+ *   its dot product with the sum so far is negative.  That sign rule is sequential and order-dependent and is kept as it is; the
+ *   order comes from the (view, camera) indices, so results do not depend on the order of the blocks, a camera's c_T_r does not
+ *   depend on the other cameras' blocks, and two identical calls are bitwise identical.
+ * Departure: the reference's template estimate_planar_pose has no failure branch.  Here, as in its CameraMatrix overload
+ * (planarpose_linear.cpp:54-76), a block of >= 4 points whose homography fit fails (non-finite, or a singular normal matrix) gets
+ * the identity pose and blk_ok = 0; the skip rules of steps 2 and 3 count points only, as the reference's do, so such a block still
+ * enters the averages with that identity.  blk_ok = 0 also marks blocks of fewer than 4 points.
+ * Errors: n_cams < 1 or n_views < 1 -> CBA_ERR_RUNTIME "Empty views or cameras provided" (the reference's runtime_error); null
+ * required pointers, n_blocks < 0, offsets not starting at 0 or decreasing, a view or camera index out of range, or two blocks with
+ * the same (view, camera) -> CBA_ERR_INVALID_ARGUMENT, all checked before any device work.  n_blocks == 0 gives identities without
+ * a device; otherwise no device -> CBA_ERR_NO_DEVICE. */
+cba_status cba_estimate_extrinsic_dlt(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
+                                      const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
+                                      const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok);
 
 #ifdef __cplusplus
 }
