@@ -60,4 +60,14 @@ from .rig import (  # noqa: F401
     estimate_extrinsic_dlt,
 )
 
+from .handeye_rig import (  # noqa: F401
+    BundleRigResult,
+    BundleSeed,
+    HandeyeRigResult,
+    calibrate_bundle_rig,
+    calibrate_handeye_rig,
+    estimate_bundle_seed,
+    estimate_bundle_seed_blocks,
+)
+
 __version__ = "0.1.0"

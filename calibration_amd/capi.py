@@ -17,6 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 CBA_OK, CBA_ERR_INVALID_ARGUMENT, CBA_ERR_RUNTIME, CBA_ERR_NO_DEVICE, CBA_ERR_HIP, CBA_ERR_INTERNAL = range(6)
 CHAIN_INTRINSIC, CHAIN_EXTRINSIC, CHAIN_BUNDLE = 0, 1, 2
+# cba_estimate_bundle_seed: per-camera status, initial-target source (calibba.h)
+HANDEYE_DLT, HANDEYE_GIVEN, HANDEYE_TOO_FEW_VIEWS, HANDEYE_NO_PAIRS, HANDEYE_SINGULAR = range(5)
+TARGET_ESTIMATED, TARGET_CONFIG, TARGET_IDENTITY = range(3)
 CAMERA_PINHOLE_BC, CAMERA_SCHEIMPFLUG = 0, 1
 TERM_CONVERGENCE, TERM_NO_CONVERGENCE, TERM_FAILURE = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
@@ -310,6 +313,10 @@ PROTOTYPES = {
     "cba_estimate_extrinsic_dlt": (
         C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_int64_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
                     c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    "cba_estimate_bundle_seed": (
+        C.c_int32, [C.c_int32, C.c_int32, c_int64_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                    C.c_double, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_double_p,
+                    c_int32_p]),
 }
 
 

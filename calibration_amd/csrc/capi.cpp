@@ -1468,6 +1468,75 @@ cba_status cba_estimate_extrinsic_dlt(int32_t n_cams, int32_t n_views, int32_t n
                               nullptr);
 }
 
+// ---- seed of the hand-eye and bundle stages (bundle_seed.hip, bundle_seed_math.hpp) ------------------------------------------
+static cba_status bundle_seed_impl(int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g,
+                                   const double* X, const double* Y, const double* u, const double* v, const double* kmtx5,
+                                   double min_angle_deg, const int32_t* given_mask, const double* g_T_c_given, const double* b_T_t_given,
+                                   double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, double* b_T_t, int32_t* target_source,
+                                   double* blk_c_T_t, int32_t* blk_ok, double* stage_ms) {
+    return guarded([&] {
+        if (n_cams < 1) throw std::invalid_argument("n_cams must be >= 1");
+        if (n_blocks < 0) throw std::invalid_argument("n_blocks must be >= 0");
+        if (!(min_angle_deg >= 0.0) || !std::isfinite(min_angle_deg)) throw std::invalid_argument("min_angle_deg must be finite and >= 0");
+        if (!blk_offset || !kmtx5 || !g_T_c || !cam_status || !cam_pairs || !b_T_t || !target_source ||
+            (n_blocks > 0 && (!blk_cam || !blk_b_T_g)))
+            throw std::invalid_argument("null argument");
+        if (given_mask && !g_T_c_given) throw std::invalid_argument("given_mask needs g_T_c_given");
+        if (blk_offset[0] != 0) throw std::invalid_argument("block offsets must start at 0");
+        for (int b = 0; b < n_blocks; ++b)
+            if (blk_offset[b + 1] < blk_offset[b] || blk_offset[b + 1] - blk_offset[b] > 0x7fffffff)
+                throw std::invalid_argument("bad block offsets");
+        if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
+        for (int b = 0; b < n_blocks; ++b)
+            if (blk_cam[b] < 0 || blk_cam[b] >= n_cams) throw std::invalid_argument("block " + std::to_string(b) + ": camera index out of range");
+        // each camera's pose list: its blocks of >= 4 points in increasing block index (the reference's SensorAccumulator)
+        std::vector<int32_t> cam_start(static_cast<size_t>(n_cams) + 1, 0), cam_blk;
+        for (int b = 0; b < n_blocks; ++b)
+            if (blk_offset[b + 1] - blk_offset[b] >= 4) ++cam_start[static_cast<size_t>(blk_cam[b]) + 1];
+        for (int c = 0; c < n_cams; ++c) cam_start[c + 1] += cam_start[c];
+        cam_blk.resize(static_cast<size_t>(cam_start[n_cams]));
+        {
+            std::vector<int32_t> fill(cam_start.begin(), cam_start.end() - 1);
+            for (int b = 0; b < n_blocks; ++b)
+                if (blk_offset[b + 1] - blk_offset[b] >= 4) cam_blk[fill[blk_cam[b]]++] = b;
+        }
+        // statuses the host decides; the device overwrites the DLT cameras'
+        for (int c = 0; c < n_cams; ++c) {
+            double* g = g_T_c + 7 * static_cast<int64_t>(c);
+            cam_pairs[c] = 0;
+            if (given_mask && given_mask[c]) {
+                for (int k = 0; k < 7; ++k) g[k] = g_T_c_given[7 * static_cast<int64_t>(c) + k];
+                cam_status[c] = CBA_HANDEYE_GIVEN;
+                continue;
+            }
+            for (int k = 0; k < 7; ++k) g[k] = k == 0 ? 1.0 : 0.0;
+            cam_status[c] = cam_start[c + 1] - cam_start[c] >= 2 ? CBA_HANDEYE_DLT : CBA_HANDEYE_TOO_FEW_VIEWS;
+        }
+        if (b_T_t_given) {
+            for (int k = 0; k < 7; ++k) b_T_t[k] = b_T_t_given[k];
+            *target_source = CBA_TARGET_CONFIG;
+        } else {
+            for (int k = 0; k < 7; ++k) b_T_t[k] = k == 0 ? 1.0 : 0.0;
+            *target_source = cam_start[n_cams] > 0 ? CBA_TARGET_ESTIMATED : CBA_TARGET_IDENTITY;
+        }
+        if (stage_ms)
+            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
+        if (n_blocks == 0) return;  // nothing for a device to do
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        bundle_seed_gpu(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, cam_start.data(), cam_blk.data(),
+                        g_T_c, cam_status, cam_pairs, b_T_t_given, b_T_t, blk_c_T_t, blk_ok, stage_ms, default_device());
+    });
+}
+
+cba_status cba_estimate_bundle_seed(int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g,
+                                    const double* X, const double* Y, const double* u, const double* v, const double* kmtx5,
+                                    double min_angle_deg, const int32_t* given_mask, const double* g_T_c_given, const double* b_T_t_given,
+                                    double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, double* b_T_t, int32_t* target_source,
+                                    double* blk_c_T_t, int32_t* blk_ok) {
+    return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, given_mask, g_T_c_given,
+                            b_T_t_given, g_T_c, cam_status, cam_pairs, b_T_t, target_source, blk_c_T_t, blk_ok, nullptr);
+}
+
 #ifdef CBA_EXPERIMENTS
 // Experiment builds only (tools/bench_extrinsic_seed.py): cba_estimate_extrinsic_dlt timing its stages on the device: stage_ms [4] =
 // block poses, camera averages, target averages, total (uploads excluded).  Not part of calibba.h.
@@ -1477,6 +1546,18 @@ __attribute__((visibility("default"))) cba_status cba_estimate_extrinsic_dlt_tim
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, nullptr, nullptr,
                               stage_ms);
+}
+
+// Experiment builds only (tools/bench_bundle_seed.py): cba_estimate_bundle_seed timing its stages on the device: stage_ms [6] =
+// block poses, pass 1 + rotation solve, pass 2 + translation solve, candidates + scan, total, scan alone (uploads excluded).
+// Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_estimate_bundle_seed_timed(
+    int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
+    const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, double* g_T_c, int32_t* cam_status,
+    int32_t* cam_pairs, double* b_T_t, int32_t* target_source, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, nullptr, nullptr, nullptr,
+                            g_T_c, cam_status, cam_pairs, b_T_t, target_source, nullptr, nullptr, stage_ms);
 }
 #endif
 

@@ -323,6 +323,14 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
 void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const int32_t* table,
                        const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r,
                        double* r_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
+// bundle_seed.hip: the hand-eye / bundle seed on the blocked layout of cba_optimize_bundle.  cam_start / cam_blk: each camera's list
+// (built and checked by the caller); g_T_c / cam_status in: the given or identity rows and GIVEN / TOO_FEW_VIEWS / DLT (the cameras
+// to estimate), out: the DLT cameras' results; b_T_t written only when b_T_t_given is NULL and some block is listed; blk_pose,
+// blk_ok, stage_ms [6] optional
+void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
+                     const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, const int32_t* cam_start,
+                     const int32_t* cam_blk, double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, const double* b_T_t_given,
+                     double* b_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -2,6 +2,7 @@
 // the linear seed of optimize_extrinsics (cba_optimize_extrinsics), on the same blocked layout.  Three kernels on one stream:
 //   k_ext_block_pose   one wavefront per (view, camera) block: seed_math.hpp::planar_seed_view with the block's camera K, the
 //                      code k_planar_seed (seed.hip) runs, so a block's pose is bitwise what cba_estimate_planar_pose_batch gives
+//                      (block_pose.hpp, shared with bundle_seed.hip)
 //   k_ext_cam_avg      one workgroup per camera c >= 1: lanes form T[v][c] T[v][0]^-1 and its quaternion for a chunk of views,
 //                      lane 0 then adds the chunk to the running sign-aligned sum in increasing view order (LDS hand-off)
 //   k_ext_target_avg   one lane per view: c_T_r[c]^-1 T[v][c] averaged over cameras in increasing c
@@ -9,31 +10,13 @@
 // order comes from (view, camera) and never from the order the blocks are listed in.
 #include <vector>
 
+#include "block_pose.hpp"
 #include "engine.hpp"
 #include "extrinsic_dlt_math.hpp"
 
 namespace cba {
 
-constexpr int EXT_WAVES = 4;    // block-pose kernel: wavefronts (blocks) per workgroup
 constexpr int EXT_CHUNK = 256;  // camera-average kernel: views per chunk = lanes per workgroup; target kernel: views per workgroup
-
-__global__ __launch_bounds__(64 * EXT_WAVES) void k_ext_block_pose(int n_blocks, const int64_t* __restrict__ off,
-                                                                   const int32_t* __restrict__ blk_cam, const double* __restrict__ X,
-                                                                   const double* __restrict__ Y, const double* __restrict__ u,
-                                                                   const double* __restrict__ v, const double* __restrict__ kmtx5,
-                                                                   double* __restrict__ pose7, int32_t* __restrict__ ok) {
-    const int i = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * EXT_WAVES + (threadIdx.x >> 6)));
-    if (i >= n_blocks) return;  // whole wave leaves together
-    double K[5], p[7];
-    const double* K5 = kmtx5 + 5 * static_cast<int64_t>(blk_cam[i]);
-    for (int k = 0; k < 5; ++k) K[k] = K5[k];
-    WaveCoop co;
-    const bool good = planar_seed_view(static_cast<int>(off[i + 1] - off[i]), X + off[i], Y + off[i], u + off[i], v + off[i], K, co, p);
-    if (co.lane() == 0) {
-        for (int k = 0; k < 7; ++k) pose7[7 * static_cast<int64_t>(i) + k] = p[k];
-        ok[i] = good ? 1 : 0;
-    }
-}
 
 // block b of (view, cam), or -1 when it is absent or has fewer than 4 points (the reference's skip rule, extrinsics.h:57, 68)
 __device__ __forceinline__ int ext_block(const int32_t* __restrict__ table, const int64_t* __restrict__ off, int n_cams, int view, int cam) {
@@ -143,9 +126,7 @@ void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk
         dcam.upload(blk_cam, n_blocks, stream);
         dtab.upload(table, n_tab, stream);
         tm.mark(0, stream);
-        hipLaunchKernelGGL(k_ext_block_pose, dim3((n_blocks + EXT_WAVES - 1) / EXT_WAVES), dim3(64 * EXT_WAVES), 0, stream, n_blocks,
-                           doff.p, dcam.p, dX.p, dY.p, du.p, dv.p, dK.p, dP.p, dok.p);
-        CBA_HIP(hipGetLastError());
+        launch_block_pose(n_blocks, doff.p, dcam.p, dX.p, dY.p, du.p, dv.p, dK.p, dP.p, dok.p, stream);
         tm.mark(1, stream);
         hipLaunchKernelGGL(k_ext_cam_avg, dim3(n_cams), dim3(EXT_CHUNK), 0, stream, n_views, n_cams, dtab.p, doff.p, dP.p, dC.p);
         CBA_HIP(hipGetLastError());

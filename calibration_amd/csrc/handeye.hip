@@ -8,15 +8,14 @@
 // two-level sum over workgroups (no atomics; bitwise reproducible).  Compute-bound: ~1.2 kFLOP per pair.
 #include <rccl/rccl.h>
 
+#include "axxb_pairs.hpp"
 #include "engine.hpp"
 #include "handeye_core.hpp"
 #include "seed_math.hpp"
-#include "wave_reduce.hpp"
 
 namespace cba {
 
-// MODE 0: the AX = XB residual blocks of optimize_handeye; MODE 1 / 2: the rotation / translation sums of the Tsai-Lenz
-// all-pairs seed estimate_handeye_dlt (handeyedlt.cpp:84-137) — same pair enumeration, same filter, same reduction.
+// one workgroup per (first pose i, 256 second poses): axxb_pair_tile (axxb_pairs.hpp)
 template <int MODE>
 __global__ __launch_bounds__(256) void k_axxb(int n, const double* __restrict__ poses /*[n][24]: Rb tb Rc tc*/,
                                               const double* __restrict__ X /*RX(9) tX(3)*/, double min_angle,
@@ -24,54 +23,18 @@ __global__ __launch_bounds__(256) void k_axxb(int n, const double* __restrict__ 
     __shared__ double sh[4][AXXB_NACC];
     const int i = i_first + blockIdx.y;  // this launch covers first poses [i_first, i_first + gridDim.y)
     const int j = blockIdx.x * 256 + threadIdx.x;
-    double acc[AXXB_NACC];
-#pragma unroll
-    for (int e = 0; e < AXXB_NACC; ++e) acc[e] = 0.0;
-    if (j > i && j < n) {
-        const double* pi = poses + 24 * static_cast<int64_t>(i);
-        const double* pj = poses + 24 * static_cast<int64_t>(j);
-        double RA[9], RB[9], tA[3], tB[3];
-        if (motion_pair(pi, pi + 9, pj, pj + 9, pi + 12, pi + 21, pj + 12, pj + 21, min_angle, axis_eps, RA, RB, tA, tB)) {
-            if (MODE == 0) {
-                double r[6], J[36];
-                axxb_point(X, X + 9, RA, RB, tA, tB, r, J);
-                axxb_accumulate(r, J, huber_delta, acc);
-            } else {
-                tsai_lenz_accumulate(MODE - 1, RA, RB, tA, tB, X, acc);
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < AXXB_NACC; ++e) {
-        const double v = wave_sum63(acc[e]);
-        if (lane == 63) sh[wave][e] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < AXXB_NACC)
-        partial[(static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * AXXB_NACC + threadIdx.x] =
-            (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    axxb_pair_tile<MODE>(n, poses, X, min_angle, axis_eps, huber_delta, i, j, sh,
+                         partial + (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * AXXB_NACC);
 }
 
-// out[b][e] = sum of rows [b * chunk, (b + 1) * chunk) of a row-major [n_rows][AXXB_NACC] table, in a FIXED order: thread
-// (column e, group r) adds rows r, r + 8, ... of the chunk, the 8 group sums are combined in group order through LDS.
+// out[b][e] = sum of rows [b * chunk, (b + 1) * chunk) of a row-major [n_rows][AXXB_NACC] table, in a FIXED order (axxb_rows_sum).
 // Applied twice (chunks of 64 rows, then the <= few hundred chunk sums) it replaces one wave walking all ~16 000 workgroup
 // partials of a 2000-pose problem serially (3.8 ms per evaluation, 17x the pair kernel itself).
 __global__ __launch_bounds__(256) void k_axxb_chunk_sum(int64_t n_rows, int64_t chunk, const double* __restrict__ rows,
                                                         double* __restrict__ out) {
     __shared__ double sh[8][32];
-    const int e = threadIdx.x & 31, r = threadIdx.x >> 5;
     const int64_t t0 = static_cast<int64_t>(blockIdx.x) * chunk, t1 = t0 + chunk < n_rows ? t0 + chunk : n_rows;
-    double s = 0.0;
-    if (e < AXXB_NACC)
-        for (int64_t t = t0 + r; t < t1; t += 8) s += rows[t * AXXB_NACC + e];
-    sh[r][e] = s;
-    __syncthreads();
-    if (r == 0 && e < AXXB_NACC) {
-        double tot = 0.0;
-        for (int k = 0; k < 8; ++k) tot += sh[k][e];
-        out[static_cast<int64_t>(blockIdx.x) * AXXB_NACC + e] = tot;
-    }
+    axxb_rows_sum(t0, t1, rows, sh, out + static_cast<int64_t>(blockIdx.x) * AXXB_NACC);
 }
 
 namespace {

@@ -26,6 +26,7 @@
  *   cba_optimize_homography     include/calib/estimation/optim/homography.h:17-18
  *                               (src/estimation/optim/homography.cpp:144-175)
  *   cba_estimate_extrinsic_dlt  include/calib/estimation/linear/extrinsics.h:27-78
+ *   cba_estimate_bundle_seed    src/pipeline/detail/bundle_utils.cpp:46-237 (+ estimate_handeye_dlt)
  *   cba_reproj_* (handle API)   the ceres::Problem the reference builds and solves inside those
  *                               functions (intrinsics.cpp:63-90, extrinsics.cpp:86-160,
  *                               bundle.cpp:83-133, detail/ceresutils.h:27-43,69-126); exposed so
@@ -611,6 +612,56 @@ cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5
 cba_status cba_estimate_extrinsic_dlt(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
                                       const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
                                       const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok);
+
+/* ---- seed of the hand-eye and bundle stages of a robot-mounted rig (src/pipeline/detail/bundle_utils.cpp:46-237 with
+ * estimate_handeye_dlt, src/estimation/linear/handeyedlt.cpp:126-137; stages src/pipeline/stages/handeye_stage.cpp,
+ * bundle_stage.cpp) ------------------------------------------------------------------------------------------------------------
+ *
+ * On the blocked layout of cba_optimize_bundle: block b holds the points [blk_offset[b], blk_offset[b+1]) seen by camera blk_cam[b]
+ * from robot pose blk_b_T_g[b] (row-major R (9) then t (3)).  kmtx5 [n_cams][5] = [fx, fy, cx, cy, skew].  The outputs feed
+ * cba_optimize_bundle directly: g_T_c [n_cams][7] and b_T_t [7] (pose7).
+ *   1. Every block's pose c_T_t is estimate_planar_pose with its camera's K: pixels normalised by K only, so DISTORTION IS IGNORED;
+ *      a block's pose is bitwise what cba_estimate_planar_pose_batch returns for it (blk_c_T_t, blk_ok; both may be NULL).
+ *   2. Camera c's pose list (the reference's SensorAccumulator, bundle_utils.cpp:126-127) is its blocks of >= 4 points in
+ *      increasing block index: collect_bundle_observations appends in view order and observations are listed view-major.
+ *   3. compute_handeye_initialization (bundle_utils.cpp:154-200), per camera:
+ *        given_mask[c] != 0 -> g_T_c_given[c] is copied, status GIVEN (a successful hand-eye stage result; no DLT is run);
+ *        fewer than 2 listed blocks -> the identity, TOO_FEW_VIEWS ("insufficient_observations");
+ *        otherwise estimate_handeye_dlt over the list at min_angle_deg: all pairs i < j, the pair filter of build_all_pairs
+ *        (axis eps 1e-3), the Tsai-Lenz rotation then translation ridge solves (1e-12).  cam_pairs[c] = pairs that pass the filter.
+ *        No pair -> the identity, NO_PAIRS (the reference's "No valid motion pairs after filtering. Increase motion or relax
+ *        thresholds."); else DLT.  The per-camera sums are reduced in the order cba_estimate_handeye_dlt reduces one pose list.
+ *   4. choose_initial_target (bundle_utils.cpp:202-237): b_T_t_given non-NULL -> copied, CONFIG.  Otherwise the candidates
+ *      b_T_g * g_T_c[c] * c_T_t of every listed block, camera-major and then in list order (a camera whose seed failed takes part
+ *      with its identity g_T_c, as in the reference), are averaged by average_isometries with its sequential sign rule
+ *      (se3_utils.h:75-95): ESTIMATED; no candidate -> the identity, IDENTITY.
+ * A camera's g_T_c depends only on its own blocks and their order, b_T_t only on each camera's own order: interleaving different
+ * cameras' blocks changes neither, and two identical calls are bitwise identical.
+ * Departures: a singular Tsai-Lenz system gives SINGULAR and the identity (the reference's LDLT returns whatever it returns, as
+ * cba_estimate_handeye_dlt does); a block of >= 4 points whose fit fails gets the identity pose and blk_ok = 0 but stays in its
+ * camera's list, because the reference's skip rule counts points only (as cba_estimate_extrinsic_dlt).
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all before any device work): n_cams < 1, n_blocks < 0, offsets not starting at 0 or
+ * decreasing, a blk_cam out of range, a negative or non-finite min_angle_deg, a NULL required pointer, given_mask without
+ * g_T_c_given.  n_blocks == 0 needs no device; otherwise no device -> CBA_ERR_NO_DEVICE. */
+enum {
+    CBA_HANDEYE_DLT = 0,           /* estimated here */
+    CBA_HANDEYE_GIVEN = 1,         /* copied from g_T_c_given */
+    CBA_HANDEYE_TOO_FEW_VIEWS = 2, /* fewer than 2 listed blocks: identity */
+    CBA_HANDEYE_NO_PAIRS = 3,      /* no motion pair passes the filter: identity */
+    CBA_HANDEYE_SINGULAR = 4       /* a singular Tsai-Lenz system: identity */
+};
+enum {
+    CBA_TARGET_ESTIMATED = 0, /* averaged from the candidates */
+    CBA_TARGET_CONFIG = 1,    /* copied from b_T_t_given */
+    CBA_TARGET_IDENTITY = 2   /* no candidate */
+};
+cba_status cba_estimate_bundle_seed(int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam,
+                                    const double* blk_b_T_g /*[n_blocks][12]*/, const double* X, const double* Y, const double* u,
+                                    const double* v, const double* kmtx5 /*[n_cams][5]*/, double min_angle_deg,
+                                    const int32_t* given_mask /*[n_cams] or NULL*/, const double* g_T_c_given /*[n_cams][7] or NULL*/,
+                                    const double* b_T_t_given /*[7] or NULL*/, double* g_T_c /*[n_cams][7]*/,
+                                    int32_t* cam_status /*[n_cams]*/, int32_t* cam_pairs /*[n_cams]*/, double* b_T_t /*[7]*/,
+                                    int32_t* target_source, double* blk_c_T_t /*[n_blocks][7] or NULL*/, int32_t* blk_ok /*or NULL*/);
 
 #ifdef __cplusplus
 }
