@@ -69,5 +69,18 @@ from .handeye_rig import (  # noqa: F401
     estimate_bundle_seed,
     estimate_bundle_seed_blocks,
 )
+from .distortion import (  # noqa: F401
+    DistortionWithResiduals,
+    DualDistortionWithResiduals,
+    PinholeBrownConrady,
+    estimate_intrinsics_linear,
+    estimate_intrinsics_linear_batch,
+    estimate_intrinsics_linear_iterative,
+    estimate_intrinsics_linear_iterative_batch,
+    fit_distortion,
+    fit_distortion_batch,
+    fit_distortion_dual,
+    fit_distortion_full,
+)
 
 __version__ = "0.1.0"

@@ -20,6 +20,9 @@ CHAIN_INTRINSIC, CHAIN_EXTRINSIC, CHAIN_BUNDLE = 0, 1, 2
 # cba_estimate_bundle_seed: per-camera status, initial-target source (calibba.h)
 HANDEYE_DLT, HANDEYE_GIVEN, HANDEYE_TOO_FEW_VIEWS, HANDEYE_NO_PAIRS, HANDEYE_SINGULAR = range(5)
 TARGET_ESTIMATED, TARGET_CONFIG, TARGET_IDENTITY = range(3)
+# cba_estimate_intrinsics_linear(_iterative)_batch: per-problem status (calibba.h)
+LINEAR_OK, LINEAR_TOO_FEW, LINEAR_DEGENERATE = range(3)
+LINEAR_MAX_ITERATIONS = 65536
 CAMERA_PINHOLE_BC, CAMERA_SCHEIMPFLUG = 0, 1
 TERM_CONVERGENCE, TERM_NO_CONVERGENCE, TERM_FAILURE = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
@@ -317,6 +320,15 @@ PROTOTYPES = {
         C.c_int32, [C.c_int32, C.c_int32, c_int64_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                     C.c_double, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_double_p,
                     c_int32_p]),
+    "cba_fit_distortion_batch": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, c_int32_p,
+                    c_double_p, C.c_int32, c_double_p, c_double_p, c_int32_p, c_double_p]),
+    "cba_estimate_intrinsics_linear_batch": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p,
+                    c_int32_p, c_int32_p]),
+    "cba_estimate_intrinsics_linear_iterative_batch": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                    c_double_p, c_int32_p, c_int32_p, c_int32_p]),
 }
 
 

@@ -1537,6 +1537,98 @@ cba_status cba_estimate_bundle_seed(int32_t n_cams, int32_t n_blocks, const int6
                             b_T_t_given, g_T_c, cam_status, cam_pairs, b_T_t, target_source, blk_c_T_t, blk_ok, nullptr);
 }
 
+// ---- distortion fits and the linear intrinsic estimators (distortion_fit.hip, distortion_fit_math.hpp) ----------------------
+static void check_problems(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v) {
+    if (n_problems < 0) throw std::invalid_argument("n_problems must be >= 0");
+    if (n_problems == 0) return;
+    if (!offset) throw std::invalid_argument("null argument");
+    if (offset[0] != 0) throw std::invalid_argument("offsets must start at 0");
+    for (int p = 0; p < n_problems; ++p)
+        if (offset[p + 1] < offset[p]) throw std::invalid_argument("offsets must not decrease");
+    if (offset[n_problems] > 0 && (!x || !y || !u || !v)) throw std::invalid_argument("null argument");
+}
+
+static void check_num_radial(int32_t num_radial) {
+    if (num_radial < 0 || num_radial > 3) throw std::invalid_argument("num_radial must be in [0, 3]");
+}
+
+static cba_status fit_distortion_impl(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
+                                      const double* v, const double* kmtx5, int32_t num_radial, int32_t n_fixed, const int32_t* fixed_idx,
+                                      const double* fixed_val, int32_t dual, double* coeffs, double* inverse, int32_t* ok,
+                                      double* residuals, double* stage_ms) {
+    return guarded([&] {
+        check_problems(n_problems, offset, x, y, u, v);
+        check_num_radial(num_radial);
+        const int m = num_radial + 2;
+        if (n_fixed < 0) throw std::invalid_argument("n_fixed must be >= 0");
+        if (n_fixed > 0 && !fixed_idx) throw std::invalid_argument("null argument");
+        int mask = 0;
+        double val[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int i = 0; i < n_fixed; ++i) {
+            const int idx = fixed_idx[i];
+            if (idx < 0 || idx >= m) throw std::invalid_argument("Fixed distortion index out of range");
+            if (mask >> idx & 1) continue;  // the first in input order wins
+            mask |= 1 << idx;
+            val[idx] = fixed_val ? fixed_val[i] : 0.0;
+        }
+        if (dual && !inverse) throw std::invalid_argument("dual needs inverse");
+        if (stage_ms)
+            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
+        if (n_problems == 0) return;
+        if (!kmtx5 || !coeffs || !ok) throw std::invalid_argument("null argument");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        distortion_fit_gpu(n_problems, offset, x, y, u, v, kmtx5, num_radial, mask, val, dual != 0, coeffs, inverse, ok, residuals, stage_ms,
+                           default_device());
+    });
+}
+
+cba_status cba_fit_distortion_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
+                                    const double* v, const double* kmtx5, int32_t num_radial, int32_t n_fixed, const int32_t* fixed_idx,
+                                    const double* fixed_val, int32_t dual, double* coeffs, double* inverse, int32_t* ok, double* residuals) {
+    return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, n_fixed, fixed_idx, fixed_val, dual, coeffs, inverse, ok,
+                               residuals, nullptr);
+}
+
+cba_status cba_estimate_intrinsics_linear_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
+                                                const double* u, const double* v, const double* bounds_lo5, const double* bounds_hi5,
+                                                int32_t use_skew, double* kmtx5, int32_t* status, int32_t* fallback) {
+    return guarded([&] {
+        check_problems(n_problems, offset, x, y, u, v);
+        if (!bounds_lo5 != !bounds_hi5) throw std::invalid_argument("bounds_lo5 and bounds_hi5 go together");
+        if (n_problems == 0) return;
+        if (!kmtx5 || !status || !fallback) throw std::invalid_argument("null argument");
+        const double dlo[5] = {0.0, 0.0, 0.0, 0.0, -0.01}, dhi[5] = {2000.0, 2000.0, 1280.0, 720.0, 0.01};  // CalibrationBounds{}
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        intrinsics_linear_gpu(n_problems, offset, x, y, u, v, bounds_lo5 ? bounds_lo5 : dlo, bounds_hi5 ? bounds_hi5 : dhi, use_skew != 0,
+                              kmtx5, status, fallback, default_device());
+    });
+}
+
+static cba_status linear_iterative_impl(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
+                                        const double* v, int32_t num_radial, int32_t max_iterations, int32_t use_skew, double* kmtx5,
+                                        double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback, double* stage_ms) {
+    return guarded([&] {
+        check_problems(n_problems, offset, x, y, u, v);
+        check_num_radial(num_radial);
+        if (max_iterations > CBA_LINEAR_MAX_ITERATIONS) throw std::invalid_argument("max_iterations above CBA_LINEAR_MAX_ITERATIONS");
+        if (stage_ms)
+            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
+        if (n_problems == 0) return;
+        if (!kmtx5 || !coeffs || !status || !iterations || !fallback) throw std::invalid_argument("null argument");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        intrinsics_linear_iterative_gpu(n_problems, offset, x, y, u, v, num_radial, std::max(max_iterations, 0), use_skew != 0, kmtx5, coeffs,
+                                        status, iterations, fallback, stage_ms, default_device());
+    });
+}
+
+cba_status cba_estimate_intrinsics_linear_iterative_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
+                                                          const double* u, const double* v, int32_t num_radial, int32_t max_iterations,
+                                                          int32_t use_skew, double* kmtx5, double* coeffs, int32_t* status,
+                                                          int32_t* iterations, int32_t* fallback) {
+    return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status, iterations,
+                                 fallback, nullptr);
+}
+
 #ifdef CBA_EXPERIMENTS
 // Experiment builds only (tools/bench_extrinsic_seed.py): cba_estimate_extrinsic_dlt timing its stages on the device: stage_ms [4] =
 // block poses, camera averages, target averages, total (uploads excluded).  Not part of calibba.h.
@@ -1558,6 +1650,24 @@ __attribute__((visibility("default"))) cba_status cba_estimate_bundle_seed_timed
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, nullptr, nullptr, nullptr,
                             g_T_c, cam_status, cam_pairs, b_T_t, target_source, nullptr, nullptr, stage_ms);
+}
+// Experiment builds only (tools/bench_distortion.py): the distortion fit and the iterative estimator timing their stages on the
+// device: stage_ms [6] = moment passes, chunk sums, uploads, tail, residuals, total without uploads.  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_fit_distortion_batch_timed(
+    int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, const double* kmtx5,
+    int32_t num_radial, int32_t dual, double* coeffs, double* inverse, int32_t* ok, double* residuals, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, 0, nullptr, nullptr, dual, coeffs, inverse, ok, residuals,
+                               stage_ms);
+}
+
+__attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_linear_iterative_batch_timed(
+    int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, int32_t num_radial,
+    int32_t max_iterations, int32_t use_skew, double* kmtx5, double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback,
+    double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status, iterations,
+                                 fallback, stage_ms);
 }
 #endif
 

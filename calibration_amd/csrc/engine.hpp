@@ -331,6 +331,17 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
                      const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, const int32_t* cam_start,
                      const int32_t* cam_blk, double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, const double* b_T_t_given,
                      double* b_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
+// distortion_fit.hip: fit_distortion_full / _dual and estimate_intrinsics_linear(_iterative) over a batch of problems (offset
+// [P+1], checked by the caller).  fixed_mask / fixed_val5: the resolved fixed coefficients; residuals, stage_ms [6] optional
+void distortion_fit_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                        const double* kmtx5, int num_radial, int fixed_mask, const double* fixed_val5, bool dual, double* coeffs,
+                        double* inverse, int32_t* ok, double* residuals, double* stage_ms, int device);
+void intrinsics_linear_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                           const double* bounds_lo5, const double* bounds_hi5, int use_skew, double* kmtx5, int32_t* status,
+                           int32_t* fallback, int device);
+void intrinsics_linear_iterative_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                                     int num_radial, int max_iterations, int use_skew, double* kmtx5, double* coeffs, int32_t* status,
+                                     int32_t* iterations, int32_t* fallback, double* stage_ms, int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -663,6 +663,74 @@ cba_status cba_estimate_bundle_seed(int32_t n_cams, int32_t n_blocks, const int6
                                     int32_t* cam_status /*[n_cams]*/, int32_t* cam_pairs /*[n_cams]*/, double* b_T_t /*[7]*/,
                                     int32_t* target_source, double* blk_c_T_t /*[n_blocks][7] or NULL*/, int32_t* blk_ok /*or NULL*/);
 
+/* ---- distortion fits and the iterative linear intrinsic seed (include/calib/models/distortion.h:229-406;
+ * include/calib/estimation/linear/intrinsics.h:60-70, src/estimation/linear/intrinsicsdlt.cpp:147-368) ----------------------
+ *
+ * Batched over independent problems: problem p owns the observations [offset[p], offset[p+1]) of x, y (normalised, undistorted)
+ * and u, v (pixels), the reference's Observation (distortion.h:69-72).  kmtx5 = [fx, fy, cx, cy, skew]; coefficients are
+ * [k1 .. k_nr, p1, p2] (m = num_radial + 2 per problem).  One data pass forms each problem's moments (distortion_fit_math.hpp);
+ * the solves and the alternation then run on the moments alone.  Results are bitwise reproducible: a problem's result does not
+ * depend on its position in the batch or on the other problems, and two identical calls agree bit for bit.
+ *
+ * cba_fit_distortion_batch: fit_distortion_full (:231-363) of every problem at its kmtx5, coeffs [P][m], ok [P] (0 where the
+ * reference returns nullopt: fewer than 8 observations; coeffs are then 0), residuals [2 N] (optional: design * alpha - rhs, rows
+ * 2i and 2i + 1 of observation i; 0 for problems with ok = 0).  dual = 1: fit_distortion_dual (:373-406), whose inverse fit runs on
+ * ((u - cx - skew y_d) / fx, (v - cy) / fy) -> the undistorted pixels, with the same fixed set; inverse [P][m] is then required and
+ * the residuals are the forward fit's.  Fixed coefficients (fixed_idx [n_fixed], fixed_val [n_fixed] or NULL, the same for every
+ * problem): an index outside [0, m - 1] is CBA_ERR_INVALID_ARGUMENT (:315-318); a NULL fixed_val holds every fixed value at 0 (the
+ * reference's missing values); fixed entries come back bit-exact; with every coefficient fixed, alpha is the fixed values and the
+ * residuals are still computed (:334-337).
+ * cba_estimate_intrinsics_linear_batch: estimate_intrinsics_linear (:289-312) with CalibrationBounds bounds_lo5 / bounds_hi5
+ * ([fx, fy, cx, cy, skew]; both NULL select CalibrationBounds{}, as nullopt does).  status [P]; fallback [P] = 1 where
+ * apply_bounds_and_fallback took its fallback (the reference's stderr warning).  use_skew is honoured.
+ * cba_estimate_intrinsics_linear_iterative_batch: estimate_intrinsics_linear_iterative (:319-368).  Kept from the reference:
+ *   - every K fit uses the DEFAULT bounds (it passes nullopt, :323, :343), so K outside fx, fy <= 2000, cx <= 1280, cy <= 720,
+ *     |skew| <= 0.01 takes the fallback: fx, fy -> clamp(max(500, f)); cx, cy -> clamp(mean(u_corr) / 2), clamp(mean(v_corr) / 2);
+ *     skew -> clamp(skew) when use_skew, else 0.  fallback [P] counts the fits of K (the initial one included) that took it;
+ *   - the loop breaks when the distortion fit fails (fewer than 8 observations) or the K refit fails, and stops when
+ *     Σ|ΔK| < 1e-6, compared against the post-fallback K; iterations [P] counts the K refits adopted;
+ *   - the final fit failing (fewer than 8 observations) gives TOO_FEW; use_skew is honoured.
+ *   kmtx5 [P][5] and coeffs [P][m] are 0 where status != OK.
+ * Departures:
+ *   (a) normal equations from fixed-order moments replace JacobiSVD.  The distortion fit's m x m Gram (of the free columns) is
+ *       column-equilibrated and eigen-decomposed by cyclic Jacobi; eigenvalues <= 1e-13 lambda_max are dropped and the
+ *       minimum-norm solution (in the coefficients' own scale) is returned, which is what svd.solve returns up to the cutoff.
+ *       JacobiSVD's own rank cutoff is relative too (about 1e-15 of sigma_max), so the distortion fits differ only for designs whose
+ *       equilibrated singular-value ratio lies between about 1e-15 and 3.2e-7, which the Gram cannot resolve.
+ *       The K fit's sigma_min < 1e-12 test is ABSOLUTE in the reference, so it depends on the scale of the data; here it becomes
+ *       the relative test lambda_min <= 1e-13 lambda_max on the equilibrated 2 x 2 / 3 x 3 Gram.  Both reject identical x (or y)
+ *       values.  They differ in two places: this test rejects a spread of x or y below ~4.5e-7 of its mean, which the reference
+ *       may accept; and the reference rejects a well-conditioned design whose x or y values are all tiny in magnitude (sigma_min
+ *       below 1e-12 in absolute terms), which this test accepts.  Neither arises with normalised coordinates of a real camera.
+ *   (b) num_radial must be in [0, 3].
+ *   (c) max_iterations is at most CBA_LINEAR_MAX_ITERATIONS; a negative value means 0, as in the reference.
+ *   (d) duplicate fixed indices: the first in input order wins (the reference's sort + unique leaves it unspecified).
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): n_problems < 0; NULL required pointers; offsets not
+ * starting at 0 or decreasing; num_radial outside [0, 3]; n_fixed < 0 or a fixed index out of range; dual without inverse; one
+ * bounds pointer NULL and not the other; max_iterations above CBA_LINEAR_MAX_ITERATIONS.  n_problems == 0 is no work; otherwise
+ * no device -> CBA_ERR_NO_DEVICE.
+ * Order of checks: the fixed set is one per call, so cba_fit_distortion_batch rejects a fixed index out of range for the whole
+ * batch, even when every problem has fewer than 8 observations.  The reference returns nullopt for fewer than 8 observations
+ * before it looks at the indices (distortion.h:235-238, 315-318); the single-problem wrappers (Python calibration_amd.distortion,
+ * C++ calibba_distortion.hpp) restore that order by returning nullopt / None before they call the batch. */
+#define CBA_LINEAR_MAX_ITERATIONS 65536
+enum {
+    CBA_LINEAR_OK = 0,
+    CBA_LINEAR_TOO_FEW = 1,    /* < 2 observations for a K fit, < 8 for a distortion fit (the iterative estimator's final fit) */
+    CBA_LINEAR_DEGENERATE = 2  /* a K fit's design is rank-deficient */
+};
+cba_status cba_fit_distortion_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
+                                    const double* v, const double* kmtx5 /*[P][5]*/, int32_t num_radial, int32_t n_fixed,
+                                    const int32_t* fixed_idx, const double* fixed_val, int32_t dual, double* coeffs /*[P][m]*/,
+                                    double* inverse /*[P][m] or NULL*/, int32_t* ok /*[P]*/, double* residuals /*[2 N] or NULL*/);
+cba_status cba_estimate_intrinsics_linear_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
+                                                const double* u, const double* v, const double* bounds_lo5, const double* bounds_hi5,
+                                                int32_t use_skew, double* kmtx5 /*[P][5]*/, int32_t* status, int32_t* fallback);
+cba_status cba_estimate_intrinsics_linear_iterative_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
+                                                          const double* u, const double* v, int32_t num_radial, int32_t max_iterations,
+                                                          int32_t use_skew, double* kmtx5 /*[P][5]*/, double* coeffs /*[P][m]*/,
+                                                          int32_t* status, int32_t* iterations, int32_t* fallback);
+
 #ifdef __cplusplus
 }
 #endif
