@@ -82,5 +82,12 @@ from .distortion import (  # noqa: F401
     fit_distortion_dual,
     fit_distortion_full,
 )
+from .camera import (  # noqa: F401
+    UndistortMap,
+    distort,
+    project,
+    undistort,
+    unproject,
+)
 
 __version__ = "0.1.0"

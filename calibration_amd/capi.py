@@ -24,6 +24,9 @@ TARGET_ESTIMATED, TARGET_CONFIG, TARGET_IDENTITY = range(3)
 LINEAR_OK, LINEAR_TOO_FEW, LINEAR_DEGENERATE = range(3)
 LINEAR_MAX_ITERATIONS = 65536
 CAMERA_PINHOLE_BC, CAMERA_SCHEIMPFLUG = 0, 1
+# cba_undistort_map_apply: image element types (calibba.h)
+DTYPE_U8, DTYPE_F32 = 0, 1
+IMAGE_MAX_SIDE = 32768
 TERM_CONVERGENCE, TERM_NO_CONVERGENCE, TERM_FAILURE = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
 
@@ -329,6 +332,14 @@ PROTOTYPES = {
     "cba_estimate_intrinsics_linear_iterative_batch": (
         C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p,
                     c_double_p, c_int32_p, c_int32_p, c_int32_p]),
+    "cba_camera_project": (C.c_int32, [C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    "cba_camera_unproject": (C.c_int32, [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int64, c_double_p, c_double_p]),
+    "cba_undistort_map_create": (
+        C.c_int32, [C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_undistort_map_fetch": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cba_undistort_map_apply": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "cba_undistort_map_destroy": (None, [C.c_void_p]),
 }
 
 

@@ -1671,4 +1671,137 @@ __attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_linear
 }
 #endif
 
+// ---- camera models (camera.hip, camera_math.hpp) ----------------------------------------------------------------------------
+static void check_camera(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs) {
+    if (camera_model != CBA_CAMERA_PINHOLE_BC && camera_model != CBA_CAMERA_SCHEIMPFLUG) throw std::invalid_argument("bad camera model");
+    if (!intr) throw std::invalid_argument("null argument");
+    if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV))
+        throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
+}
+
+static void check_side(int32_t s) {
+    if (s < 1 || s > CBA_IMAGE_MAX_SIDE) throw std::invalid_argument("image width and height must be in [1, 32768]");
+}
+
+static cba_status camera_project_impl(int32_t camera_model, const double* intr, int64_t n, const double* xyz, double* uv, double* stage_ms) {
+    return guarded([&] {
+        check_camera(camera_model, intr, 0, nullptr);
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (n == 0) return;
+        if (!xyz || !uv) throw std::invalid_argument("null argument");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        camera_project_gpu(camera_model, intr, n, xyz, uv, stage_ms, default_device());
+    });
+}
+
+static cba_status camera_unproject_impl(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                        int64_t n, const double* uv, double* xy, double* stage_ms) {
+    return guarded([&] {
+        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (n == 0) return;
+        if (!uv || !xy) throw std::invalid_argument("null argument");
+        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        camera_unproject_gpu(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, n, uv, xy, stage_ms, default_device());
+    });
+}
+
+cba_status cba_camera_project(int32_t camera_model, const double* intr, int64_t n, const double* xyz, double* uv) {
+    return camera_project_impl(camera_model, intr, n, xyz, uv, nullptr);
+}
+
+cba_status cba_camera_unproject(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int64_t n,
+                                const double* uv, double* xy) {
+    return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, nullptr);
+}
+
+static cba_status undistort_map_create_impl(int32_t camera_model, int32_t n_cams, const double* intr, const double* R, const double* new_k5,
+                                            int32_t width, int32_t height, int32_t device, cba_undistort_map** out, double* stage_ms) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        check_camera(camera_model, intr, 0, nullptr);
+        if (n_cams < 1) throw std::invalid_argument("n_cams must be >= 1");
+        check_side(width);
+        check_side(height);
+        const int ni = camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10;
+        for (int c = 0; c < n_cams; ++c) {
+            const double* k = new_k5 ? new_k5 + 5 * static_cast<size_t>(c) : intr + static_cast<size_t>(c) * ni;
+            if (k[0] == 0.0 || k[1] == 0.0) throw std::invalid_argument("fx' and fy' must not be 0");
+        }
+        const int ndev = device_count();
+        if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+        *out = reinterpret_cast<cba_undistort_map*>(undistort_map_create(camera_model, n_cams, intr, R, new_k5, width, height, stage_ms, device));
+    });
+}
+
+cba_status cba_undistort_map_create(int32_t camera_model, int32_t n_cams, const double* intr, const double* R, const double* new_k5,
+                                    int32_t width, int32_t height, int32_t device, cba_undistort_map** out) {
+    return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, nullptr);
+}
+
+cba_status cba_undistort_map_fetch(cba_undistort_map* h, float* map_x, float* map_y) {
+    return guarded([&] {
+        if (!h || !map_x || !map_y) throw std::invalid_argument("null argument");
+        undistort_map_fetch(reinterpret_cast<UndistortMap*>(h), map_x, map_y);
+    });
+}
+
+static cba_status undistort_map_apply_impl(cba_undistort_map* h, int32_t n_images, const int32_t* cam, int32_t src_width, int32_t src_height,
+                                           int32_t channels, int32_t dtype, double border, const void* src, void* dst, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        if (n_images < 0) throw std::invalid_argument("n_images must be >= 0");
+        check_side(src_width);
+        check_side(src_height);
+        if (channels < 1 || channels > 4) throw std::invalid_argument("channels must be in 1..4");
+        if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
+        if (n_images == 0) return;
+        if (!cam || !src || !dst) throw std::invalid_argument("null argument");
+        UndistortMap* m = reinterpret_cast<UndistortMap*>(h);
+        const int n_cams = undistort_map_cams(m);
+        for (int i = 0; i < n_images; ++i)
+            if (cam[i] < 0 || cam[i] >= n_cams) throw std::invalid_argument("camera index out of range");
+        undistort_map_apply(m, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
+    });
+}
+
+cba_status cba_undistort_map_apply(cba_undistort_map* h, int32_t n_images, const int32_t* cam, int32_t src_width, int32_t src_height,
+                                   int32_t channels, int32_t dtype, double border, const void* src, void* dst) {
+    return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, nullptr);
+}
+
+void cba_undistort_map_destroy(cba_undistort_map* h) { undistort_map_destroy(reinterpret_cast<UndistortMap*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_camera.py): the camera entry points timing their stages on the device: stage_ms [3] = upload,
+// kernel, download.  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_camera_project_timed(int32_t camera_model, const double* intr, int64_t n,
+                                                                           const double* xyz, double* uv, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return camera_project_impl(camera_model, intr, n, xyz, uv, stage_ms);
+}
+__attribute__((visibility("default"))) cba_status cba_camera_unproject_timed(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs,
+                                                                             const double* inverse_coeffs, int64_t n, const double* uv,
+                                                                             double* xy, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, stage_ms);
+}
+__attribute__((visibility("default"))) cba_status cba_undistort_map_create_timed(int32_t camera_model, int32_t n_cams, const double* intr,
+                                                                                 const double* R, const double* new_k5, int32_t width,
+                                                                                 int32_t height, int32_t device, cba_undistort_map** out,
+                                                                                 double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, stage_ms);
+}
+__attribute__((visibility("default"))) cba_status cba_undistort_map_apply_timed(cba_undistort_map* h, int32_t n_images, const int32_t* cam,
+                                                                                int32_t src_width, int32_t src_height, int32_t channels,
+                                                                                int32_t dtype, double border, const void* src, void* dst,
+                                                                                double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
+}
+#endif
+
 }  // extern "C"

@@ -342,6 +342,19 @@ void intrinsics_linear_gpu(int n_problems, const int64_t* offset, const double* 
 void intrinsics_linear_iterative_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
                                      int num_radial, int max_iterations, int use_skew, double* kmtx5, double* coeffs, int32_t* status,
                                      int32_t* iterations, int32_t* fallback, double* stage_ms, int device);
+// camera.hip: project / unproject of caller points (intr: 10 | 12 entries; inv: n_inv inverse coefficients or NULL) and the
+// undistortion / rectification map handle (checked by the caller; stage_ms [3] optional: upload, kernel, download)
+void camera_project_gpu(int model, const double* intr, int64_t n, const double* xyz, double* uv, double* stage_ms, int device);
+void camera_unproject_gpu(int model, const double* intr, int n_inv, const double* inv, int64_t n, const double* uv, double* xy,
+                          double* stage_ms, int device);
+struct UndistortMap;
+UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, const double* R9, const double* new_k5, int W, int H,
+                                   double* stage_ms, int device);
+void undistort_map_fetch(UndistortMap* m, float* map_x, float* map_y);
+void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int sw, int sh, int ch, int dtype, double border,
+                         const void* src, void* dst, double* stage_ms);
+void undistort_map_destroy(UndistortMap* m) noexcept;
+int undistort_map_cams(const UndistortMap* m);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -731,6 +731,55 @@ cba_status cba_estimate_intrinsics_linear_iterative_batch(int32_t n_problems, co
                                                           int32_t use_skew, double* kmtx5 /*[P][5]*/, double* coeffs /*[P][m]*/,
                                                           int32_t* status, int32_t* iterations, int32_t* fallback);
 
+/* ---- camera models: project, unproject and undistortion / rectification maps (include/calib/models/pinhole.h:96-113,
+ * scheimpflug.h:139-181, distortion.h:119-160, 208-218) ----------------------------------------------------------------------
+ *
+ * A camera is described as for cba_calibrate_laser_plane: camera_model CBA_CAMERA_PINHOLE_BC or CBA_CAMERA_SCHEIMPFLUG, intr [10 | 12];
+ * where an inverse is needed, inverse_coeffs [n_inverse_coeffs] (n in [2, 16], [k1 .. k_nr, p1, p2]) select DualDistortion's one-step
+ * undistortion and NULL BrownConrady's 5-step fixed point.  All arithmetic is fp64 unless stated.
+ *
+ * cba_camera_project: uv [n][2] = project(xyz [n][3]) (camera frame), the reference's project(xyz) with its Scheimpflug form, in the
+ * expression order of the reprojection residual, with the Horner radial polynomial.  No masking: z <= 0, or a Scheimpflug sensor denominator
+ * <= 0, gives whatever the division gives, as in the reference.  xyz = (x, y, 1) is project(norm_xy); with intr = [1, 1, 0, 0, 0,
+ * k1, k2, k3, p1, p2] it is the distortion's distort.
+ * cba_camera_unproject: xy [n][2] = the normalised coordinates of pixels uv [n][2]: the pinhole's unproject (normalize, then
+ * undistort); for Scheimpflug the exact inverse of the projection that cba_calibrate_laser_plane documents and runs.
+ *
+ * cba_undistort_map: a handle that owns the maps on one device and one stream.  cba_undistort_map_create takes n_cams cameras of one
+ * model, intr [n_cams][10 | 12], an optional rectifying rotation per camera R [n_cams][9] (row-major; NULL: identity), an optional
+ * new camera matrix per camera new_k5 [n_cams][5] ([fx', fy', cx', cy', skew']; NULL: each camera's own K) and one output size
+ * width x height.  For every output pixel centre (u', v') (integer coordinates) of every camera it computes on the device
+ *   y = (v' - cy') / fy',  x = (u' - cx' - skew' y) / fx',  P = R^T (x, y, 1),  (map_x, map_y) = project(P) rounded to nearest float32;
+ * a ray with z <= 0 (pinhole) or a sensor denominator <= 0 (Scheimpflug) gives NaN in both.  The maps are [n_cams][height][width]
+ * float32, the layout of OpenCV's remap.  cba_undistort_map_fetch downloads them (map_x, map_y [n_cams][height][width]).
+ * cba_undistort_map_apply resamples n_images source images src [n_images][src_height][src_width][channels] (channels 1..4,
+ * interleaved; dtype CBA_DTYPE_U8 or CBA_DTYPE_F32) through the maps of cameras cam [n_images] into dst
+ * [n_images][height][width][channels].  Bilinear with a constant border: a tap outside the source reads the border value; a NaN map
+ * coordinate, or one beyond +-2^24, gives the border value for the pixel.  The maps never leave the device.  Arithmetic:
+ *   uint8    OpenCV's fixed-point rule: X = rintf(32 map_x) (round half to even), x0 = X >> 5, a = X & 31 (the same for y, b);
+ *            weights (32-a)(32-b)32, a(32-b)32, (32-a)b32 and ab32 of the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1),
+ *            which sum to 2^15; the result is (sum w p + 2^14) >> 15, saturated: exact integers.  The border is rounded half to
+ *            even and clamped to [0, 255] (NaN: 0).
+ *   float32  x0 = floorf(map_x), fx = map_x - x0 (the same for y); t = p00 + fx (p01 - p00), b = p10 + fx (p11 - p10),
+ *            result = t + fy (b - t) in fp32; the border is converted to float32.
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL required pointers; an unknown model; an inverse count
+ * outside [2, 16]; n < 0; n_cams < 1; width, height, src_width or src_height outside [1, 32768]; fx' or fy' equal to 0; n_images < 0;
+ * a camera index out of range; channels outside 1..4; an unknown dtype.  n == 0 (n_images == 0) is no work; otherwise no device ->
+ * CBA_ERR_NO_DEVICE. */
+enum { CBA_DTYPE_U8 = 0, CBA_DTYPE_F32 = 1 };
+#define CBA_IMAGE_MAX_SIDE 32768
+cba_status cba_camera_project(int32_t camera_model, const double* intr, int64_t n, const double* xyz /*[n][3]*/, double* uv /*[n][2]*/);
+cba_status cba_camera_unproject(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int64_t n,
+                                const double* uv /*[n][2]*/, double* xy /*[n][2]*/);
+typedef struct cba_undistort_map cba_undistort_map; /* opaque: owns the maps on the device + one HIP stream */
+cba_status cba_undistort_map_create(int32_t camera_model, int32_t n_cams, const double* intr, const double* R /*[n_cams][9] or NULL*/,
+                                    const double* new_k5 /*[n_cams][5] or NULL*/, int32_t width, int32_t height, int32_t device,
+                                    cba_undistort_map** out);
+cba_status cba_undistort_map_fetch(cba_undistort_map* h, float* map_x, float* map_y);
+cba_status cba_undistort_map_apply(cba_undistort_map* h, int32_t n_images, const int32_t* cam, int32_t src_width, int32_t src_height,
+                                   int32_t channels, int32_t dtype, double border, const void* src, void* dst);
+void cba_undistort_map_destroy(cba_undistort_map* h);
+
 #ifdef __cplusplus
 }
 #endif
