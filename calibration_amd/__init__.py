@@ -89,5 +89,17 @@ from .camera import (  # noqa: F401
     undistort,
     unproject,
 )
+from .diagnostics import (  # noqa: F401
+    ResidualStats,
+    RobustOptions,
+    RobustResult,
+    build_planar_intrinsics_report,
+    bundle_view_errors,
+    compute_global_rms,
+    extrinsic_view_errors,
+    refine_with_outlier_rejection,
+    subset_problem,
+    view_errors,
+)
 
 __version__ = "0.1.0"

@@ -211,6 +211,9 @@ PROTOTYPES = {
     "cba_reproj_set_scalar": (C.c_int32, [C.c_void_p, C.c_int32]),
     "cba_reproj_eval_fetch_f32": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cba_reproj_cost": (C.c_int32, [C.c_void_p, C.c_double, c_double_p]),
+    "cba_reproj_residual_stats": (C.c_int32, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    "cba_reproj_residuals_fetch_blocks": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, c_double_p, c_uint8_p]),
+    "cba_reproj_residual_stats_timed": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_double_p]),
     "cba_reproj_block_normal_eq": (C.c_int32, [C.c_void_p, c_double_p]),
     "cba_reproj_block_normal_eq_size": (C.c_int64, [C.c_void_p]),
     "cba_reproj_solve": (C.c_int32, [C.c_void_p, C.POINTER(CbaOptions), C.POINTER(CbaSummary)]),

@@ -754,6 +754,65 @@ cba_status cba_reproj_cost(cba_reproj* h, double huber_delta, double* cost) {
     });
 }
 
+// The largest e2 whose correctly rounded square root is <= threshold_px: "kept" is then exactly sqrt(e2) <= threshold_px (a threshold
+// set to an observation's own sqrt(e2) keeps it, which e2 <= threshold_px^2 would not always do)
+static double keep_bound(double thr) {
+    if (std::isnan(thr) || thr < 0.0) throw std::invalid_argument("threshold_px must be >= 0 or +inf");
+    if (std::isinf(thr)) return thr;
+    double t = thr * thr;
+    for (int i = 0; i < 8 && std::sqrt(t) > thr; ++i) t = std::nextafter(t, 0.0);
+    for (int i = 0; i < 8; ++i) {
+        const double n = std::nextafter(t, HUGE_VAL);
+        if (!(std::sqrt(n) <= thr)) break;
+        t = n;
+    }
+    return t;
+}
+
+static void require_device() {
+    if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+}
+
+cba_status cba_reproj_residual_stats(cba_reproj* h, double threshold_px, double* blk_stats, double* total) {
+    return guarded([&] {
+        require_device();
+        Engine& e = *as_engine(h);
+        const double t2 = keep_bound(threshold_px);
+        CBA_HIP(hipSetDevice(e.device));
+        residual_stats(e, t2, blk_stats, total);
+    });
+}
+
+cba_status cba_reproj_residuals_fetch_blocks(cba_reproj* h, int32_t b0, int32_t b1, double threshold_px, double* r, uint8_t* keep) {
+    return guarded([&] {
+        require_device();
+        Engine& e = *as_engine(h);
+        const double t2 = keep_bound(threshold_px);
+        if (b0 < 0 || b1 < b0 || b1 > e.n_blocks) throw std::invalid_argument("block range outside the problem");
+        CBA_HIP(hipSetDevice(e.device));
+        residuals_fetch_range(e, b0, b1, t2, r, keep);
+    });
+}
+
+cba_status cba_reproj_residual_stats_timed(cba_reproj* h, int32_t fetch, int32_t iters, double* ms) {
+    return guarded([&] {
+        require_device();
+        Engine& e = *as_engine(h);
+        if (iters <= 0 || !ms) throw std::invalid_argument("iters must be positive and ms given");
+        CBA_HIP(hipSetDevice(e.device));
+        for (int i = -1; i < iters; ++i) {  // (one untimed warm-up call)
+            CBA_HIP(hipEventRecord(e.ev0, e.stream));
+            if (fetch) residuals_fetch_range(e, 0, e.n_blocks, HUGE_VAL, nullptr, nullptr);
+            else residual_stats_launch(e, HUGE_VAL);
+            CBA_HIP(hipEventRecord(e.ev1, e.stream));
+            CBA_HIP(hipEventSynchronize(e.ev1));
+            float t = 0.f;
+            CBA_HIP(hipEventElapsedTime(&t, e.ev0, e.ev1));
+            if (i >= 0) ms[i] = static_cast<double>(t);
+        }
+    });
+}
+
 int64_t cba_reproj_block_normal_eq_size(const cba_reproj* h) { return h ? reinterpret_cast<const Engine*>(h)->NACC : 0; }
 
 cba_status cba_reproj_block_normal_eq(cba_reproj* h, double* out) {

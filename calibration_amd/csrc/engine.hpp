@@ -223,6 +223,10 @@ struct Engine {
     DevBuf<Tile> tilesA, tilesB;
     DevBuf<int64_t> d_blk_tile_off;
     DevBuf<double> partial, blk_acc, blk_s, scalar_out;
+    // reprojection diagnostics (residual_stats.hip): buffers of their own, never shared with the cost / LM path
+    DevBuf<double> diag_part, diag_blk, diag_tot;   // per-tile rows [n_tilesB][4], per-block rows [n_blocks][4], totals [4]
+    DevBuf<double> diag_fpart, diag_ru, diag_rv;    // the fetch form: tile rows and residuals of the requested block range
+    DevBuf<uint8_t> diag_keep;
     DevBuf<double> cost_part; // [2 * ceil(n_blocks / 2048)] partial cost pairs (only above 4096 blocks)
     DevBuf<double> blk_mom;   // [n_blocks][MomLayout::N] Mode B moment rows of the two-pose chains (kernels_reproj.hip)
     int modeb_moments = 1;    // 0 = accumulate the 12 pose columns directly (CBA_MODEB_MOMENTS=0, for A/B comparison)
@@ -266,6 +270,12 @@ void warm_reproj_kernels();                              // forces the code obje
 void launch_normal_eq(Engine& e);                       // Mode B: blk_acc[b] = [H | g | s]
 bool launch_normal_eq_shared_rows(Engine& e, double* rows);  // kernels_modeb.hip: the parts of a tile as one workgroup, rows through LDS
 void launch_cost(Engine& e, double huber_delta, double* out = nullptr);  // out (default scalar_out) = {1/2 sum rho(blk_s), sum blk_s}
+
+// residual_stats.hip: raw residual statistics (t2: the largest e2 that counts as kept).  blk_stats [n_blocks][4] / total [4] host,
+// either may be null: {sum e2, max sqrt(e2), #not kept, #obs}.  The fetch form: r [2n] interleaved and keep [n] of blocks [b0, b1)
+void residual_stats_launch(Engine& e, double t2);  // device only: diag_blk, diag_tot
+void residual_stats(Engine& e, double t2, double* blk_stats, double* total);
+void residuals_fetch_range(Engine& e, int b0, int b1, double t2, double* r, uint8_t* keep);
 
 // backend_hip.hip
 void init_lm_state(Engine& e, const cba_reproj_problem& d, bool have_records = false);

@@ -27,6 +27,18 @@ __device__ __forceinline__ double wave_sum63(double v) {
     return v;
 }
 
+// Wave-wide maximum of NON-NEGATIVE values, the steps of wave_sum63 (lanes that receive nothing get 0, the identity here); NaN
+// entries are ignored (v_max_f64).  The maximum lands in LANE 63.
+__device__ __forceinline__ double wave_max63(double v) {
+    v = fmax(v, dpp_f64<0xB1, 0xF>(v));
+    v = fmax(v, dpp_f64<0x4E, 0xF>(v));
+    v = fmax(v, dpp_f64<0x141, 0xF>(v));
+    v = fmax(v, dpp_f64<0x140, 0xF>(v));
+    v = fmax(v, dpp_f64<0x142, 0xA>(v));
+    v = fmax(v, dpp_f64<0x143, 0xC>(v));
+    return v;
+}
+
 // Transposed wave reduction: every lane enters with N partial sums w[0..N) (N a multiple of 16) and leaves with the
 // WAVE TOTALS of TransposeSum<N>::CNT of them in w[0..CNT): entry j of an OWNING lane's result is element (return value + j).
 // Each butterfly step halves the working set — a lane keeps the lower or upper half (by one bit of its lane id), hands the

@@ -392,6 +392,32 @@ class ReprojHandle:
         capi.check(self.lib, self.lib.cba_reproj_cost(self.h, float(huber_delta), C.byref(c)))
         return float(c.value)
 
+    def residual_stats(self, threshold_px: float = float("inf")):
+        """Raw reprojection statistics at the current parameters (cba_reproj_residual_stats): a ``diagnostics.ResidualStats``."""
+        from .diagnostics import ResidualStats
+
+        nb = self.flat.n_blocks
+        blk = np.zeros((max(nb, 1), 4))
+        tot = np.zeros(4)
+        capi.check(self.lib, self.lib.cba_reproj_residual_stats(self.h, float(threshold_px), dptr(blk), dptr(tot)))
+        return ResidualStats.from_flat(self.flat, blk[:nb], tot, float(threshold_px))
+
+    def residuals_fetch_blocks(self, b0: int, b1: int, threshold_px: float = float("inf")):
+        """Raw residuals r [2n] (interleaved u, v) and keep flags [n] (sqrt(e2) <= threshold_px) of the residual blocks [b0, b1)
+        (cba_reproj_residuals_fetch_blocks; no Jacobian, no prior eval)."""
+        n = int(self.flat.blk_offset[b1] - self.flat.blk_offset[b0]) if 0 <= b0 <= b1 <= self.flat.n_blocks else 0
+        r = np.zeros(max(2 * n, 1))
+        keep = np.zeros(max(n, 1), dtype=np.uint8)
+        capi.check(self.lib, self.lib.cba_reproj_residuals_fetch_blocks(self.h, int(b0), int(b1), float(threshold_px), dptr(r),
+                                                                        capi.u8ptr(keep)))
+        return r[:2 * n], keep[:n].astype(bool)
+
+    def residual_stats_timed(self, iters: int = 5, fetch: bool = False) -> np.ndarray:
+        """Device milliseconds of ``iters`` diagnostics passes over the whole handle (cba_reproj_residual_stats_timed)."""
+        ms = np.zeros(int(iters))
+        capi.check(self.lib, self.lib.cba_reproj_residual_stats_timed(self.h, int(bool(fetch)), int(iters), dptr(ms)))
+        return ms
+
     def block_normal_eq(self) -> np.ndarray:
         w = int(self.lib.cba_reproj_block_normal_eq_size(self.h))
         out = np.zeros((self.flat.n_blocks, w))

@@ -216,6 +216,24 @@ cba_status cba_reproj_eval_fetch_f32(cba_reproj* h, float* r, float* J);
 /* Cost 1/2 sum rho(|r_b|^2) at the current parameters (residual-only pass). */
 cba_status cba_reproj_cost(cba_reproj* h, double huber_delta, double* cost);
 
+/* Reprojection diagnostics at the handle's current parameters: raw residuals r = projection - observation (no loss, no
+ * weights), one residual-only pass that leaves Mode A output, LM state and the cost buffers untouched.
+ * e2 = r_u^2 + r_v^2 (fp64, no FMA).  blk_stats[b] = {sum e2, max sqrt(e2) (px), #not kept, #observations};
+ * total[4] = the same over the handle's blocks.  Either pointer may be NULL.  Multi-rank handles: this rank's blocks, no
+ * exchange.  threshold_px: >= 0 or +inf; NaN / negative -> CBA_ERR_INVALID_ARGUMENT.
+ * An observation is kept exactly when sqrt(e2) <= threshold_px (correctly rounded square root), so a threshold equal to an
+ * observation's own error keeps it; a NaN residual is never kept and counts as over the threshold; the maximum ignores NaN.
+ * Sums run in a fixed order (tiles, then blocks): two calls give the same bits. */
+cba_status cba_reproj_residual_stats(cba_reproj* h, double threshold_px, double* blk_stats, double* total);
+/* Residuals and inlier flags of residual blocks [b0, b1): r[2n] interleaved as cba_reproj_eval_fetch_blocks,
+ * keep[n] = (sqrt(e2) <= threshold_px) (0 for NaN).  Either pointer may be NULL.  Needs no prior cba_reproj_eval.
+ * Device buffers are sized to the range.  Bad block ranges -> CBA_ERR_INVALID_ARGUMENT. */
+cba_status cba_reproj_residuals_fetch_blocks(cba_reproj* h, int32_t b0, int32_t b1, double threshold_px, double* r,
+                                             uint8_t* keep);
+/* Device time (HIP events) of `iters` diagnostics passes over the whole handle after one untimed call, ms[iters]:
+ * fetch = 0 the statistics form, 1 the fetch form's kernel (residuals and flags of every block written on the device). */
+cba_status cba_reproj_residual_stats_timed(cba_reproj* h, int32_t fetch, int32_t iters, double* ms);
+
 /* Per-block normal-equation blocks at the current parameters ("Mode B", unweighted):
  * out[b] = [ upper triangle of J_b^T J_b row-major (P(P+1)/2) | J_b^T r_b (P) | |r_b|^2 (1) ]. */
 cba_status cba_reproj_block_normal_eq(cba_reproj* h, double* out);
