@@ -1356,21 +1356,31 @@ struct HipBackend final : Backend {
     // the chip goes from the controller straight into the next step (the host's read of the record and its ~15 launches of 3-5 us
     // are off the critical path).  The head assumes the accept has happened: the buffer exchange is made here and undone by
     // ctl_prelaunch_cancel() if the record says otherwise.
+    // Queuing the head also sets host-side flags for what follows it (vstats_pending: stage 3 reduces the views' step statistics;
+    // e.head_weights: Mode B left the robust weights): a cancel restores them with the buffers, so that the next system does not
+    // take along the output of launches that did nothing.
+    bool pre_vstats_pending = false, pre_head_weights = false;
     bool ctl_prelaunch() override {
         if (!st.ctl_prelaunch || e.scalar || !e.modeb_shared || (e.chain != CBA_CHAIN_INTRINSIC && !e.modeb_moments)) return false;
+        pre_vstats_pending = vstats_pending;
+        pre_head_weights = e.head_weights;
         ctl_accept(true);
         e.gate = st.ctl_view.scal + CS_GO;
         try {
             step_head_speculative();
         } catch (...) {
             e.gate = nullptr;
-            ctl_accept(true);
+            ctl_prelaunch_cancel();
             throw;
         }
         e.gate = nullptr;
         return true;
     }
-    void ctl_prelaunch_cancel() override { ctl_accept(true); }  // (the gated launches did nothing)
+    void ctl_prelaunch_cancel() override {  // (the gated launches did nothing)
+        ctl_accept(true);
+        vstats_pending = pre_vstats_pending;
+        e.head_weights = pre_head_weights;
+    }
     void ctl_step_tail(double huber, const PackLayout& L, const AllReduce& ar, int rank) override {
         (void)rank;
         step_tail_speculative(huber, L, ar);

@@ -354,6 +354,9 @@ class LMDriver {
             wait();
         }
         if (pre) be_.ctl_prelaunch_cancel();
+        // the invocation that ended the solve may have accepted a step first (the loop-top tests after an accepted speculative
+        // step: iteration cap, gradient tolerance, minimum radius): its private poses are still the trial copy
+        if (rec[CS_ACCEPT] != 0.0) be_.ctl_accept(rec[CS_ACCEPT] == 2.0);
         // the accepted point: shared blocks from the controller, private poses from the backend
         {
             std::vector<double> d(std::max(1, s_.nsh));

@@ -601,12 +601,13 @@ CBA_HD bool ctl_expect_convergence(const CtlView& V) {
 CBA_HD bool ctl_next_step_speculative(const CtlView& V) {
     return V.speculate && V.scal[CS_PLAIN_NEXT] == 0.0 && !ctl_expect_convergence(V);
 }
-// the loop-top tests of the iteration, on the current state; 0 = go on
-CBA_HD int ctl_top_tests(const CtlView& V, int* msg) {
-    if (V.scal[CS_ITER] >= V.max_iterations) { *msg = CM_MAX_ITER; return CBA_TERM_NO_CONVERGENCE; }
-    if (V.scal[CS_GMAX] <= V.eps) { *msg = CM_GRADIENT; return CBA_TERM_CONVERGENCE; }
-    if (V.scal[CS_RADIUS] <= CTL_MIN_RADIUS) { *msg = CM_MIN_RADIUS; return CBA_TERM_CONVERGENCE; }
-    return 0;
+// the loop-top tests of the iteration, on the current state; true = the solve ends with *term / *msg (CBA_TERM_CONVERGENCE is 0:
+// the termination code itself cannot double as the "go on" flag)
+CBA_HD bool ctl_top_tests(const CtlView& V, int* term, int* msg) {
+    if (V.scal[CS_ITER] >= V.max_iterations) { *term = CBA_TERM_NO_CONVERGENCE; *msg = CM_MAX_ITER; return true; }
+    if (V.scal[CS_GMAX] <= V.eps) { *term = CBA_TERM_CONVERGENCE; *msg = CM_GRADIENT; return true; }
+    if (V.scal[CS_RADIUS] <= CTL_MIN_RADIUS) { *term = CBA_TERM_CONVERGENCE; *msg = CM_MIN_RADIUS; return true; }
+    return false;
 }
 
 // Top of an iteration on the current system: the termination tests, the reduced solve, the trial point of the shared blocks and
@@ -614,9 +615,8 @@ CBA_HD int ctl_top_tests(const CtlView& V, int* msg) {
 // re-elimination after an unsolvable system, or the end of the solve.
 template <class TM>
 CBA_HD void ctl_iterate(TM& tm, const CtlView& V) {
-    int msg = CM_NONE;
-    const int t = ctl_top_tests(V, &msg);  // uniform: scalars are read after a barrier
-    if (t) { ctl_end(tm, V, t, msg); return; }
+    int term = -1, msg = CM_NONE;
+    if (ctl_top_tests(V, &term, &msg)) { ctl_end(tm, V, term, msg); return; }  // uniform: scalars are read after a barrier
     tm.sync();
     if (tm.tid() == 0) V.scal[CS_ITER] += 1.0;
     const double radius = V.scal[CS_RADIUS];
@@ -816,8 +816,8 @@ CBA_HD void ctl_run(TM& tm, const CtlView& V, int mode, int flag) {
     if (tm.tid() == 0 && static_cast<int>(V.scal[CS_EXPECT]) == CTL_RESOLVED && V.scal[CS_TERM] < 0.0) {
         // what follows the re-elimination is known now (its result does not enter the loop-top tests): the host may queue it
         // behind the re-elimination without waiting for this record's successor
-        int msg;
-        V.scal[CS_WILL_END] = ctl_top_tests(V, &msg) ? 1.0 : 0.0;
+        int term, msg;
+        V.scal[CS_WILL_END] = ctl_top_tests(V, &term, &msg) ? 1.0 : 0.0;
         V.scal[CS_STEP_SPEC] = ctl_next_step_speculative(V) ? 1.0 : 0.0;
     }
     if (tm.tid() == 0)

@@ -308,6 +308,19 @@ def scene_bundle_wide(n_poses=24, n_cams=2, model=capi.CAMERA_SCHEIMPFLUG, seed=
     return scene_bundle(n_poses, n_cams, model=model, seed=seed, noise_px=noise_px, **args)
 
 
+def scale_pixels(sc: Scene, s: float) -> Scene:
+    """The same scene in pixel units s times as large: observations u, v and every camera's fx, fy, cx, cy, skew (in place; the
+    ground truth too).  The residuals shrink by s and the cost and the gradient by s^2, while the relative cost change of a step
+    stays what it was: at s = 1e-5 a solve with epsilon 1e-9 ends by the gradient tolerance rather than the function tolerance."""
+    f = sc.flat
+    f.u *= s
+    f.v *= s
+    f.intr[:, 0:5] *= s
+    sc.gt_intr = sc.gt_intr.copy()
+    sc.gt_intr[:, 0:5] *= s
+    return sc
+
+
 def shard_views(flat: FlatProblem, rank: int, world: int) -> FlatProblem:
     """View-sharding of SURVEY.md §8(e): contiguous ranges of private views (INTRINSIC / EXTRINSIC) or of
     residual blocks (BUNDLE), balanced by observation count; shared parameters replicated."""

@@ -1399,3 +1399,154 @@ def test_default_device_of_the_handle_less_entry_points(gpu_lib):
     n = gpu_lib.cba_device_count()
     assert gpu_lib.cba_set_device(n) == capi.CBA_ERR_INVALID_ARGUMENT and gpu_lib.cba_get_device() == 0
     assert gpu_lib.cba_set_device(-1) == capi.CBA_ERR_INVALID_ARGUMENT
+
+
+# ---- LM solves that end by the iteration cap or the gradient tolerance (test_lm_endings_cpu.py, through the C ABI) -------------------
+ENDING_SCENES = {
+    "intr": lambda: synth.scene_intrinsics(10, spacing=0.08, noise_px=0.2),
+    "ext": lambda: synth.scene_extrinsics(6, 3, spacing=0.08, noise_px=0.2),
+    "bundle": lambda: synth.scene_bundle(12, 2, spacing=0.04, noise_px=0.2),
+}
+ENDING_MSG = {capi.TERM_NO_CONVERGENCE: b"Maximum number of iterations reached.", capi.TERM_CONVERGENCE: b"Gradient tolerance reached."}
+
+
+def _check_ending(oracle, sa, fa, sb, fb, term, o):
+    """oracle (sa, fa) vs engine (sb, fb): the ending the case names, the same decisions, every block (view poses included) to the
+    pinhole bar, and final_cost = the cost at the parameters returned."""
+    for s in (sa, sb):
+        assert s.termination == term and ENDING_MSG[term] in bytes(s.report), (sa.report, sb.report)
+    assert (sb.iterations, sb.successful_steps) == (sa.iterations, sa.successful_steps), (sa.report, sb.report)
+    assert helpers.param_diff(fa, fb) <= 1e-9, (helpers.param_diff(fa, fb), sb.report)
+    c = helpers.oracle_cost(oracle, fb, o.huber_delta)
+    assert abs(sb.final_cost - c) <= 1e-12 * c, (sb.final_cost, c, sb.report)
+
+
+def _check_covariance_at_the_oracle_point(oracle, fa, o, cov1):
+    """the engine's covariance right after its own solve (linearised at the point it returned) against the oracle's at the point the
+    oracle returned: test_covariance_matches_oracle's same-point bar"""
+    cov0 = helpers.oracle_covariance(oracle, fa, o)
+    assert cov0 is not None and cov1 is not None and cov0.shape == cov1.shape
+    d0 = np.abs(np.diag(cov0))
+    assert np.array_equal(d0 == 0, np.diag(cov1) == 0)
+    nz = d0 > 0
+    assert (np.abs(cov0 - cov1)[np.ix_(nz, nz)] / np.sqrt(np.outer(d0[nz], d0[nz]))).max() <= 1e-7
+
+
+@pytest.mark.parametrize("speculate", ["default", "0"])
+@pytest.mark.parametrize("kind,cap", [("intr", 1), ("intr", 2), ("intr", 3), ("ext", 1), ("ext", 2), ("ext", 3), ("bundle", 2),
+                                      ("intr", None), ("ext", None)])
+def test_lm_endings_match_oracle(gpu_lib, oracle, monkeypatch, kind, cap, speculate):
+    """A solve that ends by the iteration cap (cap 1 .. 3, mostly right after an accepted step) or by the gradient tolerance (cap None:
+    the pixel-scaled scene, synth.scale_pixels) through the C ABI, host-driven controller and resident kernel (lm_mode), speculation
+    at its default and off: everything the oracle returns, view poses and the recomputed cost included; after a capped solve the
+    covariance the handle computes next is the oracle's at its own end point (a handle that kept the poses of an earlier step would
+    linearise at a mixed point)."""
+    if speculate == "0":
+        monkeypatch.setenv("CBA_LM_SPECULATE", "0")
+    okw = dict(optimize_intrinsics=1) if kind == "bundle" else {}
+    if cap is None:
+        mk, o, term = (lambda: synth.scale_pixels(ENDING_SCENES[kind](), 1e-5)), options(epsilon=1e-9, **okw), capi.TERM_CONVERGENCE
+    else:
+        mk, o, term = ENDING_SCENES[kind], options(epsilon=1e-12, max_iterations=cap, **okw), capi.TERM_NO_CONVERGENCE
+    a, b = mk(), mk()
+    sa = helpers.oracle_solve(oracle, a.flat, o)
+    with optim.ReprojHandle(b.flat) as h:
+        sb = h.solve(o)
+        cov1 = h.covariance(o) if cap is not None else None
+    _check_ending(oracle, sa, a.flat, sb, b.flat, term, o)
+    if cap is not None:
+        _check_covariance_at_the_oracle_point(oracle, a.flat, o, cov1)
+
+
+@pytest.mark.parametrize("kind", ["intr", "ext"])
+def test_capped_solve_through_the_prelaunched_controller(gpu_lib, oracle, kind):
+    """The host-driven controller (lm mode 0, whatever CBA_LM_RESIDENT says) on a problem past the resident kernel's crossover, where
+    the head of the next speculative step is queued behind every controller invocation (ctl_prelaunch): a solve that the cap ends
+    right after an accepted speculative step cancels that head (ctl_prelaunch_cancel) and must still return the accepted step's poses,
+    cost and covariance."""
+    mk = {"intr": lambda: synth.scene_intrinsics(10, rows=30, cols=40, spacing=0.025, noise_px=0.2),
+          "ext": lambda: synth.scene_extrinsics(6, 3, rows=20, cols=30, spacing=0.03, noise_px=0.2)}[kind]
+    for cap in (1, 2, 3):
+        o = options(epsilon=1e-12, max_iterations=cap)
+        a, b = mk(), mk()
+        sa = helpers.oracle_solve(oracle, a.flat, o)
+        with optim.ReprojHandle(b.flat) as h:
+            h.set_lm_mode(0)
+            sb = h.solve(o)
+            xs = h.solve_stats()
+            cov1 = h.covariance(o)
+        assert b"resident" not in bytes(sb.report)
+        assert xs["speculation_hits"] >= (1 if cap >= 2 else 0) and xs["speculative_steps"] == cap, xs
+        _check_ending(oracle, sa, a.flat, sb, b.flat, capi.TERM_NO_CONVERGENCE, o)
+        _check_covariance_at_the_oracle_point(oracle, a.flat, o, cov1)
+
+
+@pytest.mark.parametrize("cap", [1, 2])
+def test_per_view_solvers_at_the_iteration_cap(gpu_lib, oracle, cap):
+    """The in-kernel LMs of the batched planar-pose and homography refinements (small_lm.hpp), the semi-DLT intrinsics solver and the
+    hand-eye AX = XB refinement each keep their own iteration count: capped at 1 and 2 iterations they stop where the oracle stops."""
+    from calibration_amd.geometry import pose_from_matrix
+
+    o = options(epsilon=1e-12, max_iterations=cap)
+    core = optim.OptimOptions(epsilon=1e-12, max_iterations=cap)
+    # planar pose, one launch for the batch
+    rng = np.random.default_rng(4)
+    cam = synth.camera_gt(0)
+    K = np.ascontiguousarray(cam[:5])
+    views, inits = [], []
+    for i in range(9):
+        T = synth.random_view_poses(1, rng, dist=1.5)[0]
+        views.append(synth.render_view(cam, T, synth.make_target_grid(5 + i % 4, 6 + i % 3, 0.05), noise_px=0.2, rng=rng))
+        inits.append(synth.perturb_pose(T, rng, 3.0, 0.05))
+    for nr in (0, 2):
+        out = optim.optimize_planar_pose_batch(views, K, inits, optim.PlanarPoseOptions(core=core, num_radial=nr))
+        for i, (vw, T0) in enumerate(zip(views, inits)):
+            X, Y, u, v = (np.ascontiguousarray(vw[:, k]) for k in range(4))
+            p, s, d, rms, cov = helpers.pose6_of(T0), capi.CbaSummary(), np.zeros(nr + 2), C.c_double(), np.zeros((6, 6))
+            assert oracle.orc_planar_pose_solve(len(vw), capi.dptr(X), capi.dptr(Y), capi.dptr(u), capi.dptr(v), capi.dptr(K), nr, capi.dptr(p),
+                                                C.byref(o), C.byref(s), capi.dptr(d), C.byref(rms), capi.dptr(cov)) == 0
+            r = out[i]
+            assert r.core.iterations == s.iterations and r.core.success == bool(s.success), (i, nr, s.report, r.core)
+            assert np.abs(helpers.pose6_of(r.pose) - p).max() <= 1e-9, (i, nr)
+            assert abs(r.reprojection_error - rms.value) <= 1e-9 * max(1.0, rms.value)
+    # homography, one launch for the batch
+    hviews, hinits = [], []
+    for i in range(6):
+        view, _ = helpers.homography_scene(40 + 17 * i, 0.3, seed=200 + i)
+        H0 = helpers.dlt_homography(view) * (1 + 5e-3)
+        H0[2, 2] = 1.0
+        hviews.append(view)
+        hinits.append(H0)
+    res = optim.optimize_homography_batch(hviews, hinits, core)
+    for view, H0, r in zip(hviews, hinits, res):
+        X, Y, u, v = (np.ascontiguousarray(view[:, k]) for k in range(4))
+        hh, s, cov = H0.reshape(9).copy(), capi.CbaSummary(), np.zeros((8, 8))
+        assert oracle.orc_homography_solve(len(view), capi.dptr(X), capi.dptr(Y), capi.dptr(u), capi.dptr(v), capi.dptr(hh), C.byref(o),
+                                           C.byref(s), capi.dptr(cov)) == 0
+        assert r.core.iterations == s.iterations and r.core.success == bool(s.success), (s.report, r.core)
+        assert np.abs(hh.reshape(3, 3) - r.homography).max() <= 1e-9 * max(1.0, np.abs(hh).max())
+        assert abs(s.final_cost - r.core.final_cost) <= 1e-9 * max(1.0, s.final_cost)
+    # semi-DLT
+    d, _kgt, _agt = helpers.semidlt_scene(5, noise=0.2, nr=2)
+    gpu_lib.cba_optimize_intrinsics_semidlt.argtypes = helpers.SEMIDLT_SOLVE_ARGS
+    sta, ka, pa, sa, da, va, _ = helpers.semidlt_solve(oracle.orc_semidlt_solve, d, 2, o, want_cov=False)
+    stb, kb, pb, sb, db, vb, _ = helpers.semidlt_solve(gpu_lib.cba_optimize_intrinsics_semidlt, d, 2, o, want_cov=False)
+    assert sta == 0 and stb == 0
+    assert sa.termination == sb.termination == capi.TERM_NO_CONVERGENCE and sa.iterations == sb.iterations == cap, (sa.report, sb.report)
+    assert sa.successful_steps == sb.successful_steps
+    assert np.abs(ka - kb).max() <= 1e-9 * np.abs(ka).max() and np.abs(pa - pb).max() <= 1e-9
+    assert np.abs(da - db).max() <= 1e-9 * max(1.0, np.abs(da).max()) and np.abs(va - vb).max() <= 1e-9
+    assert abs(sa.final_cost - sb.final_cost) <= 1e-9 * max(1.0, sa.final_cost)
+    # hand-eye (k_axxb)
+    bTg, cTt, _X, X0 = helpers.handeye_scene(30, seed=11, noise_rot_deg=0.3, noise_trans=0.002)
+    pairs = np.ascontiguousarray(helpers.build_all_pairs(bTg, cTt, 0.5))
+    xa, sa, ca = pose_from_matrix(X0), capi.CbaSummary(), np.zeros((7, 7))
+    assert oracle.orc_axxb_solve(len(pairs), capi.dptr(pairs), capi.dptr(xa), C.byref(o), C.byref(sa), capi.dptr(ca)) == 0
+    pb6 = np.stack([pose_from_matrix(T) for T in bTg])
+    pc6 = np.stack([pose_from_matrix(T) for T in cTt])
+    xb, sb, cb = pose_from_matrix(X0), capi.CbaSummary(), np.zeros((7, 7))
+    capi.check(gpu_lib, gpu_lib.cba_optimize_handeye(len(bTg), capi.dptr(pb6), capi.dptr(pc6), capi.dptr(xb), C.byref(o), C.byref(sb), capi.dptr(cb)))
+    assert sa.termination == sb.termination == capi.TERM_NO_CONVERGENCE and sa.iterations == sb.iterations == cap, (sa.report, sb.report)
+    assert sa.successful_steps == sb.successful_steps
+    assert np.abs(xa - xb).max() <= 1e-9
+    assert abs(sa.final_cost - sb.final_cost) <= 1e-9 * max(1.0, sa.final_cost) + 1e-18
