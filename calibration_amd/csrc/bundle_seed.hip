@@ -167,28 +167,6 @@ __global__ __launch_bounds__(64) void k_bs_scan(int n, const double* __restrict_
 }
 
 // ---- host glue -----------------------------------------------------------------------------------------------------------
-namespace {
-struct BsTimer {  // device events between the stages (experiment builds' stage timing)
-    hipEvent_t ev[6] = {};
-    explicit BsTimer(bool on) {
-        if (on)
-            for (hipEvent_t& e : ev) CBA_HIP(hipEventCreate(&e));
-    }
-    ~BsTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t s) {
-        if (ev[k]) CBA_HIP(hipEventRecord(ev[k], s));
-    }
-    double ms(int a, int b) const {
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
-        return t;
-    }
-};
-}  // namespace
-
 void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
                      const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, const int32_t* cam_start,
                      const int32_t* cam_blk, double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, const double* b_T_t_given,
@@ -215,37 +193,31 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        BsTimer tm(stage_ms != nullptr);
-        const int64_t n_obs = blk_offset[n_blocks];
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_obs, 1));
+        StageTimer<6> tm(stream, stage_ms != nullptr);  // device events between the stages
         const size_t nb = static_cast<size_t>(n_blocks), nc = static_cast<size_t>(n_cams), nl = static_cast<size_t>(std::max(n_list, 1));
-        DevBuf<double> dX, dY, du, dv, dK, dB, dP, dT, dXs, dG, dPart, dPart2, dSum, dCq, dCt, dOut;
-        DevBuf<int64_t> doff, drow, dchunk;
+        ObsSoA d;
+        DevBuf<double> dK, dB, dP, dT, dXs, dG, dPart, dPart2, dSum, dCq, dCt, dOut;
+        DevBuf<int64_t> drow, dchunk;
         DevBuf<int32_t> dcam, dok, dlist, dstat, dpairs;
         DevBuf<BsCam> dcams;
-        dX.alloc(n); dY.alloc(n); du.alloc(n); dv.alloc(n);
-        dK.alloc(5 * nc); dB.alloc(12 * nb); dP.alloc(7 * nb); dok.alloc(nb); doff.alloc(nb + 1); dcam.alloc(nb);
-        dT.alloc(24 * nl); dlist.alloc(nl); dXs.alloc(12 * nc); dG.alloc(7 * nc); dstat.alloc(nc); dpairs.alloc(nc);
-        dCq.alloc(4 * nl); dCt.alloc(3 * nl); dOut.alloc(7);
+        d.upload(stream, n_blocks, blk_offset, X, Y, u, v);
+        dP.alloc(7 * nb); dok.alloc(nb); dT.alloc(24 * nl); dCq.alloc(4 * nl); dCt.alloc(3 * nl); dOut.alloc(7);
         dPart.alloc(static_cast<size_t>(std::max<int64_t>(n_rows, 1)) * AXXB_NACC);
         dPart2.alloc(static_cast<size_t>(std::max<int64_t>(n_chunks, 1)) * AXXB_NACC);
         dSum.alloc(static_cast<size_t>(std::max(n_dlt, 1)) * AXXB_NACC);
-        dcams.alloc(std::max<size_t>(cams.size(), 1)); drow.alloc(row_bound.size()); dchunk.alloc(chunk_bound.size());
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        dK.upload(kmtx5, 5 * nc, stream);
-        dB.upload(blk_b_T_g, 12 * nb, stream);
-        doff.upload(blk_offset, nb + 1, stream);
-        dcam.upload(blk_cam, nb, stream);
-        dlist.upload(cam_blk, static_cast<size_t>(n_list), stream);
+        dK.assign(kmtx5, 5 * nc, stream);
+        dB.assign(blk_b_T_g, 12 * nb, stream);
+        dcam.assign(blk_cam, nb, stream);
+        dlist.assign(cam_blk, static_cast<size_t>(n_list), stream);
         std::vector<double> xs(12 * nc, 0.0);  // R_X = I until the rotation solve
         for (size_t c = 0; c < nc; ++c) xs[12 * c] = xs[12 * c + 4] = xs[12 * c + 8] = 1.0;
-        dXs.upload(xs.data(), xs.size(), stream);
-        dG.upload(g_T_c, 7 * nc, stream);  // given / identity rows; the DLT cameras' rows are overwritten
-        dstat.upload(cam_status, nc, stream);
-        dpairs.upload(cam_pairs, nc, stream);
-        dcams.upload(cams.data(), cams.size(), stream);
-        drow.upload(row_bound.data(), row_bound.size(), stream);
-        dchunk.upload(chunk_bound.data(), chunk_bound.size(), stream);
+        dXs.assign(xs.data(), xs.size(), stream);
+        dG.assign(g_T_c, 7 * nc, stream);  // given / identity rows; the DLT cameras' rows are overwritten
+        dstat.assign(cam_status, nc, stream);
+        dpairs.assign(cam_pairs, nc, stream);
+        dcams.assign(cams.data(), cams.size(), stream);
+        drow.assign(row_bound.data(), row_bound.size(), stream);
+        dchunk.assign(chunk_bound.data(), chunk_bound.size(), stream);
         const double min_angle = min_angle_deg * 3.14159265358979323846 / 180.0;  // as handeye_dlt converts it
         const unsigned list_grid = static_cast<unsigned>((n_list + 255) / 256), dlt_grid = static_cast<unsigned>((n_dlt + 63) / 64);
         auto sums = [&]() {
@@ -253,9 +225,9 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
             hipLaunchKernelGGL(k_bs_chunk_total, dim3(static_cast<unsigned>(n_dlt)), dim3(256), 0, stream, dchunk.p, dPart2.p, dSum.p);
         };
 
-        tm.mark(0, stream);
-        launch_block_pose(n_blocks, doff.p, dcam.p, dX.p, dY.p, du.p, dv.p, dK.p, dP.p, dok.p, stream);
-        tm.mark(1, stream);
+        tm.mark(0);
+        launch_block_pose(n_blocks, d.off.p, dcam.p, d.X.p, d.Y.p, d.u.p, d.v.p, dK.p, dP.p, dok.p, stream);
+        tm.mark(1);
         if (n_list > 0) hipLaunchKernelGGL(k_bs_pose_table, dim3(list_grid), dim3(256), 0, stream, n_list, dlist.p, dB.p, dP.p, dT.p);
         if (n_dlt > 0) {
             hipLaunchKernelGGL(k_bs_pairs<1>, dim3(static_cast<unsigned>(n_rows)), dim3(256), 0, stream, n_dlt, dcams.p, drow.p, dT.p, dXs.p,
@@ -264,7 +236,7 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
             hipLaunchKernelGGL(k_bs_rot_solve, dim3(dlt_grid), dim3(64), 0, stream, n_dlt, dcams.p, dSum.p, dXs.p, dstat.p, dpairs.p);
         }
         CBA_HIP(hipGetLastError());
-        tm.mark(2, stream);
+        tm.mark(2);
         if (n_dlt > 0) {
             hipLaunchKernelGGL(k_bs_pairs<2>, dim3(static_cast<unsigned>(n_rows)), dim3(256), 0, stream, n_dlt, dcams.p, drow.p, dT.p, dXs.p,
                                min_angle, dPart.p);
@@ -272,14 +244,14 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
             hipLaunchKernelGGL(k_bs_trans_solve, dim3(dlt_grid), dim3(64), 0, stream, n_dlt, dcams.p, dSum.p, dXs.p, dstat.p, dG.p);
         }
         CBA_HIP(hipGetLastError());
-        tm.mark(3, stream);
+        tm.mark(3);
         const bool scan = !b_T_t_given && n_list > 0;
         if (scan)
             hipLaunchKernelGGL(k_bs_candidates, dim3(list_grid), dim3(256), 0, stream, n_list, dlist.p, dcam.p, dB.p, dP.p, dG.p, dCq.p, dCt.p);
-        tm.mark(4, stream);
+        tm.mark(4);
         if (scan) hipLaunchKernelGGL(k_bs_scan, dim3(1), dim3(64), 0, stream, n_list, dCq.p, dCt.p, dOut.p);
         CBA_HIP(hipGetLastError());
-        tm.mark(5, stream);
+        tm.mark(5);
         dG.download(g_T_c, 7 * nc, stream);
         dstat.download(cam_status, nc, stream);
         dpairs.download(cam_pairs, nc, stream);

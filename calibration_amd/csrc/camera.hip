@@ -36,32 +36,15 @@ int cam_grid(int64_t lanes) {
 int64_t whole_waves(int64_t lanes) { return (lanes + 63) / 64 * 64; }
 
 // device events of the experiment builds' timing: 0 start, 1 uploaded, 2 kernel done, 3 downloaded
-struct CamTimer {
-    hipEvent_t ev[4] = {};
-    explicit CamTimer(bool on) {
-        if (on)
-            for (hipEvent_t& e : ev) CBA_HIP(hipEventCreate(&e));
-    }
-    ~CamTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t s) {
-        if (ev[k]) CBA_HIP(hipEventRecord(ev[k], s));
-    }
-    double ms(int a, int b) const {
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
-        return t;
-    }
-    // stage_ms [3]: upload, kernel, download
-    void report(double* stage_ms) const {
-        if (!stage_ms || !ev[0]) return;
-        stage_ms[0] = ms(0, 1);
-        stage_ms[1] = ms(1, 2);
-        stage_ms[2] = ms(2, 3);
-    }
-};
+using CamTimer = StageTimer<4>;
+
+// stage_ms [3]: upload, kernel, download
+void cam_report(const CamTimer& tm, double* stage_ms) {
+    if (!stage_ms) return;
+    stage_ms[0] = tm.ms(0, 1);
+    stage_ms[1] = tm.ms(1, 2);
+    stage_ms[2] = tm.ms(2, 3);
+}
 
 }  // namespace
 
@@ -221,24 +204,24 @@ void camera_project_gpu(int model, const double* intr, int64_t n, const double* 
     CBA_HIP(hipSetDevice(device));
     StreamLease lease;
     const hipStream_t s = lease;
-    CamTimer tm(stage_ms != nullptr);
+    CamTimer tm(s, stage_ms != nullptr);
     DevBuf<double> dxyz, duv;
     dxyz.alloc(3 * static_cast<size_t>(n));
     duv.alloc(2 * static_cast<size_t>(n));
-    tm.mark(0, s);
+    tm.mark(0);
     dxyz.upload(xyz, 3 * static_cast<size_t>(n), s);
-    tm.mark(1, s);
+    tm.mark(1);
     const int g = cam_grid((n + 1) / 2);
     if (model == CAM_SCHEIMPFLUG)
         hipLaunchKernelGGL(k_cam_project<CAM_SCHEIMPFLUG>, dim3(g), dim3(CAM_BLOCK), 0, s, n, dxyz.p, duv.p, c);
     else
         hipLaunchKernelGGL(k_cam_project<CAM_PINHOLE_BC>, dim3(g), dim3(CAM_BLOCK), 0, s, n, dxyz.p, duv.p, c);
     CBA_HIP(hipGetLastError());
-    tm.mark(2, s);
+    tm.mark(2);
     duv.download(uv, 2 * static_cast<size_t>(n), s);
-    tm.mark(3, s);
+    tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    tm.report(stage_ms);
+    cam_report(tm, stage_ms);
 }
 
 void camera_unproject_gpu(int model, const double* intr, int n_inv, const double* inv, int64_t n, const double* uv, double* xy,
@@ -251,20 +234,20 @@ void camera_unproject_gpu(int model, const double* intr, int n_inv, const double
     CBA_HIP(hipSetDevice(device));
     StreamLease lease;
     const hipStream_t s = lease;
-    CamTimer tm(stage_ms != nullptr);
+    CamTimer tm(s, stage_ms != nullptr);
     DevBuf<double> duv, dxy;
     duv.alloc(2 * static_cast<size_t>(n));
     dxy.alloc(2 * static_cast<size_t>(n));
-    tm.mark(0, s);
+    tm.mark(0);
     duv.upload(uv, 2 * static_cast<size_t>(n), s);
-    tm.mark(1, s);
+    tm.mark(1);
     hipLaunchKernelGGL(k_cam_unproject, dim3(cam_grid(n)), dim3(CAM_BLOCK), 0, s, n, duv.p, dxy.p, c);
     CBA_HIP(hipGetLastError());
-    tm.mark(2, s);
+    tm.mark(2);
     dxy.download(xy, 2 * static_cast<size_t>(n), s);
-    tm.mark(3, s);
+    tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    tm.report(stage_ms);
+    cam_report(tm, stage_ms);
 }
 
 // The map handle: the maps stay on the device from create to destroy.  Every call ends with its stream synchronised, so nothing is
@@ -293,15 +276,15 @@ UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, co
         for (int j = 0; j < 5; ++j) k.kp[j] = new_k5 ? new_k5[5 * static_cast<size_t>(c) + j] : k.intr[j];
     }
     const hipStream_t s = m->lease;
-    CamTimer tm(stage_ms != nullptr);
+    CamTimer tm(s, stage_ms != nullptr);
     DevBuf<CamMapCam> dcams;
     dcams.alloc(n_cams);
     const size_t npx = static_cast<size_t>(W) * H * n_cams;
     m->map_x.alloc(npx);
     m->map_y.alloc(npx);
-    tm.mark(0, s);
+    tm.mark(0);
     dcams.upload(hc.data(), n_cams, s);
-    tm.mark(1, s);
+    tm.mark(1);
     const int cw = (W + CAM_MAP_PX - 1) / CAM_MAP_PX;
     const int64_t lpc = whole_waves(static_cast<int64_t>(H) * cw);
     const int g = cam_grid(lpc * n_cams);
@@ -315,10 +298,10 @@ UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, co
     }
 #undef CAM_MAP_LAUNCH
     CBA_HIP(hipGetLastError());
-    tm.mark(2, s);
-    tm.mark(3, s);
+    tm.mark(2);
+    tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));  // dcams goes out of scope
-    tm.report(stage_ms);
+    cam_report(tm, stage_ms);
     return m.release();
 }
 
@@ -369,11 +352,11 @@ void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int 
     if (m->src.n < src_bytes + CAM_SRC_PAD) m->src.alloc(src_bytes + CAM_SRC_PAD);
     if (m->dst.n < dst_bytes) m->dst.alloc(dst_bytes);
     if (m->img_cam.n < static_cast<size_t>(n_images)) m->img_cam.alloc(n_images);
-    CamTimer tm(stage_ms != nullptr);
-    tm.mark(0, s);
+    CamTimer tm(s, stage_ms != nullptr);
+    tm.mark(0);
     m->img_cam.upload(cam, n_images, s);
     m->src.upload(static_cast<const uint8_t*>(src), src_bytes, s);
-    tm.mark(1, s);
+    tm.mark(1);
     if (dtype == CBA_DTYPE_F32) {
         apply_dispatch<float>(m, n_images, sw, sh, ch, static_cast<float>(border), 0, s);
     } else {
@@ -382,11 +365,11 @@ void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int 
         apply_dispatch<uint8_t>(m, n_images, sw, sh, ch, b8, u8_load_shape(), s);
     }
     CBA_HIP(hipGetLastError());
-    tm.mark(2, s);
+    tm.mark(2);
     m->dst.download(static_cast<uint8_t*>(dst), dst_bytes, s);
-    tm.mark(3, s);
+    tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    tm.report(stage_ms);
+    cam_report(tm, stage_ms);
 }
 
 int undistort_map_cams(const UndistortMap* m) { return m->n_cams; }

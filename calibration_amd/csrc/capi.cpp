@@ -54,10 +54,35 @@ static cba_status guarded(F&& f) {
 static std::atomic<int> g_default_device{0};
 static int default_device() { return g_default_device.load(); }
 
+// The offset table [n + 1] of a call's groups of observations.  The entry points differ in two policies, kept as they shipped:
+// whether the table must start at 0, and whether a group is limited to INT32_MAX observations (the kernels that count a group in
+// an int need it).  what: "view " / "block " / "" for the message.
+enum : unsigned { OFF_ANY_START = 0, OFF_FROM_ZERO = 1, OFF_INT32_GROUPS = 2 };
+static bool bad_offset_step(const int64_t* off, int i, unsigned policy) {
+    return off[i + 1] < off[i] || ((policy & OFF_INT32_GROUPS) && off[i + 1] - off[i] > 0x7fffffff);
+}
+static void check_offsets(const int64_t* off, int n, const char* what, unsigned policy) {
+    if ((policy & OFF_FROM_ZERO) && off[0] != 0) throw std::invalid_argument(std::string(what) + "offsets must start at 0");
+    for (int i = 0; i < n; ++i)
+        if (bad_offset_step(off, i, policy))
+            throw std::invalid_argument(*what ? std::string("bad ") + what + "offsets" : "offsets must not decrease");
+}
+
 static int device_count() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+
+// every entry point that needs a device, after its argument checks: the number of visible devices, or CBA_ERR_NO_DEVICE
+static int require_device() {
+    const int n = device_count();
+    if (n <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+    return n;
+}
+// ... and those that take a device index
+static void require_device(int device) {
+    if (device < 0 || device >= require_device()) throw std::invalid_argument("device index out of range");
 }
 
 Engine::~Engine() {
@@ -209,9 +234,7 @@ static void build_engine(const cba_reproj_problem& d, int device, Engine& e, con
         e.ld = ld;
     }
 
-    const int ndev = device_count();
-    if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-    if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+    require_device(device);
     e.device = device;
     CBA_HIP(hipSetDevice(device));
     e.stream = cache_stream();
@@ -415,9 +438,7 @@ int32_t cba_device_count(void) { return device_count(); }
 void cba_trim_cache(void) { try { cache_trim(); } catch (...) {} }
 cba_status cba_set_device(int32_t device) {
     return guarded([&] {
-        const int n = device_count();
-        if (n <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-        if (device < 0 || device >= n) throw std::invalid_argument("device index out of range");
+        require_device(device);
         g_default_device.store(device);
     });
 }
@@ -769,10 +790,6 @@ static double keep_bound(double thr) {
     return t;
 }
 
-static void require_device() {
-    if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-}
-
 cba_status cba_reproj_residual_stats(cba_reproj* h, double threshold_px, double* blk_stats, double* total) {
     return guarded([&] {
         require_device();
@@ -985,7 +1002,7 @@ cba_status cba_optimize_handeye(int32_t n_poses, const double* base_T_gripper, c
                                 const cba_options* opts, cba_summary* summary, double* cov) {
     return guarded([&] {
         if (!opts || !summary || !g_T_c) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         handeye_solve(n_poses, base_T_gripper, cam_T_target, g_T_c, opts, summary, cov, default_device());
     });
 }
@@ -995,7 +1012,7 @@ cba_status cba_estimate_handeye_dlt(int32_t n_poses, const double* base_T_grippe
     return guarded([&] {
         if (!g_T_c) throw std::invalid_argument("null argument");
         if (n_poses < 2 || !base_T_gripper || !cam_T_target) throw std::runtime_error("Inconsistent hand-eye input sizes");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         handeye_dlt(n_poses, base_T_gripper, cam_T_target, min_angle_deg, g_T_c, default_device());
     });
 }
@@ -1014,9 +1031,7 @@ cba_status cba_estimate_and_optimize_handeye_sharded(int32_t n_poses, const doub
                                                      int32_t rank, int32_t device) {
     return guarded([&] {
         if (!opts || !summary || !g_T_c) throw std::invalid_argument("null argument");
-        const int ndev = device_count();
-        if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-        if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+        require_device(device);
         if (estimate) handeye_dlt(n_poses, base_T_gripper, cam_T_target, min_angle_deg, g_T_c, device, fn, user, n_ranks, rank);
         handeye_solve(n_poses, base_T_gripper, cam_T_target, g_T_c, opts, summary, cov, device, fn, user, n_ranks, rank);
     });
@@ -1028,9 +1043,7 @@ cba_status cba_estimate_and_optimize_handeye_rccl(int32_t n_poses, const double*
                                                   int32_t n_ranks, int32_t rank, int32_t device) {
     return guarded([&] {
         if (!opts || !summary || !g_T_c || !id) throw std::invalid_argument("null argument");
-        const int ndev = device_count();
-        if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-        if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+        require_device(device);
         CBA_HIP(hipSetDevice(device));
         void* comm = rccl_comm_create(id, n_ranks, rank);
         try {
@@ -1049,7 +1062,7 @@ cba_status cba_optimize_planar_pose_batch(int32_t n_views, const int64_t* view_o
                                           double* pose7, const cba_options* opts, cba_summary* summaries, double* distortion,
                                           double* reprojection_error, double* cov36) {
     return guarded([&] {
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         planar_pose_batch(n_views, view_offset, X, Y, u, v, kmtx5, num_radial, pose7, opts, summaries, distortion, reprojection_error,
                           cov36, default_device());
     });
@@ -1071,7 +1084,7 @@ cba_status cba_optimize_homography_batch(int32_t n_views, const int64_t* view_of
         if (n_views <= 0) throw std::invalid_argument("At least 4 correspondences are required.");
         for (int i = 0; i < n_views; ++i)  // homography.cpp:146-148, checked before any device work like the reference
             if (view_offset[i + 1] - view_offset[i] < 4) throw std::invalid_argument("At least 4 correspondences are required.");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         homography_batch(n_views, view_offset, X, Y, u, v, h9, opts, summaries, cov64, default_device());
     });
 }
@@ -1099,10 +1112,8 @@ cba_status cba_optimize_intrinsics_semidlt(int32_t n_views, const int64_t* view_
         if (num_radial < 0 || num_radial > 3) throw std::invalid_argument("num_radial must be in [0, 3]");
         if ((bounds_lo5 == nullptr) != (bounds_hi5 == nullptr)) throw std::invalid_argument("bounds need both ends");
         if (n_fixed < 0 || (n_fixed > 0 && !fixed_idx)) throw std::invalid_argument("bad fixed distortion list");
-        for (int i = 0; i < n_views; ++i)
-            if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff)
-                throw std::invalid_argument("bad view offsets");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        check_offsets(view_offset, n_views, "view ", OFF_ANY_START | OFF_INT32_GROUPS);  // any start, int32 groups
+        require_device();
         semidlt_solve(n_views, view_offset, X, Y, u, v, kmtx5, c_T_t, num_radial, bounds_lo5, bounds_hi5, fixed_idx, fixed_val, n_fixed,
                       opts, summary, distortion, view_errors, (cov && opts->compute_covariance) ? cov : nullptr, default_device());
     });
@@ -1127,11 +1138,8 @@ bool semidlt_sharded_args(int32_t n_local, const int64_t* view_offset, const dou
     if (num_radial < 0 || num_radial > 3) throw std::invalid_argument("num_radial must be in [0, 3]");
     if ((lo == nullptr) != (hi == nullptr)) throw std::invalid_argument("bounds need both ends");
     if (n_fixed < 0 || (n_fixed > 0 && !fixed_idx)) throw std::invalid_argument("bad fixed distortion list");
-    for (int i = 0; i < n_local; ++i)
-        if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff) throw std::invalid_argument("bad view offsets");
-    const int ndev = device_count();
-    if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-    if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+    check_offsets(view_offset, n_local, "view ", OFF_ANY_START | OFF_INT32_GROUPS);  // any start, int32 groups
+    require_device(device);
     return true;
 }
 }  // namespace
@@ -1184,10 +1192,8 @@ cba_status cba_estimate_homography_batch(int32_t n_views, const int64_t* view_of
                                          const double* u, const double* v, double* h9, int32_t* success) {
     return guarded([&] {
         if (n_views <= 0 || !view_offset || !X || !Y || !u || !v || !h9 || !success) throw std::invalid_argument("null argument");
-        for (int i = 0; i < n_views; ++i)
-            if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff)
-                throw std::invalid_argument("bad view offsets");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        check_offsets(view_offset, n_views, "view ", OFF_ANY_START | OFF_INT32_GROUPS);  // any start, int32 groups
+        require_device();
         dlt_homography_batch(n_views, view_offset, X, Y, u, v, h9, success, default_device());
     });
 }
@@ -1196,10 +1202,8 @@ cba_status cba_estimate_planar_pose_batch(int32_t n_views, const int64_t* view_o
                                           const double* u, const double* v, const double* kmtx5, double* pose7) {
     return guarded([&] {
         if (n_views <= 0 || !view_offset || !X || !Y || !u || !v || !kmtx5 || !pose7) throw std::invalid_argument("null argument");
-        for (int i = 0; i < n_views; ++i)
-            if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff)
-                throw std::invalid_argument("bad view offsets");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        check_offsets(view_offset, n_views, "view ", OFF_ANY_START | OFF_INT32_GROUPS);  // any start, int32 groups
+        require_device();
         planar_seed_batch(n_views, view_offset, X, Y, u, v, kmtx5, pose7, default_device());
     });
 }
@@ -1237,14 +1241,15 @@ static cba_status laser_plane_impl(int32_t camera_model, const double* intr, int
         // validate_observations (linescan.h:39-47)
         if (n_views < 2) throw std::invalid_argument("At least 2 views are required");
         if (target_offset[0] != 0 || laser_offset[0] != 0) throw std::invalid_argument("offsets must start at 0");
+        // both tables start at 0; int32 groups of target points, laser pixels unlimited.  A loop of its own: the two tables and the
+        // reference's count check are tested view by view, and the first failing view names the error
         for (int i = 0; i < n_views; ++i) {
-            if (target_offset[i + 1] < target_offset[i] || target_offset[i + 1] - target_offset[i] > 0x7fffffff ||
-                laser_offset[i + 1] < laser_offset[i])
+            if (bad_offset_step(target_offset, i, OFF_INT32_GROUPS) || bad_offset_step(laser_offset, i, 0))
                 throw std::invalid_argument("bad view offsets");
             if (target_offset[i + 1] - target_offset[i] < 4) throw std::invalid_argument("Each view requires >=4 target correspondences");
         }
         if (laser_offset[n_views] > 0 && (!laser_u || !laser_v)) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         laser_plane_calibrate(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
                               laser_v, *opts, result, points_xyz, inlier_mask, stage_ms, default_device());
     });
@@ -1279,7 +1284,7 @@ cba_status cba_fit_plane(int64_t n, const double* xyz, const cba_plane_fit_optio
         if (!xyz || !plane || !inlier_rms || !inlier_count) throw std::invalid_argument("null argument");
         check_plane_fit_options(opts);
         if (n < 3) throw std::invalid_argument("Not enough points to fit a plane");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         plane_fit(n, xyz, *opts, plane, inlier_rms, inlier_count, inlier_mask, default_device());
     });
 }
@@ -1364,10 +1369,7 @@ void cba_ransac_options_default(cba_ransac_options* o) {
 static void check_views(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v) {
     if (n_views < 0 || !view_offset) throw std::invalid_argument("null argument");
     if (n_views > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
-    if (view_offset[0] != 0) throw std::invalid_argument("view offsets must start at 0");
-    for (int i = 0; i < n_views; ++i)
-        if (view_offset[i + 1] < view_offset[i] || view_offset[i + 1] - view_offset[i] > 0x7fffffff)
-            throw std::invalid_argument("bad view offsets");
+    check_offsets(view_offset, n_views, "view ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
 }
 
 static void check_ransac_options(const cba_ransac_options* o) {
@@ -1385,7 +1387,7 @@ cba_status cba_estimate_homography_ransac_batch(int32_t n_views, const int64_t* 
         if (!h9 || !success || !inlier_count || !symmetric_rms) throw std::invalid_argument("null argument");
         if (opts) check_ransac_options(opts);
         if (n_views == 0) return;
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         homography_ransac_batch(n_views, view_offset, X, Y, u, v, opts, h9, success, inlier_count, symmetric_rms, inlier_mask,
                                 default_device());
     });
@@ -1409,7 +1411,7 @@ static cba_status estimate_intrinsics_impl(int32_t n_views, const int64_t* view_
         *sanitized = 0;
         for (int k = 0; k < 5; ++k) kmtx5[k] = 0.0;
         if (n_views == 0) return;  // intrinsicsdlt.cpp:104-106
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         estimate_intrinsics_gpu(n_views, view_offset, X, Y, u, v, use_ransac ? ransac : nullptr, bounds_lo5, bounds_hi5, success, kmtx5,
                                 sanitized, view_ok, h9, forward_rms_px, rt12, pose_ok, inlier_mask, stage_ms, default_device());
     });
@@ -1489,10 +1491,7 @@ static cba_status extrinsic_dlt_impl(int32_t n_cams, int32_t n_views, int32_t n_
         if (n_cams < 1 || n_views < 1) throw std::runtime_error("Empty views or cameras provided");  // extrinsics.h:31-33
         if (n_blocks < 0) throw std::invalid_argument("n_blocks must be >= 0");
         if (!blk_offset || !kmtx5 || !c_T_r || !r_T_t || (n_blocks > 0 && (!blk_view || !blk_cam))) throw std::invalid_argument("null argument");
-        if (blk_offset[0] != 0) throw std::invalid_argument("block offsets must start at 0");
-        for (int b = 0; b < n_blocks; ++b)
-            if (blk_offset[b + 1] < blk_offset[b] || blk_offset[b + 1] - blk_offset[b] > 0x7fffffff)
-                throw std::invalid_argument("bad block offsets");
+        check_offsets(blk_offset, n_blocks, "block ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
         if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
         // the (view, camera) -> block table: the averaging order of the device stages comes from it, never from the block order
         std::vector<int32_t> table(static_cast<size_t>(n_views) * static_cast<size_t>(n_cams), -1);
@@ -1514,7 +1513,7 @@ static cba_status extrinsic_dlt_impl(int32_t n_cams, int32_t n_views, int32_t n_
                 for (int k = 0; k < 4; ++k) stage_ms[k] = 0.0;
             return;
         }
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         extrinsic_dlt_gpu(n_cams, n_views, n_blocks, blk_offset, blk_cam, table.data(), X, Y, u, v, kmtx5, c_T_r, r_T_t, blk_c_T_t, blk_ok,
                           stage_ms, default_device());
     });
@@ -1541,10 +1540,7 @@ static cba_status bundle_seed_impl(int32_t n_cams, int32_t n_blocks, const int64
             (n_blocks > 0 && (!blk_cam || !blk_b_T_g)))
             throw std::invalid_argument("null argument");
         if (given_mask && !g_T_c_given) throw std::invalid_argument("given_mask needs g_T_c_given");
-        if (blk_offset[0] != 0) throw std::invalid_argument("block offsets must start at 0");
-        for (int b = 0; b < n_blocks; ++b)
-            if (blk_offset[b + 1] < blk_offset[b] || blk_offset[b + 1] - blk_offset[b] > 0x7fffffff)
-                throw std::invalid_argument("bad block offsets");
+        check_offsets(blk_offset, n_blocks, "block ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
         if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
         for (int b = 0; b < n_blocks; ++b)
             if (blk_cam[b] < 0 || blk_cam[b] >= n_cams) throw std::invalid_argument("block " + std::to_string(b) + ": camera index out of range");
@@ -1581,7 +1577,7 @@ static cba_status bundle_seed_impl(int32_t n_cams, int32_t n_blocks, const int64
         if (stage_ms)
             for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
         if (n_blocks == 0) return;  // nothing for a device to do
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         bundle_seed_gpu(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, cam_start.data(), cam_blk.data(),
                         g_T_c, cam_status, cam_pairs, b_T_t_given, b_T_t, blk_c_T_t, blk_ok, stage_ms, default_device());
     });
@@ -1601,9 +1597,7 @@ static void check_problems(int32_t n_problems, const int64_t* offset, const doub
     if (n_problems < 0) throw std::invalid_argument("n_problems must be >= 0");
     if (n_problems == 0) return;
     if (!offset) throw std::invalid_argument("null argument");
-    if (offset[0] != 0) throw std::invalid_argument("offsets must start at 0");
-    for (int p = 0; p < n_problems; ++p)
-        if (offset[p + 1] < offset[p]) throw std::invalid_argument("offsets must not decrease");
+    check_offsets(offset, n_problems, "", OFF_FROM_ZERO);  // from 0, groups of any size (the chunked kernels index in int64)
     if (offset[n_problems] > 0 && (!x || !y || !u || !v)) throw std::invalid_argument("null argument");
 }
 
@@ -1635,7 +1629,7 @@ static cba_status fit_distortion_impl(int32_t n_problems, const int64_t* offset,
             for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
         if (n_problems == 0) return;
         if (!kmtx5 || !coeffs || !ok) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         distortion_fit_gpu(n_problems, offset, x, y, u, v, kmtx5, num_radial, mask, val, dual != 0, coeffs, inverse, ok, residuals, stage_ms,
                            default_device());
     });
@@ -1657,7 +1651,7 @@ cba_status cba_estimate_intrinsics_linear_batch(int32_t n_problems, const int64_
         if (n_problems == 0) return;
         if (!kmtx5 || !status || !fallback) throw std::invalid_argument("null argument");
         const double dlo[5] = {0.0, 0.0, 0.0, 0.0, -0.01}, dhi[5] = {2000.0, 2000.0, 1280.0, 720.0, 0.01};  // CalibrationBounds{}
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         intrinsics_linear_gpu(n_problems, offset, x, y, u, v, bounds_lo5 ? bounds_lo5 : dlo, bounds_hi5 ? bounds_hi5 : dhi, use_skew != 0,
                               kmtx5, status, fallback, default_device());
     });
@@ -1674,7 +1668,7 @@ static cba_status linear_iterative_impl(int32_t n_problems, const int64_t* offse
             for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
         if (n_problems == 0) return;
         if (!kmtx5 || !coeffs || !status || !iterations || !fallback) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         intrinsics_linear_iterative_gpu(n_problems, offset, x, y, u, v, num_radial, std::max(max_iterations, 0), use_skew != 0, kmtx5, coeffs,
                                         status, iterations, fallback, stage_ms, default_device());
     });
@@ -1748,7 +1742,7 @@ static cba_status camera_project_impl(int32_t camera_model, const double* intr, 
         if (n < 0) throw std::invalid_argument("n must be >= 0");
         if (n == 0) return;
         if (!xyz || !uv) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         camera_project_gpu(camera_model, intr, n, xyz, uv, stage_ms, default_device());
     });
 }
@@ -1760,7 +1754,7 @@ static cba_status camera_unproject_impl(int32_t camera_model, const double* intr
         if (n < 0) throw std::invalid_argument("n must be >= 0");
         if (n == 0) return;
         if (!uv || !xy) throw std::invalid_argument("null argument");
-        if (device_count() <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
+        require_device();
         camera_unproject_gpu(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, n, uv, xy, stage_ms, default_device());
     });
 }
@@ -1788,9 +1782,7 @@ static cba_status undistort_map_create_impl(int32_t camera_model, int32_t n_cams
             const double* k = new_k5 ? new_k5 + 5 * static_cast<size_t>(c) : intr + static_cast<size_t>(c) * ni;
             if (k[0] == 0.0 || k[1] == 0.0) throw std::invalid_argument("fx' and fy' must not be 0");
         }
-        const int ndev = device_count();
-        if (ndev <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-        if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
+        require_device(device);
         *out = reinterpret_cast<cba_undistort_map*>(undistort_map_create(camera_model, n_cams, intr, R, new_k5, width, height, stage_ms, device));
     });
 }

@@ -246,33 +246,15 @@ namespace {
 
 // device events between the stages (experiment builds' stage timing): 5 start, 0 uploaded, 1 moment passes, 2 chunk sums, 3 tail,
 // 4 residuals
-struct DfTimer {
-    hipEvent_t ev[6] = {};
-    explicit DfTimer(bool on) {
-        if (on)
-            for (hipEvent_t& e : ev) CBA_HIP(hipEventCreate(&e));
-    }
-    ~DfTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t s) {
-        if (ev[k]) CBA_HIP(hipEventRecord(ev[k], s));
-    }
-    double ms(int a, int b) const {
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
-        return t;
-    }
-};
+using DfTimer = StageTimer<6>;
 
 // the observations, the problem offsets and the chunk table, on the device (the host tables live as long as the call)
 struct DfInput {
     int n_problems = 0, n_chunks = 0;
     std::vector<int64_t> hb;
     std::vector<int32_t> hp, hc;
-    DevBuf<double> x, y, u, v;
-    DevBuf<int64_t> off, cbeg;
+    ObsSoA obs;
+    DevBuf<int64_t> cbeg;
     DevBuf<int32_t> cprob, pchunk;
 
     DfInput(int P, const int64_t* offset, const double* hx, const double* hy, const double* hu, const double* hv, hipStream_t s) {
@@ -286,17 +268,12 @@ struct DfInput {
             }
         }
         hc[P] = static_cast<int32_t>(hp.size());
-        const int64_t n = offset[P];
-        hb.push_back(n);
+        hb.push_back(offset[P]);
         n_chunks = static_cast<int>(hp.size());
-        x.alloc(static_cast<size_t>(n)); y.alloc(static_cast<size_t>(n)); u.alloc(static_cast<size_t>(n)); v.alloc(static_cast<size_t>(n));
-        off.alloc(static_cast<size_t>(P) + 1); cbeg.alloc(hb.size()); cprob.alloc(hp.size()); pchunk.alloc(hc.size());
-        x.upload(hx, static_cast<size_t>(n), s); y.upload(hy, static_cast<size_t>(n), s);
-        u.upload(hu, static_cast<size_t>(n), s); v.upload(hv, static_cast<size_t>(n), s);
-        off.upload(offset, static_cast<size_t>(P) + 1, s);
-        cbeg.upload(hb.data(), hb.size(), s);
-        cprob.upload(hp.data(), hp.size(), s);
-        pchunk.upload(hc.data(), hc.size(), s);
+        obs.upload(s, P, offset, hx, hy, hu, hv);
+        cbeg.assign(hb.data(), hb.size(), s);
+        cprob.assign(hp.data(), hp.size(), s);
+        pchunk.assign(hc.data(), hc.size(), s);
     }
 };
 
@@ -307,11 +284,11 @@ void df_moment_pass(const DfInput& in, bool dual, const double* dK, DevBuf<doubl
     part.alloc(static_cast<size_t>(std::max(in.n_chunks, 1)) * NM);
     if (in.n_chunks == 0) return;
     if (dual)
-        hipLaunchKernelGGL((k_df_moments<M, true>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.x.p, in.y.p, in.u.p,
-                           in.v.p, dK, part.p);
+        hipLaunchKernelGGL((k_df_moments<M, true>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.obs.X.p, in.obs.Y.p,
+                           in.obs.u.p, in.obs.v.p, dK, part.p);
     else
-        hipLaunchKernelGGL((k_df_moments<M, false>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.x.p, in.y.p, in.u.p,
-                           in.v.p, dK, part.p);
+        hipLaunchKernelGGL((k_df_moments<M, false>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.obs.X.p, in.obs.Y.p,
+                           in.obs.u.p, in.obs.v.p, dK, part.p);
     CBA_HIP(hipGetLastError());
 }
 
@@ -330,35 +307,34 @@ void df_fit_m(int P, const int64_t* offset, const double* x, const double* y, co
               const DfitFixed& fixed, bool dual, double* coeffs, double* inverse, int32_t* ok, double* residuals, double* stage_ms) {
     StreamLease lease;
     const hipStream_t s = lease;
-    DfTimer tm(stage_ms != nullptr);
-    tm.mark(5, s);
+    DfTimer tm(s, stage_ms != nullptr);
+    tm.mark(5);
     DfInput in(P, offset, x, y, u, v, s);
     DevBuf<double> dK, partf, momf, parti, momi, dC, dI, dR;
     DevBuf<int32_t> dok;
-    dK.alloc(5 * static_cast<size_t>(P));
-    dK.upload(kmtx5, 5 * static_cast<size_t>(P), s);
+    dK.assign(kmtx5, 5 * static_cast<size_t>(P), s);
     dC.alloc(static_cast<size_t>(P) * M);
     dok.alloc(static_cast<size_t>(P));
     if (dual) dI.alloc(static_cast<size_t>(P) * M);
-    tm.mark(0, s);
+    tm.mark(0);
     df_moment_pass<M>(in, false, dK.p, partf, s);
     if (dual) df_moment_pass<M>(in, true, dK.p, parti, s);
-    tm.mark(1, s);
+    tm.mark(1);
     df_chunk_sum<M>(in, partf, momf, s);
     if (dual) df_chunk_sum<M>(in, parti, momi, s);
-    tm.mark(2, s);
-    hipLaunchKernelGGL((k_df_fit_tail<M>), dim3(df_lane_blocks(P)), dim3(64), 0, s, P, in.off.p, momf.p, dual ? momi.p : nullptr, dK.p,
+    tm.mark(2);
+    hipLaunchKernelGGL((k_df_fit_tail<M>), dim3(df_lane_blocks(P)), dim3(64), 0, s, P, in.obs.off.p, momf.p, dual ? momi.p : nullptr, dK.p,
                        fixed, dC.p, dual ? dI.p : nullptr, dok.p);
     CBA_HIP(hipGetLastError());
-    tm.mark(3, s);
+    tm.mark(3);
     const int64_t n = offset[P];
     if (residuals && in.n_chunks > 0) {
         dR.alloc(2 * static_cast<size_t>(n));
-        hipLaunchKernelGGL((k_df_residuals<M>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.x.p, in.y.p, in.u.p,
-                           in.v.p, dK.p, dC.p, dok.p, dR.p);
+        hipLaunchKernelGGL((k_df_residuals<M>), dim3(in.n_chunks), dim3(DF_BLOCK), 0, s, in.cbeg.p, in.cprob.p, in.obs.X.p, in.obs.Y.p,
+                           in.obs.u.p, in.obs.v.p, dK.p, dC.p, dok.p, dR.p);
         CBA_HIP(hipGetLastError());
     }
-    tm.mark(4, s);
+    tm.mark(4);
     dC.download(coeffs, static_cast<size_t>(P) * M, s);
     if (dual) dI.download(inverse, static_cast<size_t>(P) * M, s);
     dok.download(ok, static_cast<size_t>(P), s);
@@ -379,23 +355,23 @@ void df_iter_m(int P, const int64_t* offset, const double* x, const double* y, c
                int use_skew, double* kmtx5, double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback, double* stage_ms) {
     StreamLease lease;
     const hipStream_t s = lease;
-    DfTimer tm(stage_ms != nullptr);
-    tm.mark(5, s);
+    DfTimer tm(s, stage_ms != nullptr);
+    tm.mark(5);
     DfInput in(P, offset, x, y, u, v, s);
     DevBuf<double> part, mom, dK, dC;
     DevBuf<int32_t> dst, dit, dfb;
     dK.alloc(5 * static_cast<size_t>(P)); dC.alloc(static_cast<size_t>(P) * M);
     dst.alloc(static_cast<size_t>(P)); dit.alloc(static_cast<size_t>(P)); dfb.alloc(static_cast<size_t>(P));
-    tm.mark(0, s);
+    tm.mark(0);
     df_moment_pass<M>(in, false, nullptr, part, s);
-    tm.mark(1, s);
+    tm.mark(1);
     df_chunk_sum<M>(in, part, mom, s);
-    tm.mark(2, s);
-    hipLaunchKernelGGL((k_df_iter_tail<M>), dim3(df_lane_blocks(P)), dim3(64), 0, s, P, in.off.p, mom.p, max_iterations, use_skew, dK.p,
+    tm.mark(2);
+    hipLaunchKernelGGL((k_df_iter_tail<M>), dim3(df_lane_blocks(P)), dim3(64), 0, s, P, in.obs.off.p, mom.p, max_iterations, use_skew, dK.p,
                        dC.p, dst.p, dit.p, dfb.p);
     CBA_HIP(hipGetLastError());
-    tm.mark(3, s);
-    tm.mark(4, s);
+    tm.mark(3);
+    tm.mark(4);
     dK.download(kmtx5, 5 * static_cast<size_t>(P), s);
     dC.download(coeffs, static_cast<size_t>(P) * M, s);
     dst.download(status, static_cast<size_t>(P), s);
@@ -448,7 +424,7 @@ void intrinsics_linear_gpu(int n_problems, const int64_t* offset, const double* 
     // accumulation per chunk in a call that is bound by its upload, and the shared moment kernel keeps one reduction order
     df_moment_pass<2>(in, false, nullptr, part, s);
     df_chunk_sum<2>(in, part, mom, s);
-    hipLaunchKernelGGL(k_df_linear_tail, dim3(df_lane_blocks(n_problems)), dim3(64), 0, s, n_problems, in.off.p, mom.p, use_skew, bounds,
+    hipLaunchKernelGGL(k_df_linear_tail, dim3(df_lane_blocks(n_problems)), dim3(64), 0, s, n_problems, in.obs.off.p, mom.p, use_skew, bounds,
                        dK.p, dst.p, dfb.p);
     CBA_HIP(hipGetLastError());
     dK.download(kmtx5, 5 * static_cast<size_t>(n_problems), s);

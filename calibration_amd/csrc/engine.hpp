@@ -106,6 +106,11 @@ struct DevBuf {
         if (count) CBA_HIP(hipMemcpyAsync(dst, p + first, count * sizeof(T), hipMemcpyDeviceToHost, s));
     }
     void zero(hipStream_t s) { CBA_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
+    // a host table on the device: alloc + upload
+    void assign(const T* src, size_t count, hipStream_t s) {
+        alloc(count);
+        upload(src, count, s);
+    }
 };
 
 // Page-locked host staging for the small device-to-host results of an LM step: a copy into pageable memory blocks the
@@ -148,6 +153,52 @@ struct StreamLease {
         }
     }
     operator hipStream_t() const { return s; }
+};
+
+// ---- host glue shared by the batched pipelines behind the C ABI ------------------------------------------
+// Stage timing of the experiment builds' _timed entry points: up to N device events on the call's stream.  The shipped library
+// passes stage_ms == nullptr everywhere, so `on` is false there: no event exists, mark() does nothing and ms() is 0.  The events
+// are created up front, outside the timed region.  (Hidden, like ObsSoA: internal helpers add nothing to the dynamic symbols.)
+template <int N>
+struct __attribute__((visibility("hidden"))) StageTimer {
+    hipStream_t stream;
+    hipEvent_t ev[N] = {};
+    bool marked[N] = {};
+    StageTimer(hipStream_t s, bool on) : stream(s) {
+        if (on)
+            for (hipEvent_t& e : ev) CBA_HIP(hipEventCreate(&e));
+    }
+    StageTimer(const StageTimer&) = delete;
+    StageTimer& operator=(const StageTimer&) = delete;
+    ~StageTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int k) {
+        if (!ev[k]) return;
+        CBA_HIP(hipEventRecord(ev[k], stream));
+        marked[k] = true;
+    }
+    // milliseconds from mark a to mark b (after the stream was synchronised); 0 when either was never recorded
+    double ms(int a, int b) const {
+        if (!marked[a] || !marked[b]) return 0.0;
+        float t = 0.0f;
+        CBA_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
+        return t;
+    }
+};
+
+// The observations of a call on the device: the four arrays of the off_h[n_groups] observations and the offset table
+// [n_groups + 1] of their groups (views, blocks, problems), queued on the call's stream.  Declare it after the stream lease.
+struct __attribute__((visibility("hidden"))) ObsSoA {
+    DevBuf<double> X, Y, u, v;
+    DevBuf<int64_t> off;
+    void upload(hipStream_t s, int n_groups, const int64_t* off_h, const double* X_h, const double* Y_h, const double* u_h,
+                const double* v_h) {
+        const size_t n = static_cast<size_t>(off_h[n_groups]);
+        X.assign(X_h, n, s); Y.assign(Y_h, n, s); u.assign(u_h, n, s); v.assign(v_h, n, s);
+        off.assign(off_h, static_cast<size_t>(n_groups) + 1, s);
+    }
 };
 
 struct Tile {          // 32 bytes, read with scalar loads (wave-uniform)

@@ -79,29 +79,6 @@ __global__ __launch_bounds__(EXT_CHUNK) void k_ext_target_avg(int n_views, int n
 }
 
 // ---- host glue -----------------------------------------------------------------------------------------------------------
-namespace {
-// device events between the stages (experiment builds' stage timing)
-struct ExtTimer {
-    hipEvent_t ev[4] = {};
-    explicit ExtTimer(bool on) {
-        if (on)
-            for (hipEvent_t& e : ev) CBA_HIP(hipEventCreate(&e));
-    }
-    ~ExtTimer() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t s) {
-        if (ev[k]) CBA_HIP(hipEventRecord(ev[k], s));
-    }
-    double ms(int a, int b) const {
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[a], ev[b]));
-        return t;
-    }
-};
-}  // namespace
-
 void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const int32_t* table,
                        const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r,
                        double* r_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device) {
@@ -109,32 +86,26 @@ void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        ExtTimer tm(stage_ms != nullptr);
-        const int64_t n_obs = blk_offset[n_blocks];
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_obs, 1));
-        const size_t n_tab = static_cast<size_t>(n_views) * static_cast<size_t>(n_cams);
-        DevBuf<double> dX, dY, du, dv, dK, dP, dC, dR;
-        DevBuf<int64_t> doff;
+        StageTimer<4> tm(stream, stage_ms != nullptr);  // device events between the stages
+        ObsSoA d;
+        DevBuf<double> dK, dP, dC, dR;
         DevBuf<int32_t> dcam, dtab, dok;
-        dX.alloc(n); dY.alloc(n); du.alloc(n); dv.alloc(n);
-        dK.alloc(5 * static_cast<size_t>(n_cams)); dP.alloc(7 * static_cast<size_t>(n_blocks)); dok.alloc(n_blocks);
+        d.upload(stream, n_blocks, blk_offset, X, Y, u, v);
+        dP.alloc(7 * static_cast<size_t>(n_blocks)); dok.alloc(n_blocks);
         dC.alloc(7 * static_cast<size_t>(n_cams)); dR.alloc(7 * static_cast<size_t>(n_views));
-        doff.alloc(n_blocks + 1); dcam.alloc(n_blocks); dtab.alloc(n_tab);
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        dK.upload(kmtx5, 5 * static_cast<size_t>(n_cams), stream);
-        doff.upload(blk_offset, n_blocks + 1, stream);
-        dcam.upload(blk_cam, n_blocks, stream);
-        dtab.upload(table, n_tab, stream);
-        tm.mark(0, stream);
-        launch_block_pose(n_blocks, doff.p, dcam.p, dX.p, dY.p, du.p, dv.p, dK.p, dP.p, dok.p, stream);
-        tm.mark(1, stream);
-        hipLaunchKernelGGL(k_ext_cam_avg, dim3(n_cams), dim3(EXT_CHUNK), 0, stream, n_views, n_cams, dtab.p, doff.p, dP.p, dC.p);
+        dK.assign(kmtx5, 5 * static_cast<size_t>(n_cams), stream);
+        dcam.assign(blk_cam, n_blocks, stream);
+        dtab.assign(table, static_cast<size_t>(n_views) * static_cast<size_t>(n_cams), stream);
+        tm.mark(0);
+        launch_block_pose(n_blocks, d.off.p, dcam.p, d.X.p, d.Y.p, d.u.p, d.v.p, dK.p, dP.p, dok.p, stream);
+        tm.mark(1);
+        hipLaunchKernelGGL(k_ext_cam_avg, dim3(n_cams), dim3(EXT_CHUNK), 0, stream, n_views, n_cams, dtab.p, d.off.p, dP.p, dC.p);
         CBA_HIP(hipGetLastError());
-        tm.mark(2, stream);
+        tm.mark(2);
         hipLaunchKernelGGL(k_ext_target_avg, dim3((n_views + EXT_CHUNK - 1) / EXT_CHUNK), dim3(EXT_CHUNK), 0, stream, n_views, n_cams,
-                           dtab.p, doff.p, dP.p, dC.p, dR.p);
+                           dtab.p, d.off.p, dP.p, dC.p, dR.p);
         CBA_HIP(hipGetLastError());
-        tm.mark(3, stream);
+        tm.mark(3);
         dC.download(c_T_r, 7 * static_cast<size_t>(n_cams), stream);
         dR.download(r_T_t, 7 * static_cast<size_t>(n_views), stream);
         if (blk_pose) dP.download(blk_pose, 7 * static_cast<size_t>(n_blocks), stream);

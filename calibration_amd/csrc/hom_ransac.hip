@@ -306,66 +306,42 @@ __global__ void k_hr_pose(int n_views, const int32_t* __restrict__ ok, const dou
 // ---- host glue -----------------------------------------------------------------------------------------------------------
 namespace {
 
-struct HrTimer {
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ev;
-    int at[HR_NMARKS];
-    explicit HrTimer(hipStream_t s) : stream(s) { for (int& a : at) a = -1; }
-    ~HrTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    void mark(int which) {
-        hipEvent_t e;
-        CBA_HIP(hipEventCreate(&e));
-        CBA_HIP(hipEventRecord(e, stream));
-        at[which] = static_cast<int>(ev.size());
-        ev.push_back(e);
-    }
-    double ms(int a, int b) const {
-        if (at[a] < 0 || at[b] < 0) return 0.0;
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[at[a]], ev[at[b]]));
-        return t;
-    }
-};
-void hmark(HrTimer* t, int which) { if (t) t->mark(which); }
+using HrTimer = StageTimer<HR_NMARKS>;
 
 // Device inputs and per-view homography outputs of one call
 struct HrViews {
-    DevBuf<double> X, Y, u, v, cand, h9, srms;
-    DevBuf<int64_t> off;
+    ObsSoA obs;
+    DevBuf<double> cand, h9, srms;
     DevBuf<int32_t> ok, cnt;
     DevBuf<uint8_t> mask;
 
     void upload(hipStream_t s, int n_views, const int64_t* off_h, const double* Xh, const double* Yh, const double* uh, const double* vh,
                 bool want_mask) {
-        const int64_t n_obs = off_h[n_views];
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_obs, 1));
-        X.alloc(n); Y.alloc(n); u.alloc(n); v.alloc(n); off.alloc(n_views + 1);
+        obs.upload(s, n_views, off_h, Xh, Yh, uh, vh);
         h9.alloc(9 * static_cast<size_t>(n_views)); srms.alloc(n_views); ok.alloc(n_views); cnt.alloc(n_views);
-        if (want_mask) mask.alloc(n);
-        X.upload(Xh, n_obs, s); Y.upload(Yh, n_obs, s); u.upload(uh, n_obs, s); v.upload(vh, n_obs, s);
-        off.upload(off_h, n_views + 1, s);
+        if (want_mask) mask.alloc(static_cast<size_t>(off_h[n_views]));
     }
 
     // every view's homography (RANSAC when o is given, else the all-points DLT), queued on s
-    void homographies(hipStream_t s, int n_views, const cba_ransac_options* o, int rescale, HrTimer* tm) {
+    void homographies(hipStream_t s, int n_views, const cba_ransac_options* o, int rescale, HrTimer& tm) {
         int nb = 1;
         if (o) {
             // max_iters <= CBA_RANSAC_MAX_ITERS (checked at the C ABI): at most 256 candidate records per view
             nb = std::max(1, (o->max_iters + HR_BLOCK - 1) / HR_BLOCK);
             cand.alloc(static_cast<size_t>(n_views) * nb * HR_CAND);
             hipLaunchKernelGGL(k_hr_score, dim3(n_views, nb), dim3(HR_BLOCK), 0, s, o->max_iters, o->thresh, o->min_inliers,
-                               o->refit_on_inliers, o->seed, off.p, X.p, Y.p, u.p, v.p, cand.p);
+                               o->refit_on_inliers, o->seed, obs.off.p, obs.X.p, obs.Y.p, obs.u.p, obs.v.p, cand.p);
         } else {
             cand.alloc(static_cast<size_t>(n_views) * HR_CAND);
-            hipLaunchKernelGGL(k_hr_dlt, dim3((n_views + HR_VIEW_WAVES - 1) / HR_VIEW_WAVES), dim3(64 * HR_VIEW_WAVES), 0, s, n_views, off.p,
-                               X.p, Y.p, u.p, v.p, cand.p);
+            hipLaunchKernelGGL(k_hr_dlt, dim3((n_views + HR_VIEW_WAVES - 1) / HR_VIEW_WAVES), dim3(64 * HR_VIEW_WAVES), 0, s, n_views,
+                               obs.off.p, obs.X.p, obs.Y.p, obs.u.p, obs.v.p, cand.p);
         }
         CBA_HIP(hipGetLastError());
-        hmark(tm, HM_SCORE);
-        hipLaunchKernelGGL(k_hr_finish, dim3(n_views), dim3(HR_BLOCK), 0, s, nb, o ? 1 : 0, rescale, o ? o->thresh : 0.0, off.p, X.p, Y.p, u.p,
-                           v.p, cand.p, h9.p, ok.p, cnt.p, srms.p, mask.p);
+        tm.mark(HM_SCORE);
+        hipLaunchKernelGGL(k_hr_finish, dim3(n_views), dim3(HR_BLOCK), 0, s, nb, o ? 1 : 0, rescale, o ? o->thresh : 0.0, obs.off.p, obs.X.p,
+                           obs.Y.p, obs.u.p, obs.v.p, cand.p, h9.p, ok.p, cnt.p, srms.p, mask.p);
         CBA_HIP(hipGetLastError());
-        hmark(tm, HM_HOM);
+        tm.mark(HM_HOM);
     }
 };
 
@@ -378,9 +354,10 @@ void homography_ransac_batch(int n_views, const int64_t* view_offset, const doub
     StreamLease lease;
     const hipStream_t stream = lease;
     {
+        HrTimer tm(stream, false);
         HrViews d;
         d.upload(stream, n_views, view_offset, X, Y, u, v, inlier_mask != nullptr);
-        d.homographies(stream, n_views, o, 0, nullptr);
+        d.homographies(stream, n_views, o, 0, tm);
         d.h9.download(h9, 9 * static_cast<size_t>(n_views), stream);
         d.ok.download(success, n_views, stream);
         d.cnt.download(inlier_count, n_views, stream);
@@ -399,8 +376,7 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
     const hipStream_t stream = lease;
     double kst[KS_SIZE];
     {
-        HrTimer tmr(stream);
-        HrTimer* tm = stage_ms ? &tmr : nullptr;
+        HrTimer tm(stream, stage_ms != nullptr);
         HrViews d;
         DevBuf<double> b10, dkst, dpose;
         DevBuf<int32_t> dpok;
@@ -411,15 +387,15 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
             b10.upload(bounds_lo5, 5, stream);
             b10.upload(bounds_hi5, 5, stream, 5);
         }
-        hmark(tm, HM_0);
+        tm.mark(HM_0);
         d.homographies(stream, n_views, o, 1, tm);
         hipLaunchKernelGGL(k_hr_zhang, dim3(1), dim3(64), 0, stream, n_views, d.ok.p, d.h9.p, has_bounds, b10.p, dkst.p);
         CBA_HIP(hipGetLastError());
-        hmark(tm, HM_ZHANG);
+        tm.mark(HM_ZHANG);
         hipLaunchKernelGGL(k_hr_pose, dim3((n_views + HR_BLOCK - 1) / HR_BLOCK), dim3(HR_BLOCK), 0, stream, n_views, d.ok.p, d.h9.p, dkst.p,
                            dpose.p, dpok.p);
         CBA_HIP(hipGetLastError());
-        hmark(tm, HM_POSE);
+        tm.mark(HM_POSE);
         dkst.download(kst, KS_SIZE, stream);
         d.h9.download(h9, 9 * static_cast<size_t>(n_views), stream);
         d.ok.download(view_ok, n_views, stream);
@@ -428,12 +404,12 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
         dpok.download(pose_ok, n_views, stream);
         if (inlier_mask) d.mask.download(inlier_mask, view_offset[n_views], stream);
         CBA_HIP(hipStreamSynchronize(stream));
-        if (tm) {  // stage_ms [5]: homographies (scoring), homographies (select + rms), Zhang + sanitize, poses, total
-            stage_ms[0] = tm->ms(HM_0, HM_SCORE);
-            stage_ms[1] = tm->ms(HM_SCORE, HM_HOM);
-            stage_ms[2] = tm->ms(HM_HOM, HM_ZHANG);
-            stage_ms[3] = tm->ms(HM_ZHANG, HM_POSE);
-            stage_ms[4] = tm->ms(HM_0, HM_POSE);
+        if (stage_ms) {  // stage_ms [5]: homographies (scoring), homographies (select + rms), Zhang + sanitize, poses, total
+            stage_ms[0] = tm.ms(HM_0, HM_SCORE);
+            stage_ms[1] = tm.ms(HM_SCORE, HM_HOM);
+            stage_ms[2] = tm.ms(HM_HOM, HM_ZHANG);
+            stage_ms[3] = tm.ms(HM_ZHANG, HM_POSE);
+            stage_ms[4] = tm.ms(HM_0, HM_POSE);
         }
     }
     *success = kst[KS_OK] != 0.0 ? 1 : 0;

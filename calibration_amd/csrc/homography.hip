@@ -47,22 +47,17 @@ void homography_batch(int n_views, const int64_t* view_offset, const double* X, 
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        const int64_t n_obs = view_offset[n_views];
-        DevBuf<double> dX, dY, du, dv;
-        DevBuf<int64_t> doff;
+        ObsSoA d;
         DevBuf<HomResult> dres;
-        dX.alloc(n_obs); dY.alloc(n_obs); du.alloc(n_obs); dv.alloc(n_obs);
-        doff.alloc(n_views + 1); dres.alloc(n_views);
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        doff.upload(view_offset, n_views + 1, stream);
+        d.upload(stream, n_views, view_offset, X, Y, u, v);
         std::vector<HomResult> h(n_views);
         for (int i = 0; i < n_views; ++i)  // HomographyBlocks::create (homography.cpp:79-84): the first 8 entries, as given
             for (int k = 0; k < 8; ++k) h[i].h[k] = h9[static_cast<size_t>(i) * 9 + k];
-        dres.upload(h.data(), n_views, stream);
+        dres.assign(h.data(), n_views, stream);
         const auto t0 = std::chrono::steady_clock::now();
         const int blocks = (n_views + HOM_WAVES_PER_BLOCK - 1) / HOM_WAVES_PER_BLOCK;
-        hipLaunchKernelGGL(k_homography, dim3(blocks), dim3(64 * HOM_WAVES_PER_BLOCK), 0, stream, n_views, doff.p, dX.p, dY.p, du.p,
-                           dv.p, o->huber_delta, o->epsilon, o->max_iterations, (cov64 && o->compute_covariance) ? 1 : 0, dres.p);
+        hipLaunchKernelGGL(k_homography, dim3(blocks), dim3(64 * HOM_WAVES_PER_BLOCK), 0, stream, n_views, d.off.p, d.X.p, d.Y.p,
+                           d.u.p, d.v.p, o->huber_delta, o->epsilon, o->max_iterations, (cov64 && o->compute_covariance) ? 1 : 0, dres.p);
         CBA_HIP(hipGetLastError());
         dres.download(h.data(), n_views, stream);
         CBA_HIP(hipStreamSynchronize(stream));

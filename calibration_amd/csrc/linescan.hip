@@ -332,27 +332,7 @@ namespace {
 int grid_for(int64_t n) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(LS_GRID, (n + LS_BLOCK - 1) / LS_BLOCK))); }
 
 // Optional stage timing (cba_calibrate_laser_plane_timed): events recorded between the stages of one call.
-struct StageTimer {
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ev;
-    int at[LS_NSTAGE_MARKS];
-    explicit StageTimer(hipStream_t s) : stream(s) { for (int& a : at) a = -1; }
-    ~StageTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    void mark(int which) {
-        hipEvent_t e;
-        CBA_HIP(hipEventCreate(&e));
-        CBA_HIP(hipEventRecord(e, stream));
-        at[which] = static_cast<int>(ev.size());
-        ev.push_back(e);
-    }
-    double ms(int a, int b) const {
-        if (at[a] < 0 || at[b] < 0) return 0.0;
-        float t = 0.0f;
-        CBA_HIP(hipEventElapsedTime(&t, ev[at[a]], ev[at[b]]));
-        return t;
-    }
-};
-void mark(StageTimer* t, int which) { if (t) t->mark(which); }
+using LsTimer = StageTimer<LS_NSTAGE_MARKS>;
 
 // The plane fit over the n (on the device: *dn, at most n_cap) compact points px/py/pz; cmask [n_cap] optional.  Queued on
 // `stream`; the caller synchronises and reads st (ST_SIZE doubles) back.
@@ -361,7 +341,7 @@ struct PlaneFitter {
     DevBuf<int32_t> hstate;
 
     void run(hipStream_t stream, int64_t n_cap, const int64_t* dn, const double* px, const double* py, const double* pz,
-             const cba_plane_fit_options& o, uint8_t* cmask, StageTimer* tm) {
+             const cba_plane_fit_options& o, uint8_t* cmask, LsTimer& tm) {
         const int G = grid_for(n_cap);
         part.alloc(6 * static_cast<size_t>(G));
         st.alloc(ST_SIZE);
@@ -374,7 +354,7 @@ struct PlaneFitter {
             hipLaunchKernelGGL(k_ls_fin, dim3(1), dim3(64), 0, stream, stage, G, set_scale, part.p, st.p);
             CBA_HIP(hipGetLastError());
         };
-        mark(tm, MK_FIT0);
+        tm.mark(MK_FIT0);
         mom(MOM_SUM, 0, nullptr);
         fin(FIN_CENTROID, 1);
         if (!o.use_ransac) {
@@ -382,7 +362,7 @@ struct PlaneFitter {
             fin(FIN_PLANE, 0);
             mom(MOM_RES, 0, cmask);
             fin(FIN_RMS, 0);
-            mark(tm, MK_FIT1);
+            tm.mark(MK_FIT1);
             return;
         }
         // max_iters <= CBA_PLANE_FIT_MAX_ITERS (checked at the C ABI), so Hp and the partial sizes below fit their types
@@ -395,18 +375,18 @@ struct PlaneFitter {
         hpart.alloc(static_cast<size_t>(LS_NMOM) * static_cast<size_t>(C) * static_cast<size_t>(Hp));
         hipLaunchKernelGGL(k_ls_hyp, dim3(hb), dim3(LS_BLOCK), 0, stream, H, Hp, o.seed, dn, px, py, pz, st.p, hyp.p, hstate.p);
         CBA_HIP(hipGetLastError());
-        mark(tm, MK_S1A);
+        tm.mark(MK_S1A);
         hipLaunchKernelGGL(k_ls_score<true>, dim3(hb, C), dim3(LS_BLOCK), 0, stream, Hp, C, o.thresh, dn, px, py, pz, st.p, hyp.p, hpart.p);
         CBA_HIP(hipGetLastError());
-        mark(tm, MK_S1B);
+        tm.mark(MK_S1B);
         hipLaunchKernelGGL(k_ls_refit, dim3(hb), dim3(LS_BLOCK), 0, stream, H, Hp, C, o.min_inliers, o.refit_on_inliers, hpart.p, hyp.p,
                            hstate.p, hyp2.p);
         CBA_HIP(hipGetLastError());
-        mark(tm, MK_S2A);
+        tm.mark(MK_S2A);
         hipLaunchKernelGGL(k_ls_score<false>, dim3(hb, C), dim3(LS_BLOCK), 0, stream, Hp, C, o.thresh, dn, px, py, pz, st.p, hyp2.p,
                            hpart.p);
         CBA_HIP(hipGetLastError());
-        mark(tm, MK_S2B);
+        tm.mark(MK_S2B);
         hipLaunchKernelGGL(k_ls_hyp_sum, dim3(hb), dim3(LS_BLOCK), 0, stream, H, Hp, C, hpart.p, hcnt.p, hrms.p);
         CBA_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_ls_pick, dim3(1), dim3(64), 0, stream, H, hstate.p, hcnt.p, hrms.p, hyp.p, hyp2.p, st.p);
@@ -425,7 +405,7 @@ struct PlaneFitter {
         CBA_HIP(hipGetLastError());
         mom(MOM_RES, 1, cmask);
         fin(FIN_RMS, 0);
-        mark(tm, MK_FIT1);
+        tm.mark(MK_FIT1);
     }
 };
 
@@ -439,13 +419,13 @@ void set_result_plane(const double* st, bool ransac, int iters, cba_laser_plane_
     std::strcpy(r->summary, ransac ? "ransac" : "linear_svd");
 }
 
-void timings(const StageTimer* t, double* ms) {
-    if (!t || !ms) return;
-    ms[0] = t->ms(MK_V0, MK_V1);
-    ms[1] = t->ms(MK_V1, MK_FIT0);
-    ms[2] = t->ms(MK_FIT0, MK_FIT1);
-    ms[3] = t->ms(MK_S1A, MK_S1B);
-    ms[4] = t->ms(MK_S2A, MK_S2B);
+void timings(const LsTimer& t, double* ms) {
+    if (!ms) return;
+    ms[0] = t.ms(MK_V0, MK_V1);
+    ms[1] = t.ms(MK_V1, MK_FIT0);
+    ms[2] = t.ms(MK_FIT0, MK_FIT1);
+    ms[3] = t.ms(MK_S1A, MK_S1B);
+    ms[4] = t.ms(MK_S2A, MK_S2B);
 }
 
 }  // namespace
@@ -474,29 +454,27 @@ void laser_plane_calibrate(int model, const double* intr, int n_inv, const doubl
     double st[ST_SIZE];
     int64_t n_valid = 0;
     {
-        StageTimer tmr(stream);
-        StageTimer* tm = stage_ms ? &tmr : nullptr;
-        DevBuf<double> dX, dY, du, dv, dnu, dnv, dlu, dlv, dgeo, px, py, pz, dxyz;
-        DevBuf<int64_t> dtoff, dloff, dcoff, dn;
+        LsTimer tm(stream, stage_ms != nullptr);
+        ObsSoA tgt;  // the target points
+        DevBuf<double> dnu, dnv, dlu, dlv, dgeo, px, py, pz, dxyz;
+        DevBuf<int64_t> dloff, dcoff, dn;
         DevBuf<int32_t> dok;
         DevBuf<uint8_t> dmask;
-        const size_t nt = static_cast<size_t>(std::max<int64_t>(n_t, 1)), nl = static_cast<size_t>(std::max<int64_t>(n_l, 1));
-        dX.alloc(nt); dY.alloc(nt); du.alloc(nt); dv.alloc(nt); dnu.alloc(nt); dnv.alloc(nt);
-        dlu.alloc(nl); dlv.alloc(nl); px.alloc(nl); py.alloc(nl); pz.alloc(nl);
-        dgeo.alloc(LS_GEO * static_cast<size_t>(n_views)); dok.alloc(n_views);
-        dtoff.alloc(n_views + 1); dloff.alloc(n_views + 1); dcoff.alloc(n_views); dn.alloc(1);
+        const size_t nt = static_cast<size_t>(n_t), nl = static_cast<size_t>(n_l);
+        tgt.upload(stream, n_views, toff, X, Y, u, v);
+        dnu.alloc(nt); dnv.alloc(nt); px.alloc(nl); py.alloc(nl); pz.alloc(nl);
+        dgeo.alloc(LS_GEO * static_cast<size_t>(n_views)); dok.alloc(n_views); dcoff.alloc(n_views); dn.alloc(1);
         if (points_xyz) dxyz.alloc(3 * nl);
         if (inlier_mask) dmask.alloc(nl);
-        dX.upload(X, n_t, stream); dY.upload(Y, n_t, stream); du.upload(u, n_t, stream); dv.upload(v, n_t, stream);
-        dlu.upload(lu, n_l, stream); dlv.upload(lv, n_l, stream);
-        dtoff.upload(toff, n_views + 1, stream); dloff.upload(loff, n_views + 1, stream);
-        mark(tm, MK_V0);
+        dlu.assign(lu, nl, stream); dlv.assign(lv, nl, stream);
+        dloff.assign(loff, static_cast<size_t>(n_views) + 1, stream);
+        tm.mark(MK_V0);
         hipLaunchKernelGGL(k_ls_views, dim3((n_views + LS_VIEW_WAVES - 1) / LS_VIEW_WAVES), dim3(64 * LS_VIEW_WAVES), 0, stream, n_views,
-                           dtoff.p, dX.p, dY.p, du.p, dv.p, cam, dnu.p, dnv.p, dgeo.p, dok.p);
+                           tgt.off.p, tgt.X.p, tgt.Y.p, tgt.u.p, tgt.v.p, cam, dnu.p, dnv.p, dgeo.p, dok.p);
         CBA_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_ls_prefix, dim3(1), dim3(64), 0, stream, n_views, dloff.p, dok.p, dcoff.p, dn.p);
         CBA_HIP(hipGetLastError());
-        mark(tm, MK_V1);
+        tm.mark(MK_V1);
         if (n_l > 0) {
             hipLaunchKernelGGL(k_ls_points, dim3(grid_for(n_l) * 2), dim3(LS_BLOCK), 0, stream, n_views, n_l, dloff.p, dlu.p, dlv.p, cam,
                                dgeo.p, dok.p, dcoff.p, px.p, py.p, pz.p, points_xyz ? dxyz.p : nullptr);
@@ -507,10 +485,10 @@ void laser_plane_calibrate(int model, const double* intr, int n_inv, const doubl
         fit.st.download(st, ST_SIZE, stream);
         dn.download(&n_valid, 1, stream);
         dok.download(ok.data(), n_views, stream);
-        if (points_xyz) dxyz.download(points_xyz, 3 * static_cast<size_t>(n_l), stream);
+        if (points_xyz) dxyz.download(points_xyz, 3 * nl, stream);
         if (inlier_mask) {
             cmask.resize(nl);
-            dmask.download(cmask.data(), n_l, stream);
+            dmask.download(cmask.data(), nl, stream);
         }
         CBA_HIP(hipStreamSynchronize(stream));
         timings(tm, stage_ms);
@@ -546,14 +524,15 @@ void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, dou
         DevBuf<double> dxyz, px, py, pz;
         DevBuf<int64_t> dn;
         DevBuf<uint8_t> dmask;
-        dxyz.alloc(3 * static_cast<size_t>(n)); px.alloc(n); py.alloc(n); pz.alloc(n); dn.alloc(1);
+        px.alloc(n); py.alloc(n); pz.alloc(n);
         if (mask) dmask.alloc(n);
-        dxyz.upload(xyz, 3 * static_cast<size_t>(n), stream);
-        dn.upload(&n, 1, stream);
+        dxyz.assign(xyz, 3 * static_cast<size_t>(n), stream);
+        dn.assign(&n, 1, stream);
         hipLaunchKernelGGL(k_ls_aos_to_soa, dim3(grid_for(n)), dim3(LS_BLOCK), 0, stream, n, dxyz.p, px.p, py.p, pz.p);
         CBA_HIP(hipGetLastError());
+        LsTimer tm(stream, false);
         PlaneFitter fit;
-        fit.run(stream, n, dn.p, px.p, py.p, pz.p, o, mask ? dmask.p : nullptr, nullptr);
+        fit.run(stream, n, dn.p, px.p, py.p, pz.p, o, mask ? dmask.p : nullptr, tm);
         fit.st.download(st, ST_SIZE, stream);
         if (mask) dmask.download(mask, n, stream);
         CBA_HIP(hipStreamSynchronize(stream));

@@ -46,14 +46,11 @@ void planar_pose_batch(int n_views, const int64_t* view_offset, const double* X,
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        const int64_t n_obs = view_offset[n_views];
-        DevBuf<double> dX, dY, du, dv, dK;
-        DevBuf<int64_t> doff;
+        ObsSoA d;
+        DevBuf<double> dK;
         DevBuf<VPResult> dres;
-        dX.alloc(n_obs); dY.alloc(n_obs); du.alloc(n_obs); dv.alloc(n_obs); dK.alloc(5);
-        doff.alloc(n_views + 1); dres.alloc(n_views);
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        dK.upload(kmtx5, 5, stream); doff.upload(view_offset, n_views + 1, stream);
+        d.upload(stream, n_views, view_offset, X, Y, u, v);
+        dK.assign(kmtx5, 5, stream);
         std::vector<VPResult> h(n_views);
         for (int i = 0; i < n_views; ++i) {
             // ceres::RotationMatrixToAngleAxis of the initial rotation (planarpose.cpp:89-93)
@@ -63,12 +60,12 @@ void planar_pose_batch(int n_views, const int64_t* view_offset, const double* X,
             quat_to_angle_axis_ceres(q, h[i].pose6);
             for (int k = 0; k < 3; ++k) h[i].pose6[3 + k] = p[4 + k];
         }
-        dres.upload(h.data(), n_views, stream);
+        dres.assign(h.data(), n_views, stream);
         const auto t0 = std::chrono::steady_clock::now();
         const dim3 grid((n_views + VP_WAVES_PER_BLOCK - 1) / VP_WAVES_PER_BLOCK), block(64 * VP_WAVES_PER_BLOCK);
         const int want_cov = (cov && o->compute_covariance) ? 1 : 0;
 #define CBA_VP_LAUNCH(NR)                                                                                                          \
-    hipLaunchKernelGGL(k_planar_pose<NR>, grid, block, 0, stream, n_views, doff.p, dX.p, dY.p, du.p, dv.p, dK.p, num_radial,       \
+    hipLaunchKernelGGL(k_planar_pose<NR>, grid, block, 0, stream, n_views, d.off.p, d.X.p, d.Y.p, d.u.p, d.v.p, dK.p, num_radial,  \
                        o->huber_delta, o->epsilon, o->max_iterations, want_cov, dres.p)
         switch (num_radial) {  // the design-matrix width nr + 2 is a compile-time constant of the kernel: no stack arrays
             case 0: CBA_VP_LAUNCH(0); break;

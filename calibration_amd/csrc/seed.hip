@@ -45,17 +45,13 @@ void dlt_homography_batch(int n_views, const int64_t* view_offset, const double*
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        const int64_t n_obs = view_offset[n_views];
-        DevBuf<double> dX, dY, du, dv, dH;
-        DevBuf<int64_t> doff;
+        ObsSoA d;
+        DevBuf<double> dH;
         DevBuf<int32_t> dok;
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_obs, 1));
-        dX.alloc(n); dY.alloc(n); du.alloc(n); dv.alloc(n); dH.alloc(9 * static_cast<size_t>(n_views)); dok.alloc(n_views);
-        doff.alloc(n_views + 1);
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        doff.upload(view_offset, n_views + 1, stream);
+        d.upload(stream, n_views, view_offset, X, Y, u, v);
+        dH.alloc(9 * static_cast<size_t>(n_views)); dok.alloc(n_views);
         hipLaunchKernelGGL(k_dlt_homography, dim3((n_views + SEED_WAVES - 1) / SEED_WAVES), dim3(64 * SEED_WAVES), 0, stream, n_views,
-                           doff.p, dX.p, dY.p, du.p, dv.p, dH.p, dok.p);
+                           d.off.p, d.X.p, d.Y.p, d.u.p, d.v.p, dH.p, dok.p);
         CBA_HIP(hipGetLastError());
         dH.download(H9, 9 * static_cast<size_t>(n_views), stream);
         dok.download(ok, n_views, stream);
@@ -69,16 +65,12 @@ void planar_seed_batch(int n_views, const int64_t* view_offset, const double* X,
     StreamLease lease;
     const hipStream_t stream = lease;
     {
-        const int64_t n_obs = view_offset[n_views];
-        DevBuf<double> dX, dY, du, dv, dK, dP;
-        DevBuf<int64_t> doff;
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_obs, 1));
-        dX.alloc(n); dY.alloc(n); du.alloc(n); dv.alloc(n); dK.alloc(5); dP.alloc(7 * static_cast<size_t>(n_views));
-        doff.alloc(n_views + 1);
-        dX.upload(X, n_obs, stream); dY.upload(Y, n_obs, stream); du.upload(u, n_obs, stream); dv.upload(v, n_obs, stream);
-        dK.upload(kmtx5, 5, stream); doff.upload(view_offset, n_views + 1, stream);
+        ObsSoA d;
+        DevBuf<double> dK, dP;
+        d.upload(stream, n_views, view_offset, X, Y, u, v);
+        dK.assign(kmtx5, 5, stream); dP.alloc(7 * static_cast<size_t>(n_views));
         hipLaunchKernelGGL(k_planar_seed, dim3((n_views + SEED_WAVES - 1) / SEED_WAVES), dim3(64 * SEED_WAVES), 0, stream, n_views,
-                           doff.p, dX.p, dY.p, du.p, dv.p, dK.p, dP.p);
+                           d.off.p, d.X.p, d.Y.p, d.u.p, d.v.p, dK.p, dP.p);
         CBA_HIP(hipGetLastError());
         dP.download(pose7, 7 * static_cast<size_t>(n_views), stream);
         CBA_HIP(hipStreamSynchronize(stream));

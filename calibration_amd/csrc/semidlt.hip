@@ -64,8 +64,8 @@ __global__ void k_sd_alpha(int n_views, const double* __restrict__ out1, double*
     for (int a = 0; a < m; ++a) al[a] = acc[e + a];
     for (int a = 0; a < m * m; ++a) sums[a] = Nf[a];
     for (int a = 0; a < m; ++a) sums[m * m + a] = al[a];
-    const bool ok = vp_chol<m>(Nf);
-    if (ok) vp_chol_solve<m>(Nf, al);
+    const bool ok = chol_n<m>(Nf);
+    if (ok) chol_solve_n<m>(Nf, al);
     for (int a = 0; a < m; ++a) sums[m * m + m + a] = ok ? al[a] : 0.0;
     sums[m * m + 2 * m] = ok ? 1.0 : 0.0;
 }
@@ -93,8 +93,8 @@ __global__ void k_sd_alpha_finish(const double* __restrict__ raw, double* __rest
     for (int a = 0; a < m; ++a) al[a] = raw[e + a];
     for (int a = 0; a < m * m; ++a) sums[a] = Nf[a];
     for (int a = 0; a < m; ++a) sums[m * m + a] = al[a];
-    const bool ok = vp_chol<m>(Nf);
-    if (ok) vp_chol_solve<m>(Nf, al);
+    const bool ok = chol_n<m>(Nf);
+    if (ok) chol_solve_n<m>(Nf, al);
     for (int a = 0; a < m; ++a) sums[m * m + m + a] = ok ? al[a] : 0.0;
     sums[m * m + 2 * m] = ok ? 1.0 : 0.0;
 }
@@ -141,8 +141,8 @@ namespace {
 struct HipSemiDlt final : SemiDltEval {
     StreamLease lease;  // before the buffers: released after them
     hipStream_t stream = lease;
-    DevBuf<double> X, Y, u, v, kappa, poses, out1, sums, raw, out2, alpha, sview;
-    DevBuf<int64_t> off;
+    ObsSoA obs;  // this rank's views
+    DevBuf<double> kappa, poses, out1, sums, raw, out2, alpha, sview;
     PinnedBuf<double> stage;  // host-callback transport: the exchanged range on its way through the host
     dim3 grid, block;
     int Vl = 0, v0 = 0;  // this rank's views [v0, v0 + Vl) of the V views of the problem
@@ -160,11 +160,7 @@ struct HipSemiDlt final : SemiDltEval {
         fn = allreduce; user = allreduce_user; rccl = rccl_comm; multi = n_views_total >= 0;
         if (multi && !fn && !rccl) throw std::invalid_argument("a sharded semi-DLT solve needs a transport");
         if (v0 < 0 || v0 + Vl > V) throw std::invalid_argument("view range outside the problem");
-        const int64_t n_loc = view_offset[Vl];
-        const size_t n = static_cast<size_t>(std::max<int64_t>(n_loc, 1));
-        X.alloc(n); Y.alloc(n); u.alloc(n); v.alloc(n);
-        X.upload(hX, n_loc, stream); Y.upload(hY, n_loc, stream); u.upload(hu, n_loc, stream); v.upload(hv, n_loc, stream);
-        off.alloc(Vl + 1); off.upload(view_offset, Vl + 1, stream);
+        obs.upload(stream, Vl, view_offset, hX, hY, hu, hv);
         kappa.alloc(5); poses.alloc(7 * static_cast<size_t>(V));
         out1.alloc(static_cast<size_t>(std::max(1, Vl)) * 20); sums.alloc(64); raw.alloc(64); alpha.alloc(8);
         out2.alloc(static_cast<size_t>(V) * n2()); sview.alloc(V);
@@ -219,7 +215,7 @@ struct HipSemiDlt final : SemiDltEval {
         default: hipLaunchKernelGGL(KERNEL<3>, G, B, 0, stream, __VA_ARGS__); break;                   \
     }
     void launch_pass1() {
-        if (Vl > 0) SD_DISPATCH(k_sd_pass1, grid, block, Vl, off.p, X.p, Y.p, u.p, v.p, kappa.p, my_poses(), out1.p)
+        if (Vl > 0) SD_DISPATCH(k_sd_pass1, grid, block, Vl, obs.off.p, obs.X.p, obs.Y.p, obs.u.p, obs.v.p, kappa.p, my_poses(), out1.p)
         if (!multi) {
             SD_DISPATCH(k_sd_alpha, dim3(1), dim3(64), Vl, out1.p, sums.p)
             return;
@@ -245,7 +241,7 @@ struct HipSemiDlt final : SemiDltEval {
         launch_pass1();
         const int mm = m();
         if (Vl > 0)
-            SD_DISPATCH(k_sd_pass2, grid, block, Vl, off.p, X.p, Y.p, u.p, v.p, kappa.p, my_poses(), sums.p + mm * mm + mm,
+            SD_DISPATCH(k_sd_pass2, grid, block, Vl, obs.off.p, obs.X.p, obs.Y.p, obs.u.p, obs.v.p, kappa.p, my_poses(), sums.p + mm * mm + mm,
                         out2.p + static_cast<size_t>(v0) * n2())
         CBA_HIP(hipGetLastError());
         gather_rows(out2, static_cast<size_t>(n2()));
@@ -260,7 +256,7 @@ struct HipSemiDlt final : SemiDltEval {
     void resid(const double* kappa5, const double* poses7, const double* al, double* s_view) override {
         put(kappa5, poses7);
         alpha.upload(al, m(), stream);
-        if (Vl > 0) SD_DISPATCH(k_sd_resid, grid, block, Vl, off.p, X.p, Y.p, u.p, v.p, kappa.p, my_poses(), alpha.p, sview.p + v0)
+        if (Vl > 0) SD_DISPATCH(k_sd_resid, grid, block, Vl, obs.off.p, obs.X.p, obs.Y.p, obs.u.p, obs.v.p, kappa.p, my_poses(), alpha.p, sview.p + v0)
         CBA_HIP(hipGetLastError());
         gather_rows(sview, 1);
         sview.download(s_view, V, stream);

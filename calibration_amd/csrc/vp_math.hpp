@@ -137,36 +137,11 @@ CBA_HD void vp_row(const VPView& V, const double* pose6, int i, bool deriv, VPRo
     R.dy[3] = 0.0; R.dy[4] = iz; R.dy[5] = -y * iz;
 }
 
-// small SPD solve (m <= 5), in place lower Cholesky of M (row-major m x m); false if not PD
+// the small SPD solve (m <= 5) is small_lm.hpp's chol_n / chol_solve_n; these names remain for the test-only host builds
 template <int m>
-CBA_HD bool vp_chol(double* M) {
-    for (int j = 0; j < m; ++j) {
-        double d = M[j * m + j];
-        for (int k = 0; k < j; ++k) d -= M[j * m + k] * M[j * m + k];
-        if (!(d > 0.0)) return false;
-        d = sqrt(d);
-        M[j * m + j] = d;
-        for (int i = j + 1; i < m; ++i) {
-            double s = M[i * m + j];
-            for (int k = 0; k < j; ++k) s -= M[i * m + k] * M[j * m + k];
-            M[i * m + j] = s / d;
-        }
-    }
-    return true;
-}
+CBA_HD bool vp_chol(double* M) { return chol_n<m>(M); }
 template <int m>
-CBA_HD void vp_chol_solve(const double* L, double* b) {
-    for (int i = 0; i < m; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s -= L[i * m + k] * b[k];
-        b[i] = s / L[i * m + i];
-    }
-    for (int i = m - 1; i >= 0; --i) {
-        double s = b[i];
-        for (int k = i + 1; k < m; ++k) s -= L[k * m + i] * b[k];
-        b[i] = s / L[i * m + i];
-    }
-}
+CBA_HD void vp_chol_solve(const double* L, double* b) { chol_solve_n<m>(L, b); }
 
 // Evaluate at pose6: alpha, s = |r|^2 and (if want_jac) the UNWEIGHTED H = J^T J (36, full), g = J^T r (6).
 // Returns false when fit_distortion_full would fail (N < 8, distortion.h:236-239) or A^T A is singular.
@@ -193,9 +168,9 @@ CBA_HD bool vp_evaluate(const VPView& V, Coop& co, const double* pose6, bool wan
         rhs[a] = co.sum(rhs[a]);
         for (int c = 0; c <= a; ++c) M[a * m + c] = co.sum(M[a * m + c]);
     }
-    if (!vp_chol<m>(M)) return false;
+    if (!chol_n<m>(M)) return false;
     for (int a = 0; a < m; ++a) alpha[a] = rhs[a];
-    vp_chol_solve<m>(M, alpha);
+    chol_solve_n<m>(M, alpha);
     double s = 0.0;
     double G[6][VP_MAX_M];
     for (int k = 0; k < 6; ++k) for (int a = 0; a < VP_MAX_M; ++a) G[k][a] = 0.0;
@@ -221,7 +196,7 @@ CBA_HD bool vp_evaluate(const VPView& V, Coop& co, const double* pose6, bool wan
     if (!want_jac) return true;
     for (int k = 0; k < 6; ++k) {
         for (int a = 0; a < m; ++a) G[k][a] = co.sum(G[k][a]);
-        vp_chol_solve<m>(M, G[k]);  // c_k = (A^T A)^-1 G_k
+        chol_solve_n<m>(M, G[k]);  // c_k = (A^T A)^-1 G_k
     }
     double Hs[21], gs[6];  // upper triangle of H, row-major
     for (int a = 0; a < 21; ++a) Hs[a] = 0.0;
