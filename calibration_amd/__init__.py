@@ -89,6 +89,11 @@ from .camera import (  # noqa: F401
     undistort,
     unproject,
 )
+from .triangulate import (  # noqa: F401
+    TriangulateOptions,
+    TriangulationResult,
+    triangulate,
+)
 from .diagnostics import (  # noqa: F401
     ResidualStats,
     RobustOptions,

@@ -27,6 +27,9 @@ CAMERA_PINHOLE_BC, CAMERA_SCHEIMPFLUG = 0, 1
 # cba_undistort_map_apply: image element types (calibba.h)
 DTYPE_U8, DTYPE_F32 = 0, 1
 IMAGE_MAX_SIDE = 32768
+# cba_triangulate: per-point status (calibba.h)
+TRI_OK, TRI_NOT_CONVERGED, TRI_BEHIND, TRI_DEGENERATE, TRI_TOO_FEW = range(5)
+TRI_MAX_CAMS = 16
 TERM_CONVERGENCE, TERM_NO_CONVERGENCE, TERM_FAILURE = 0, 1, 2
 RCCL_UNIQUE_ID_BYTES = 128
 
@@ -34,6 +37,7 @@ c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
 c_uint8_p = C.POINTER(C.c_uint8)
+c_uint32_p = C.POINTER(C.c_uint32)
 
 
 class CbaOptions(C.Structure):
@@ -133,6 +137,17 @@ class CbaLaserPlaneResult(C.Structure):
         ("n_views_used", C.c_int32),
         ("iters", C.c_int32),
         ("summary", C.c_char * 16),
+    ]
+
+
+class CbaTriangulateOptions(C.Structure):
+    """``cba_triangulate_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("max_iterations", C.c_int32),
+        ("step_tolerance", C.c_double),
+        ("min_cams", C.c_int32),
+        ("max_reproj_px", C.c_double),
     ]
 
 
@@ -343,6 +358,10 @@ PROTOTYPES = {
     "cba_undistort_map_apply": (
         C.c_int32, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "cba_undistort_map_destroy": (None, [C.c_void_p]),
+    "cba_triangulate_options_default": (None, [C.POINTER(CbaTriangulateOptions)]),
+    "cba_triangulate": (
+        C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int64, c_double_p,
+                    C.POINTER(CbaTriangulateOptions), c_double_p, c_double_p, c_uint32_p, c_int32_p, c_double_p]),
 }
 
 

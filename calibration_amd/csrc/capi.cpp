@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <exception>
+#include <limits>
 #include <mutex>
 #include <thread>
 #include <cstring>
@@ -1852,6 +1853,61 @@ __attribute__((visibility("default"))) cba_status cba_undistort_map_apply_timed(
                                                                                 double* stage_ms) {
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
+}
+#endif
+
+// ---- multi-camera triangulation (triangulate.hip, tri_math.hpp) ---------------------------------------------------------------
+void cba_triangulate_options_default(cba_triangulate_options* o) {
+    if (!o) return;
+    o->max_iterations = 10;
+    o->step_tolerance = 1e-12;
+    o->min_cams = 2;
+    o->max_reproj_px = std::numeric_limits<double>::infinity();
+}
+
+static cba_status triangulate_impl(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs,
+                                   const double* inverse_coeffs, const double* c_T_r, int64_t n, const double* uv,
+                                   const cba_triangulate_options* opts, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
+                                   double* cov6, int32_t* linearisations, double* stage_ms) {
+    return guarded([&] {
+        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
+        if (n_cams < 2 || n_cams > CBA_TRI_MAX_CAMS) throw std::invalid_argument("n_cams must be in [2, 16]");
+        if (!c_T_r || !opts) throw std::invalid_argument("null argument");
+        const int ni = camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10;
+        for (int c = 0; c < n_cams; ++c)
+            if (intr[static_cast<size_t>(c) * ni] == 0.0 || intr[static_cast<size_t>(c) * ni + 1] == 0.0)
+                throw std::invalid_argument("fx and fy must not be 0");
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (opts->max_iterations < 0) throw std::invalid_argument("max_iterations must be >= 0");
+        if (!(opts->step_tolerance >= 0.0)) throw std::invalid_argument("step_tolerance must be >= 0");
+        if (!(opts->max_reproj_px > 0.0)) throw std::invalid_argument("max_reproj_px must be > 0");
+        if (n == 0) return;
+        if (!uv || !xyz || !status) throw std::invalid_argument("null argument");
+        require_device();
+        triangulate_gpu(camera_model, n_cams, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, c_T_r, n, uv, *opts, xyz, rms_px,
+                        used_mask, status, cov6, linearisations, stage_ms, default_device());
+    });
+}
+
+cba_status cba_triangulate(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                           const double* c_T_r, int64_t n, const double* uv, const cba_triangulate_options* opts, double* xyz,
+                           double* rms_px, uint32_t* used_mask, int32_t* status, double* cov6) {
+    return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px, used_mask, status,
+                            cov6, nullptr, nullptr);
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_triangulate.py): cba_triangulate timing its stages on the device (stage_ms [3] = upload,
+// kernel, download) and returning each point's number of linearisations.  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_triangulate_timed(int32_t camera_model, int32_t n_cams, const double* intr,
+                                                                        int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                                                        const double* c_T_r, int64_t n, const double* uv,
+                                                                        const cba_triangulate_options* opts, double* xyz, double* rms_px,
+                                                                        uint32_t* used_mask, int32_t* status, double* cov6,
+                                                                        int32_t* linearisations, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px, used_mask, status,
+                            cov6, linearisations, stage_ms);
 }
 #endif
 

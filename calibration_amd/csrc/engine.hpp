@@ -416,6 +416,11 @@ void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int 
                          const void* src, void* dst, double* stage_ms);
 void undistort_map_destroy(UndistortMap* m) noexcept;
 int undistort_map_cams(const UndistortMap* m);
+// triangulate.hip: cba_triangulate (checked by the caller; rms_px, used_mask, cov6 optional; linearisations [n] and stage_ms [3] =
+// upload, kernel, download optional: the experiment builds' per-point pass counts and timing)
+void triangulate_gpu(int model, int n_cams, const double* intr, int n_inv, const double* inv, const double* c_T_r, int64_t n,
+                     const double* uv, const cba_triangulate_options& o, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
+                     double* cov6, int32_t* linearisations, double* stage_ms, int device);
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

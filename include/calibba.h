@@ -798,6 +798,71 @@ cba_status cba_undistort_map_apply(cba_undistort_map* h, int32_t n_images, const
                                    int32_t channels, int32_t dtype, double border, const void* src, void* dst);
 void cba_undistort_map_destroy(cba_undistort_map* h);
 
+/* ---- multi-camera triangulation (no counterpart in the reference) -----------------------------------------------------------
+ *
+ * cba_triangulate turns matched pixels of n_cams calibrated cameras into 3D points in the reference frame, one independent small
+ * nonlinear least-squares problem per point, all on the device in fp64.
+ *
+ * Inputs: n_cams cameras of one model, 2 <= n_cams <= CBA_TRI_MAX_CAMS; camera_model and intr [n_cams][10 | 12] as above; optional
+ * inverse_coeffs [n_cams][n_inverse_coeffs] with the meaning they have in cba_camera_unproject (NULL: the 5-step fixed point);
+ * c_T_r [n_cams][7], pose7 rows [qw qx qy qz tx ty tz] mapping the reference frame to each camera, exactly the rows
+ * cba_estimate_extrinsic_dlt and cba_optimize_extrinsics return (the rotation is the quaternion's matrix without normalisation); n
+ * points with pixels uv [n_cams][n][2], camera-major: each camera's slice has the layout cba_camera_project writes.  A non-finite
+ * coordinate means "this camera did not see this point".
+ *
+ * Outputs: xyz [n][3] (reference frame); rms_px [n] = sqrt(sum over the used cameras of (e_u^2 + e_v^2) / n_used), evaluated with
+ * the projection of cba_camera_project at P = R_c X + t_c (each row summed left to right, then + t), so it agrees with a round trip
+ * through that entry point; used_mask [n] (bit c: camera c was used); status [n] (cba_tri_status); optional cov6 [n][6] =
+ * (J^T J)^-1 at the solution in the order 00 01 02 11 12 22: the covariance of X for unit pixel sigma, the caller scales it.
+ * rms_px, used_mask and cov6 may be NULL.
+ *
+ * Per point:
+ * 1. Seed.  For every camera of the set (first: the cameras with a finite pixel), in camera order: (x, y) = the unprojection of
+ *    cba_camera_unproject, d = R_c^T (x, y, 1) / |.|, o = -R_c^T t_c; A = sum (I - d d^T), b = sum (I - d d^T) o.  Fewer than
+ *    max(min_cams, 2) cameras: CBA_TRI_TOO_FEW, NaN outputs, used_mask 0.  A X = b by the unpivoted 3 x 3 Cholesky; when it fails or
+ *    a pivot (a squared diagonal entry of L) is <= 1e-12 n_used (two rays closer than ~2e-6 rad to parallel): CBA_TRI_DEGENERATE,
+ *    NaN outputs, used_mask = the set.
+ * 2. Refinement.  Levenberg-Marquardt on sum_c |project_c(R_c X + t_c) - uv_c|^2 through the full forward model.  Rows of J are
+ *    (du/dP) R_c and (dv/dP) R_c; H = J^T J, g = J^T r; (H + lambda diag H) delta = -g by Cholesky (a failure counts as a rejected
+ *    step).  The trial X + delta is accepted when every used camera has a positive denominator there (z for the pinhole, the sensor
+ *    denominator for Scheimpflug) and its cost does not exceed the current one by more than the cost's rounding floor
+ *    s = 4e-12 px sqrt(n_used cost); then lambda <- max(lambda / 10, 1e-10), otherwise lambda <- 10 lambda.  lambda starts at 1e-4.
+ *    The iteration stops with CBA_TRI_OK after the step (accepted or not) whose |delta| <= step_tolerance |X|, or after an accepted
+ *    step that lowers the cost by no more than s, and with CBA_TRI_NOT_CONVERGED after max_iterations steps (0: the seed is
+ *    returned); outputs are written either way.  (s bounds |sum 2 r e| for pixel roundings e of 1e-12 px.  Below it the sign of a
+ *    cost difference is noise, and with two cameras the rounding of J^T r alone keeps |delta| near 3e-12 |X|, so the step rule
+ *    cannot end such a point at the default tolerance.)
+ * 3. Outlier cameras (max_reproj_px, +inf = off).  When the largest per-camera error sqrt(e_u^2 + e_v^2) at the result exceeds it
+ *    and more than max(min_cams, 2) cameras are in the set, that camera (the lowest index among equals) leaves the set and the
+ *    point starts again at step 1: the result is, to the bit, that of a call in which that pixel was NaN.
+ * 4. A final point with a non-positive denominator in a used camera has status CBA_TRI_BEHIND (outputs written).  cov6 is the
+ *    Cholesky inverse of the H of the last accepted linearisation (the seed's when no step was accepted); NaN where H is not
+ *    positive definite.
+ *
+ * A point's result depends on nothing but its own pixels.  Errors (CBA_ERR_INVALID_ARGUMENT, before any device work): an unknown
+ * model; n_cams outside [2, 16]; an inverse count outside [2, 16]; fx or fy equal to 0; n < 0; max_iterations < 0; a negative or NaN
+ * step_tolerance; max_reproj_px not > 0; NULL intr, c_T_r, opts, or (for n > 0) uv, xyz, status.  n == 0 is no work. */
+#define CBA_TRI_MAX_CAMS 16
+typedef enum cba_tri_status {
+    CBA_TRI_OK = 0,
+    CBA_TRI_NOT_CONVERGED = 1, /* max_iterations steps without meeting step_tolerance */
+    CBA_TRI_BEHIND = 2,        /* the point is not in front of every used camera */
+    CBA_TRI_DEGENERATE = 3,    /* parallel rays: no seed */
+    CBA_TRI_TOO_FEW = 4        /* fewer than max(min_cams, 2) cameras saw the point */
+} cba_tri_status;
+typedef struct cba_triangulate_options {
+    int32_t max_iterations; /* LM steps after the seed (default 10) */
+    double step_tolerance;  /* relative step size that ends the iteration (default 1e-12) */
+    int32_t min_cams;       /* cameras a point needs (default 2; values below 2 mean 2) */
+    double max_reproj_px;   /* per-camera error above which the worst camera is dropped (default +inf: off) */
+} cba_triangulate_options;
+void cba_triangulate_options_default(cba_triangulate_options* o);
+cba_status cba_triangulate(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs,
+                           const double* inverse_coeffs /*[n_cams][n_inverse_coeffs] or NULL*/, const double* c_T_r /*[n_cams][7]*/,
+                           int64_t n, const double* uv /*[n_cams][n][2]*/, const cba_triangulate_options* opts, double* xyz /*[n][3]*/,
+                           double* rms_px /*[n] or NULL*/, uint32_t* used_mask /*[n] or NULL*/, int32_t* status /*[n]*/,
+                           double* cov6 /*[n][6] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
