@@ -174,6 +174,24 @@ def oracle_block_normal_eq(orc, flat):
     return np.stack(out)
 
 
+def scaled_normal_eq_diff(rows, ref, p) -> dict:
+    """Block rows [upper(H) | g | |r|^2] against reference rows, every entry on its own scale (taken from the reference):
+    H = max |dH_ij| / sqrt(H_ii H_jj), g = max |dg_i| / (sqrt(H_ii) |r|), s = max |d|r|^2| / |r|^2, and zero = the largest |d| among
+    the entries whose scale is exactly 0 (such an entry has to agree exactly).  The block-max measure divides by the block's
+    largest entry and cannot see an error in the small ones (k3, tangential, tilt columns next to the focal lengths)."""
+    rows, ref = np.asarray(rows, float), np.asarray(ref, float)
+    nh = p * (p + 1) // 2
+    iu = np.triu_indices(p)
+    d = np.sqrt(ref[:, [i * p - i * (i - 1) // 2 for i in range(p)]])  # sqrt(H_ii) per block
+    s = ref[:, -1]
+    scale = np.concatenate([d[:, iu[0]] * d[:, iu[1]], d * np.sqrt(s)[:, None], s[:, None]], axis=1)
+    diff = np.abs(rows - ref)
+    ok = scale > 0
+    rel = np.where(ok, diff / np.where(ok, scale, 1.0), 0.0)
+    return dict(H=float(rel[:, :nh].max()), g=float(rel[:, nh:nh + p].max()), s=float(rel[:, -1].max()),
+                zero=float(diff[~ok].max()) if (~ok).any() else 0.0)
+
+
 def rel_diff(a, b) -> float:
     if a is None or b is None:
         return 0.0

@@ -1033,9 +1033,12 @@ def test_c3_shaped_moment_mode_b_equals_direct_mode_b(gpu_lib, monkeypatch):
 
 @pytest.mark.parametrize("chain", ["intr", "ext"])
 def test_mode_b_tile_boundaries(gpu_lib, oracle, chain):
-    """Mode B / Mode R tile edges (a tile is 64 lanes x 16 passes = 1024 observations; the loads of pass k+1 are prefetched):
-    blocks of 63, 64, 65, 1023, 1024, 1025, 2049 and 3000 points, for the direct form (INTRINSIC chain) and the moment
-    form (EXTRINSIC chain), against the oracle's Jets."""
+    """Mode B / Mode R with blocks split into tiles: blocks of 63, 64, 65, 1023, 1024, 1025, 2049 and 3000 points, for the direct
+    form (INTRINSIC chain) and the moment form (EXTRINSIC chain), against the oracle's Jets.  A tile is at least 2048 observations
+    (structure.hpp choose_mode_b_tile), so only 2049 and 3000 are split, into two tiles each; a workgroup walks its tile in groups of
+    64 * NP observations (NP = its wavefronts: 2 here for the direct form, 4 for the moment form; the loads of group k+1 are
+    prefetched), so the group edges are 128 and 256, not these sizes, which date from a 1024-observation tile.  The group and
+    tile edges of every form: tests/test_mode_b_forms_gpu.py."""
     sizes = [63, 64, 65, 1023, 1024, 1025, 2049, 3000]
     if chain == "intr":
         sc = synth.scene_intrinsics(len(sizes), rows=55, cols=55, spacing=0.012, noise_px=0.3)
