@@ -29,6 +29,10 @@ from .optim import (  # noqa: F401
     PlanarPoseOptions,
 )
 from .linescan import (  # noqa: F401
+    LaserProfiles,
+    LaserScanner,
+    LaserScanOptions,
+    laser_points,
     LinescanCalibrationFacade,
     LineScanPlaneFitOptions,
     LineScanView,

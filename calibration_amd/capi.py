@@ -151,6 +151,19 @@ class CbaTriangulateOptions(C.Structure):
     ]
 
 
+class CbaLaserScanOptions(C.Structure):
+    """``cba_laser_scan_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("axis", C.c_int32),
+        ("roi_begin", C.c_int32),
+        ("roi_end", C.c_int32),
+        ("half_window", C.c_int32),
+        ("floor_level", C.c_double),
+        ("min_peak", C.c_double),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, c_double_p, C.c_int64, C.c_void_p)
 
 
@@ -362,6 +375,16 @@ PROTOTYPES = {
     "cba_triangulate": (
         C.c_int32, [C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int64, c_double_p,
                     C.POINTER(CbaTriangulateOptions), c_double_p, c_double_p, c_uint32_p, c_int32_p, c_double_p]),
+    "cba_laser_scan_options_default": (None, [C.POINTER(CbaLaserScanOptions)]),
+    "cba_laser_points": (
+        C.c_int32, [C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_int64_p, c_double_p,
+                    c_double_p, c_double_p]),
+    "cba_laser_scanner_create": (
+        C.c_int32, [C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32,
+                    C.POINTER(CbaLaserScanOptions), C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_laser_scanner_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "cba_laser_scanner_destroy": (None, [C.c_void_p]),
 }
 
 

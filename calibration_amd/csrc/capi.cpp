@@ -1911,4 +1911,103 @@ __attribute__((visibility("default"))) cba_status cba_triangulate_timed(int32_t 
 }
 #endif
 
+// ---- laser profile scanning (laser_scan.hip, laser_scan_math.hpp) ---------------------------------------------------------------
+void cba_laser_scan_options_default(cba_laser_scan_options* o) {
+    if (!o) return;
+    o->axis = 0;
+    o->roi_begin = 0;
+    o->roi_end = 0;
+    o->half_window = 5;
+    o->floor_level = 0.0;
+    o->min_peak = 1.0;
+}
+
+static void check_laser_plane(const double* plane) {
+    if (!plane) throw std::invalid_argument("null argument");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(plane[k])) throw std::invalid_argument("the plane must be finite");
+    if (plane[0] == 0.0 && plane[1] == 0.0 && plane[2] == 0.0) throw std::invalid_argument("the plane normal must not be zero");
+}
+
+cba_status cba_laser_points(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                            const double plane[4], int64_t n, const double* uv, int32_t n_frames, const int64_t* frame_offset,
+                            const double* frame_pose7, double* xyz, double* plane_xy) {
+    return guarded([&] {
+        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
+        check_laser_plane(plane);
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (n_frames < 0) throw std::invalid_argument("n_frames must be >= 0");
+        if (frame_pose7 && !frame_offset && n_frames != 1) throw std::invalid_argument("frame_pose7 without frame_offset needs n_frames == 1");
+        if (frame_offset) {
+            check_offsets(frame_offset, n_frames, "frame ", OFF_FROM_ZERO);
+            if (frame_offset[n_frames] != n) throw std::invalid_argument("frame offsets must end at n");
+        }
+        if (n == 0) return;
+        if (!uv || !xyz) throw std::invalid_argument("null argument");
+        require_device();
+        const int64_t single[2] = {0, n};  // one posed frame without a table
+        laser_points_gpu(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, plane, n, uv, n_frames,
+                         frame_pose7 ? (frame_offset ? frame_offset : single) : nullptr, frame_pose7, xyz, plane_xy, default_device());
+    });
+}
+
+cba_status cba_laser_scanner_create(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                    const double plane[4], int32_t width, int32_t height, int32_t max_frames,
+                                    const cba_laser_scan_options* opts, int32_t device, cba_laser_scanner** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
+        check_laser_plane(plane);
+        if (!opts) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        if (max_frames < 1) throw std::invalid_argument("max_frames must be >= 1");
+        if (opts->axis != 0 && opts->axis != 1) throw std::invalid_argument("axis must be 0 or 1");
+        const int32_t side = opts->axis == 0 ? height : width;
+        if (!(opts->roi_begin == 0 && opts->roi_end == 0) && (opts->roi_begin < 0 || opts->roi_end > side || opts->roi_begin >= opts->roi_end))
+            throw std::invalid_argument("the ROI must be a non-empty range inside the image");
+        if (opts->half_window < 0) throw std::invalid_argument("half_window must be >= 0");
+        if (!std::isfinite(opts->floor_level) || !std::isfinite(opts->min_peak))
+            throw std::invalid_argument("floor_level and min_peak must be finite");
+        if (static_cast<int64_t>(max_frames) * std::max(width, height) > 0x7fffffff) throw std::invalid_argument("max_frames is too large");
+        require_device(device);
+        *out = reinterpret_cast<cba_laser_scanner*>(laser_scanner_create(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0,
+                                                                          inverse_coeffs, plane, width, height, max_frames, *opts, device));
+    });
+}
+
+static cba_status laser_scanner_process_impl(cba_laser_scanner* h, int32_t n_frames, int32_t dtype, const void* images,
+                                             const double* frame_pose7, double* centre, double* amplitude, double* width_px, double* xyz,
+                                             double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        LaserScanner* sc = reinterpret_cast<LaserScanner*>(h);
+        if (n_frames < 0 || n_frames > laser_scanner_max_frames(sc)) throw std::invalid_argument("n_frames must be in [0, max_frames]");
+        if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
+        if (n_frames == 0) return;
+        if (!images) throw std::invalid_argument("null argument");
+        laser_scanner_process(sc, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
+    });
+}
+
+cba_status cba_laser_scanner_process(cba_laser_scanner* h, int32_t n_frames, int32_t dtype, const void* images, const double* frame_pose7,
+                                     double* centre, double* amplitude, double* width_px, double* xyz) {
+    return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, nullptr);
+}
+
+void cba_laser_scanner_destroy(cba_laser_scanner* h) { laser_scanner_destroy(reinterpret_cast<LaserScanner*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_laser_scan.py): cba_laser_scanner_process timing its stages on the device (stage_ms [3] = upload,
+// kernel, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_laser_scanner_process_timed(cba_laser_scanner* h, int32_t n_frames, int32_t dtype,
+                                                                                  const void* images, const double* frame_pose7,
+                                                                                  double* centre, double* amplitude, double* width_px,
+                                                                                  double* xyz, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
+}
+#endif
+
 }  // extern "C"

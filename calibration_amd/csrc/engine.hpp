@@ -421,6 +421,17 @@ int undistort_map_cams(const UndistortMap* m);
 void triangulate_gpu(int model, int n_cams, const double* intr, int n_inv, const double* inv, const double* c_T_r, int64_t n,
                      const double* uv, const cba_triangulate_options& o, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
                      double* cov6, int32_t* linearisations, double* stage_ms, int device);
+// laser_scan.hip: cba_laser_points and the cba_laser_scanner handle (checked by the caller).  frame_offset [n_frames + 1] and
+// frame_pose7 [n_frames][7]: both or neither; plane_xy optional; stage_ms [3] optional: upload, kernel, download
+void laser_points_gpu(int model, const double* intr, int n_inv, const double* inv, const double* plane, int64_t n, const double* uv,
+                      int n_frames, const int64_t* frame_offset, const double* frame_pose7, double* xyz, double* plane_xy, int device);
+struct LaserScanner;
+LaserScanner* laser_scanner_create(int model, const double* intr, int n_inv, const double* inv, const double* plane, int W, int H,
+                                   int max_frames, const cba_laser_scan_options& o, int device);
+int laser_scanner_max_frames(const LaserScanner* h);
+void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void* images, const double* frame_pose7, double* centre,
+                           double* amplitude, double* width_px, double* xyz, double* stage_ms);
+void laser_scanner_destroy(LaserScanner* h) noexcept;
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

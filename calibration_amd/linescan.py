@@ -8,6 +8,9 @@ A camera is its parameter vector: 10 entries [fx, fy, cx, cy, skew, k1, k2, k3, 
 the inverse model); without it, undistortion is BrownConrady's 5-step fixed point.  A view is a ``LineScanView``: its
 target correspondences [X, Y, u, v] and its laser pixels [u, v].  Planes are [nx, ny, nz, d] with n.p + d = 0 and the
 sign convention of calibba.h (d > 0).
+
+Laser profile scanning, which the reference does not have (``cba_laser_points``, ``cba_laser_scanner``): ``laser_points`` puts
+caller pixels on the calibrated plane, ``LaserScanner`` turns frames into sub-pixel line centres and 3D profiles.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import capi
-from .capi import CbaLaserPlaneResult, CbaPlaneFitOptions, dptr, i64ptr, u8ptr
+from .capi import CbaLaserPlaneResult, CbaLaserScanOptions, CbaPlaneFitOptions, dptr, i64ptr, u8ptr
 
 
 # cba_calibrate_laser_plane's message when fewer than 3 points survive (linescan.h:113-115)
@@ -208,3 +211,138 @@ class LinescanCalibrationFacade:
             return LinescanCalibrationRunResult(True, len(views), res)
         except capi.CbaError:
             return LinescanCalibrationRunResult(False, len(views), None)
+
+
+# ---- laser profile scanning (cba_laser_points, cba_laser_scanner; no counterpart in the reference) ----------------------------------
+@dataclass
+class LaserScanOptions:
+    """``cba_laser_scan_options``: axis 0 = one peak per column (1: per row); the ROI [roi_begin, roi_end) along the search direction
+    (0, 0: the whole side); the half window of the centre of gravity; the floor subtracted from the samples; the least valid peak."""
+    axis: int = 0
+    roi_begin: int = 0
+    roi_end: int = 0
+    half_window: int = 5
+    floor_level: float = 0.0
+    min_peak: float = 1.0
+
+
+@dataclass
+class LaserProfiles:
+    centre: np.ndarray     # [n_frames][n_lines] sub-pixel line position, NaN for an invalid line
+    amplitude: np.ndarray  # [n_frames][n_lines] the line's maximum
+    width_px: np.ndarray   # [n_frames][n_lines] equivalent width sum g / (m - floor)
+    xyz: np.ndarray        # [n_frames][n_lines][3] points on the laser plane (moved by the frame poses when given)
+
+
+def _plane(plane) -> np.ndarray:
+    if isinstance(plane, LineScanCalibrationResult):
+        plane = plane.plane
+    p = np.ascontiguousarray(np.asarray(plane, dtype=np.float64).reshape(-1))
+    if p.size != 4:
+        raise ValueError(f"a plane has 4 entries [nx, ny, nz, d], got {p.size}")
+    return p
+
+
+def _frame_poses(frame_poses, n_frames: int) -> np.ndarray:
+    from .geometry import poses_from_matrices
+
+    p = np.asarray(frame_poses, dtype=np.float64)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = poses_from_matrices(p)
+    if p.ndim != 2 or p.shape != (n_frames, 7):
+        raise ValueError(f"frame_poses must be {n_frames} 4x4 matrices or pose7 rows, got shape {p.shape}")
+    return np.ascontiguousarray(p)
+
+
+def laser_points(uv, camera, plane, frame_offset=None, frame_poses=None, inverse_coeffs=None, want_plane_xy: bool = False):
+    """Pixels uv [n][2] -> points [n][3] on the laser plane (camera frame), by the rule of calibba.h.  plane: [nx, ny, nz, d] or a
+    LineScanCalibrationResult.  frame_offset [n_frames + 1] and frame_poses ([n_frames][7] pose7 rows or 4x4 matrices) move each
+    frame's points by its pose; frame_poses alone is one pose for all pixels.  With want_plane_xy the result is (xyz, plane_xy): the
+    in-plane coordinates the calibration's homography promises."""
+    lib = capi.load_library()
+    model, intr, inv = _camera(camera, inverse_coeffs)
+    pl = _plane(plane)
+    px = np.asarray(uv, dtype=np.float64)
+    if px.ndim != 2 or px.shape[1] != 2:
+        raise ValueError(f"uv must have shape [n][2], got {px.shape}")
+    px = np.ascontiguousarray(px)
+    n = px.shape[0]
+    off, n_frames = None, 0
+    if frame_offset is not None:
+        off = np.ascontiguousarray(np.asarray(frame_offset, dtype=np.int64).reshape(-1))
+        if off.size < 1:
+            raise ValueError("frame_offset needs n_frames + 1 entries")
+        n_frames = off.size - 1
+    poses = None
+    if frame_poses is not None:
+        if off is None:
+            n_frames = 1
+            frame_poses = np.asarray(frame_poses, dtype=np.float64)
+            if frame_poses.shape in ((7,), (4, 4)):
+                frame_poses = frame_poses[None]
+        poses = _frame_poses(frame_poses, n_frames)
+    xyz = np.empty((n, 3))
+    pxy = np.empty((n, 2)) if want_plane_xy else None
+    capi.check(lib, lib.cba_laser_points(model, dptr(intr), 0 if inv is None else int(inv.size), dptr(inv), dptr(pl), n, dptr(px), n_frames,
+                                         i64ptr(off), dptr(poses), dptr(xyz), dptr(pxy)))
+    return (xyz, pxy) if want_plane_xy else xyz
+
+
+class LaserScanner:
+    """``cba_laser_scanner``: frames of one size in, laser profiles out, one kernel launch per ``process``.  The device buffers are
+    sized for max_frames at construction.  Use as a context manager or call ``close()``."""
+
+    def __init__(self, camera, plane, width: int, height: int, max_frames: int = 1, opts: Optional[LaserScanOptions] = None,
+                 inverse_coeffs=None, device: int = 0):
+        self._h = None
+        self._lib = capi.load_library()
+        model, intr, inv = _camera(camera, inverse_coeffs)
+        pl = _plane(plane)
+        o = opts or LaserScanOptions()
+        co = CbaLaserScanOptions(int(o.axis), int(o.roi_begin), int(o.roi_end), int(o.half_window), float(o.floor_level), float(o.min_peak))
+        self.width, self.height, self.max_frames, self.axis = int(width), int(height), int(max_frames), int(o.axis)
+        self.n_lines = self.width if self.axis == 0 else self.height
+        h = C.c_void_p()
+        capi.check(self._lib, self._lib.cba_laser_scanner_create(model, dptr(intr), 0 if inv is None else int(inv.size), dptr(inv), dptr(pl),
+                                                                 self.width, self.height, self.max_frames, C.byref(co), int(device),
+                                                                 C.byref(h)))
+        self._h = h
+
+    def process(self, images, frame_poses=None) -> LaserProfiles:
+        """images: [n_frames][height][width] (or one [height][width] frame), uint8 or float32; C-contiguous arrays of those types are
+        used as they are.  frame_poses: one pose per frame (pose7 rows or 4x4 matrices)."""
+        if self._h is None:
+            raise ValueError("the scanner is closed")
+        img = np.asarray(images)
+        if img.dtype not in (np.uint8, np.float32):
+            raise ValueError(f"images must be uint8 or float32, got {img.dtype}")
+        if img.ndim == 2:
+            img = img[None]
+        if img.ndim != 3 or img.shape[1:] != (self.height, self.width):
+            raise ValueError(f"images must have shape [n_frames][{self.height}][{self.width}], got {img.shape}")
+        img = np.ascontiguousarray(img)
+        n_frames = img.shape[0]
+        poses = None if frame_poses is None else _frame_poses(frame_poses, n_frames)
+        shape = (n_frames, self.n_lines)
+        centre, amplitude, width_px, xyz = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape + (3,))
+        dtype = capi.DTYPE_U8 if img.dtype == np.uint8 else capi.DTYPE_F32
+        capi.check(self._lib, self._lib.cba_laser_scanner_process(self._h, n_frames, dtype, img.ctypes.data_as(C.c_void_p), dptr(poses),
+                                                                  dptr(centre), dptr(amplitude), dptr(width_px), dptr(xyz)))
+        return LaserProfiles(centre, amplitude, width_px, xyz)
+
+    def close(self):
+        if self._h is not None:
+            self._lib.cba_laser_scanner_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -863,6 +863,74 @@ cba_status cba_triangulate(int32_t camera_model, int32_t n_cams, const double* i
                            double* rms_px /*[n] or NULL*/, uint32_t* used_mask /*[n] or NULL*/, int32_t* status /*[n]*/,
                            double* cov6 /*[n][6] or NULL*/);
 
+/* ---- laser profile scanning (no counterpart in the reference) ---------------------------------------------------------------
+ *
+ * What a line-scan rig does at frame rate with the result of cba_calibrate_laser_plane: find the laser line in each frame with
+ * sub-pixel accuracy, turn every line pixel into a ray through the camera and intersect it with the laser plane.  The reference
+ * computes the plane and its homography and never applies them.  Camera (camera_model, intr, inverse_coeffs) as for
+ * cba_camera_unproject; plane [nx ny nz d] with n.p + d = 0 as cba_calibrate_laser_plane returns it (d > 0).  fp64 unless stated.
+ *
+ * Pixel to 3D (cba_laser_points, and every line of the scanner).  For a pixel (u, v): (x, y) = the unprojection of
+ * cba_camera_unproject, r = (x, y, 1), den = n.r, s = -d / den, P = s r.  den == 0, s <= 0 or a non-finite s (a NaN pixel included)
+ * give NaN in all three coordinates.  There is no threshold on den: the plane code divides without one, and s <= 0 rejects every
+ * ray that meets the plane behind the camera.  With a frame pose pose7 = [qw qx qy qz tx ty tz], P <- R P + t: R is the quaternion's
+ * matrix without normalisation, as in cba_triangulate; each row is summed left to right, then + t.  The products and sums of this
+ * paragraph are not contracted into fused multiply-adds.  Optional plane_xy = hnormalized(Hp (x, y, 1)) with
+ * Hp = build_plane_homography(plane): the in-plane coordinates that cba_laser_plane_result.homography promises; NaN where P is.
+ *
+ * cba_laser_points: n caller pixels uv [n][2] -> xyz [n][3] and optionally plane_xy [n][2].  Frames: frame_offset [n_frames + 1],
+ * non-decreasing from 0 to n, says which pixels belong to which frame (empty frames allowed); frame_pose7 [n_frames][7] moves each
+ * frame's points.  Without frame_pose7 there is no pose (frame_offset, if given, is only checked); frame_pose7 without frame_offset
+ * needs n_frames == 1 and applies to every pixel.
+ *
+ * cba_laser_scanner: a handle that owns the camera, the plane, the options, one stream and device buffers sized at create for
+ * max_frames frames of width x height; cba_laser_scanner_process allocates nothing.  Images are single channel, CBA_DTYPE_U8 or
+ * CBA_DTYPE_F32 (chosen per call), I[frame][row][column], rows and frames contiguous.  axis 0: one peak per column, searched along
+ * the rows (n_lines = width, the pixel of line l is (l, centre)); axis 1: one peak per row, searched along the columns (n_lines =
+ * height, the pixel is (centre, l)).  "Position" p is the index along the search direction, inside the ROI [roi_begin, roi_end)
+ * (0, 0: the whole side).  For one line:
+ * 1. m = the maximum of I over the ROI; p0 = the lowest position with I == m; p1 = the end of the contiguous run of positions equal
+ *    to m that starts at p0 (the saturation plateau; normally p1 == p0).  NaN samples (float32) never compare as a maximum, end a
+ *    plateau and count as 0 in the sums.
+ * 2. The line is invalid when m < min_peak (or the ROI holds no sample that is not NaN): centre = NaN, width_px = NaN, xyz = NaN,
+ *    amplitude = m (NaN without a sample).
+ * 3. Window [max(p0 - half_window, roi_begin), min(p1 + half_window, roi_end - 1)]; g(p) = max(I(p) - floor_level, 0);
+ *    centre = sum g p / sum g.  uint8: floor_level is rounded half to even and clamped to [0, 255]; both sums are exact 64-bit
+ *    integers; centre is one fp64 division.  float32: samples are converted to fp64; g p is rounded, then added; both sums run in
+ *    ascending p in fp64; centre is one division.  sum g == 0 makes the line invalid as in step 2.
+ * 4. Outputs per line, fp64: centre, amplitude = m, width_px = sum g / (m - floor_level) (the equivalent width, with the rounded
+ *    floor for uint8), xyz = the pixel's point as above, moved by frame_pose7 [n_frames][7] when given.
+ * A line's result depends on nothing but its own samples: not on the other lines or frames of the call, and not on how the device
+ * splits the search direction.  Outputs are [n_frames][n_lines] (xyz: [n_frames][n_lines][3]); each may be NULL.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL required pointers (intr, plane, options, out, the
+ * handle; for n > 0 uv and xyz; for n_frames > 0 images); an unknown model or dtype; an inverse count outside [2, 16]; n < 0; width
+ * or height outside [1, CBA_IMAGE_MAX_SIDE]; max_frames < 1; an axis other than 0 or 1; an ROI that is empty or outside the image;
+ * half_window < 0; n_frames < 0 or n_frames > max_frames; a plane normal that is zero or non-finite, or a non-finite d; a non-finite
+ * floor_level or min_peak; frame_pose7 given while frame_offset is NULL and n_frames != 1; frame_offset not non-decreasing from 0
+ * to n.  n == 0 and n_frames == 0 are no work; otherwise no device -> CBA_ERR_NO_DEVICE. */
+typedef struct cba_laser_scan_options {
+    int32_t axis;               /* 0: one peak per column; 1: one peak per row (default 0) */
+    int32_t roi_begin, roi_end; /* positions [roi_begin, roi_end) along the search direction; 0, 0 = the whole side (default) */
+    int32_t half_window;        /* samples on each side of the peak (plateau) that enter the centre of gravity (default 5) */
+    double floor_level;         /* subtracted from every sample of the window (default 0) */
+    double min_peak;            /* a line whose maximum is below this is invalid (default 1) */
+} cba_laser_scan_options;
+void cba_laser_scan_options_default(cba_laser_scan_options* o);
+cba_status cba_laser_points(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                            const double plane[4], int64_t n, const double* uv /*[n][2]*/, int32_t n_frames,
+                            const int64_t* frame_offset /*[n_frames + 1] or NULL*/, const double* frame_pose7 /*[n_frames][7] or NULL*/,
+                            double* xyz /*[n][3]*/, double* plane_xy /*[n][2] or NULL*/);
+typedef struct cba_laser_scanner cba_laser_scanner; /* opaque: camera, plane, options, device buffers sized at create, one stream */
+cba_status cba_laser_scanner_create(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                                    const double plane[4], int32_t width, int32_t height, int32_t max_frames,
+                                    const cba_laser_scan_options* opts, int32_t device, cba_laser_scanner** out);
+cba_status cba_laser_scanner_process(cba_laser_scanner* h, int32_t n_frames, int32_t dtype, const void* images,
+                                     const double* frame_pose7 /*[n_frames][7] or NULL*/, double* centre /*[n_frames][n_lines] or NULL*/,
+                                     double* amplitude /*or NULL*/, double* width_px /*or NULL*/,
+                                     double* xyz /*[n_frames][n_lines][3] or NULL*/);
+void cba_laser_scanner_destroy(cba_laser_scanner* h);
+
 #ifdef __cplusplus
 }
 #endif
