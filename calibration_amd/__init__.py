@@ -93,6 +93,16 @@ from .camera import (  # noqa: F401
     undistort,
     unproject,
 )
+from .stereo import (  # noqa: F401
+    StereoGeometry,
+    StereoMatcher,
+    StereoMatchOptions,
+    StereoRectification,
+    StereoResult,
+    rectify,
+    rectify_maps,
+    stereo_points,
+)
 from .triangulate import (  # noqa: F401
     TriangulateOptions,
     TriangulationResult,

@@ -164,6 +164,31 @@ class CbaLaserScanOptions(C.Structure):
     ]
 
 
+class CbaStereoRectifyOptions(C.Structure):
+    """``cba_stereo_rectify_options`` (calibba.h)."""
+
+    _fields_ = [("focal", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class CbaStereoMatchOptions(C.Structure):
+    """``cba_stereo_match_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("min_disparity", C.c_int32),
+        ("num_disparities", C.c_int32),
+        ("half_window", C.c_int32),
+        ("uniqueness_percent", C.c_int32),
+        ("lr_max_diff", C.c_int32),
+        ("subpixel", C.c_int32),
+    ]
+
+
+class CbaStereoGeometry(C.Structure):
+    """``cba_stereo_geometry`` (calibba.h)."""
+
+    _fields_ = [("focal", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, c_double_p, C.c_int64, C.c_void_p)
 
 
@@ -385,6 +410,17 @@ PROTOTYPES = {
     "cba_laser_scanner_process": (
         C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "cba_laser_scanner_destroy": (None, [C.c_void_p]),
+    "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
+    "cba_stereo_rectify": (
+        C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(CbaStereoRectifyOptions), c_double_p, c_double_p,
+                    c_double_p, c_double_p]),
+    "cba_stereo_matcher_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaStereoMatchOptions), C.POINTER(CbaStereoGeometry), c_double_p, C.c_int32,
+                    C.POINTER(C.c_void_p)]),
+    "cba_stereo_matcher_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, C.POINTER(C.c_float)]),
+    "cba_stereo_matcher_destroy": (None, [C.c_void_p]),
+    "cba_stereo_points": (C.c_int32, [C.POINTER(CbaStereoGeometry), c_double_p, C.c_int64, c_double_p, c_double_p]),
 }
 
 

@@ -23,6 +23,7 @@
 #include "structure.hpp"
 #include "linescan_math.hpp"
 #include "hom_ransac_math.hpp"
+#include "stereo_math.hpp"
 
 using namespace cba;
 
@@ -2007,6 +2008,106 @@ __attribute__((visibility("default"))) cba_status cba_laser_scanner_process_time
                                                                                   double* xyz, double* stage_ms) {
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
+}
+#endif
+
+// ---- stereo depth (stereo_match.hip, stereo_math.hpp) ---------------------------------------------------------------------------
+void cba_stereo_match_options_default(cba_stereo_match_options* o) {
+    if (!o) return;
+    o->min_disparity = 0;
+    o->num_disparities = 64;
+    o->half_window = 4;
+    o->uniqueness_percent = 10;
+    o->lr_max_diff = 1;
+    o->subpixel = 1;
+}
+
+cba_status cba_stereo_rectify(int32_t camera_model, const double* intr, const double* c_T_r, int32_t width, int32_t height,
+                              const cba_stereo_rectify_options* opts, double* R, double* new_k5, double* baseline, double* r_T_rect) {
+    return guarded([&] {
+        check_camera(camera_model, intr, 0, nullptr);
+        if (!c_T_r || !opts || !R || !new_k5 || !baseline || !r_T_rect) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        const char* err = stereo_rectify(intr, camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10, c_T_r, width, height, opts->focal, opts->cx,
+                                         opts->cy, R, new_k5, baseline, r_T_rect);
+        if (err) throw std::invalid_argument(err);
+    });
+}
+
+static void check_stereo_geometry(const cba_stereo_geometry* g, const double* pose7) {
+    if (!std::isfinite(g->focal) || !std::isfinite(g->cx) || !std::isfinite(g->cy) || !std::isfinite(g->baseline))
+        throw std::invalid_argument("the stereo geometry must be finite");
+    if (!(g->focal > 0.0) || !(g->baseline > 0.0)) throw std::invalid_argument("focal and baseline must be > 0");
+    if (pose7)
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(pose7[k])) throw std::invalid_argument("the pose must be finite");
+}
+
+cba_status cba_stereo_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_stereo_match_options* opts,
+                                     const cba_stereo_geometry* geometry, const double* pose7, int32_t device, cba_stereo_matcher** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!opts) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        if (max_pairs < 1) throw std::invalid_argument("max_pairs must be >= 1");
+        if (static_cast<int64_t>(max_pairs) * width * height > 0x7fffffff) throw std::invalid_argument("max_pairs is too large");
+        if (opts->min_disparity < -32768 || opts->min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
+        if (opts->num_disparities < 1 || opts->num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
+        if (opts->half_window < 1 || opts->half_window > 10) throw std::invalid_argument("half_window must be in 1..10");
+        if (opts->uniqueness_percent < 0 || opts->uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
+        if (opts->lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
+        if (opts->subpixel != 0 && opts->subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
+        if (pose7 && !geometry) throw std::invalid_argument("a pose needs a geometry");
+        if (geometry) check_stereo_geometry(geometry, pose7);
+        require_device(device);
+        *out = reinterpret_cast<cba_stereo_matcher*>(stereo_matcher_create(width, height, max_pairs, *opts, geometry, pose7, device));
+    });
+}
+
+static cba_status stereo_matcher_process_impl(cba_stereo_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right,
+                                              float* disparity, int32_t* cost, float* xyz, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        StereoMatcher* m = reinterpret_cast<StereoMatcher*>(h);
+        if (n_pairs < 0 || n_pairs > stereo_matcher_max_pairs(m)) throw std::invalid_argument("n_pairs must be in [0, max_pairs]");
+        if (xyz && !stereo_matcher_has_geometry(m)) throw std::invalid_argument("xyz needs a matcher created with a geometry");
+        if (n_pairs == 0) return;
+        if (!left || !right) throw std::invalid_argument("null argument");
+        stereo_matcher_process(m, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+    });
+}
+
+cba_status cba_stereo_matcher_process(cba_stereo_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right, float* disparity,
+                                      int32_t* cost, float* xyz) {
+    return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, nullptr);
+}
+
+void cba_stereo_matcher_destroy(cba_stereo_matcher* h) { stereo_matcher_destroy(reinterpret_cast<StereoMatcher*>(h)); }
+
+cba_status cba_stereo_points(const cba_stereo_geometry* geometry, const double* pose7, int64_t n, const double* uvd, double* xyz) {
+    return guarded([&] {
+        if (!geometry) throw std::invalid_argument("null argument");
+        check_stereo_geometry(geometry, pose7);
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (n == 0) return;
+        if (!uvd || !xyz) throw std::invalid_argument("null argument");
+        require_device();
+        stereo_points_gpu(*geometry, pose7, n, uvd, xyz, default_device());
+    });
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_stereo.py): cba_stereo_matcher_process timing its stages on the device (stage_ms [3] = upload,
+// kernels, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_stereo_matcher_process_timed(cba_stereo_matcher* h, int32_t n_pairs,
+                                                                                   const uint8_t* left, const uint8_t* right,
+                                                                                   float* disparity, int32_t* cost, float* xyz,
+                                                                                   double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
 }
 #endif
 

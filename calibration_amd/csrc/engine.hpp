@@ -432,6 +432,17 @@ int laser_scanner_max_frames(const LaserScanner* h);
 void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void* images, const double* frame_pose7, double* centre,
                            double* amplitude, double* width_px, double* xyz, double* stage_ms);
 void laser_scanner_destroy(LaserScanner* h) noexcept;
+// stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
+// disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download
+void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device);
+struct StereoMatcher;
+StereoMatcher* stereo_matcher_create(int W, int H, int max_pairs, const cba_stereo_match_options& o, const cba_stereo_geometry* geom,
+                                     const double* pose7, int device);
+int stereo_matcher_max_pairs(const StereoMatcher* h);
+bool stereo_matcher_has_geometry(const StereoMatcher* h);
+void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost,
+                            float* xyz, double* stage_ms);
+void stereo_matcher_destroy(StereoMatcher* h) noexcept;
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

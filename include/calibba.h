@@ -931,6 +931,98 @@ cba_status cba_laser_scanner_process(cba_laser_scanner* h, int32_t n_frames, int
                                      double* xyz /*[n_frames][n_lines][3] or NULL*/);
 void cba_laser_scanner_destroy(cba_laser_scanner* h);
 
+/* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
+ *
+ * What a calibrated two-camera rig is used for: calibrated pair -> rectified pair -> dense disparity -> 3D points.
+ *
+ * cba_stereo_rectify (host, fp64, closed form; needs no device).  Inputs: camera_model, intr [2][10 | 12], c_T_r [2][7] (the pose7
+ * rows cba_estimate_extrinsic_dlt and cba_optimize_extrinsics return, reference frame -> camera), the output size width x height and
+ * options {focal, cx, cy}, each 0 or NaN for its default.  Rule: each quaternion is normalised (unlike cba_triangulate: the rotations
+ * must be orthonormal here); R_i is its matrix, o_i = -R_i^T t_i the camera centre, B = |o_1 - o_0| the baseline;
+ *   e1 = (o_1 - o_0) / B,   zbar = R_0^T e_z + R_1^T e_z (the sum of the optical axes in the reference frame),
+ *   e2 = (zbar x e1) / |zbar x e1|,   e3 = e1 x e2,   rect_R_r = the matrix with rows e1, e2, e3.
+ * Outputs: R [2][9] = rect_R_r R_i^T (row-major), exactly what cba_undistort_map_create takes (its P = R^T (x, y, 1) maps a rectified
+ * ray to a camera ray); new_k5 [2][5], two identical rows [f', f', cx', cy', 0] with f' = (fx_0 + fy_0 + fx_1 + fy_1) / 4,
+ * cx' = (width - 1) / 2, cy' = (height - 1) / 2 by default; baseline = B; r_T_rect [7], the pose7 that maps the rectified frame of
+ * camera 0 to the reference frame: rotation rect_R_r^T as a unit quaternion with w >= 0, translation o_0.
+ * Camera 1 lies at +x of camera 0 by construction, so camera 0 is the LEFT image and a point in front of both cameras has disparity
+ * u_0 - u_1 = f' B / Z > 0 (Z in the rectified frame).  If the cameras are mounted the other way round the rectified images come out
+ * rotated by 180 degrees (the rule still holds; swap the two cameras to get upright images).  Mixed camera models and an output
+ * orientation for vertical baselines are out of scope.
+ * Errors (CBA_ERR_INVALID_ARGUMENT): NULL pointers; an unknown model; fx or fy equal to 0; width or height outside
+ * [1, CBA_IMAGE_MAX_SIDE]; a zero or non-finite quaternion; B <= 1e-12 (|o_0| + |o_1| + 1); |zbar x e1| <= 1e-6 (the optical axes lie
+ * along the baseline); a focal that is negative or infinite.
+ *
+ * cba_stereo_matcher: a handle that owns the options, an optional geometry, one stream and device buffers sized at create for
+ * max_pairs pairs of width x height; cba_stereo_matcher_process allocates nothing.  Images are RECTIFIED, single channel uint8,
+ * left and right [n_pairs][height][width], rows and pairs contiguous; float32 and multi-channel input are out of scope.  Options:
+ *   min_disparity       any int32 with |.| <= 32768       lowest disparity searched
+ *   num_disparities     1..256                            D
+ *   half_window         1..10                             r: the window is (2r + 1) x (2r + 1)
+ *   uniqueness_percent  0..100                            0 = off
+ *   lr_max_diff         >= -1                             -1 = off
+ *   subpixel            0 / 1                             the parabola step
+ * Rule for one left pixel (x, y), W = width, H = height; every cost is an exact integer:
+ * 1. Candidate d in [min_disparity, min_disparity + D) is admissible when r <= y <= H-1-r, r <= x <= W-1-r, x - r - d >= 0 and
+ *    x + r - d <= W-1.  Then C(x, y, d) = sum over |i|, |j| <= r of |L(x+i, y+j) - R(x+i-d, y+j)| (at most 255 * 441).
+ * 2. No admissible candidate: the disparity is NaN (cost -1).  Otherwise d* is the admissible candidate of lowest cost, the lowest d
+ *    among equals.
+ * 3. Uniqueness (u = uniqueness_percent > 0): the pixel is NaN when some admissible d with |d - d*| > 1 has
+ *    100 C(d) <= (100 + u) C(d*).
+ * 4. Left-right check (lr_max_diff >= 0): for a right pixel x', d_R(x', y) is the lowest-cost d (the lowest d among equals) over the
+ *    d for which (x'+d, y, d) is admissible, its cost being C(x'+d, y, d).  The left pixel is NaN when d_R(x - d*, y) does not exist
+ *    or differs from d* by more than lr_max_diff.
+ * 5. Sub-pixel step (subpixel != 0): when d*-1 and d*+1 are both admissible and den = C(d*-1) - 2 C(d*) + C(d*+1) > 0,
+ *    disparity = d* + (C(d*-1) - C(d*+1)) / (2 den): integer numerator and denominator, one fp64 division, one addition; otherwise
+ *    d*.  The result is rounded once to float32.
+ * Outputs of process, each may be NULL: disparity float32 [n][H][W]; cost int32 [n][H][W] = C(d*), or -1 where step 2 gives NaN
+ * (steps 3 and 4 leave it); xyz float32 [n][H][W][3], only when a geometry was given at create (otherwise passing it is an error):
+ * the point of cba_stereo_points for (x, y, float64(disparity)), rounded once to float32.  A pixel's result depends only on its own
+ * pair: not on the other pairs of the call, and not on how the device tiles the image.
+ *
+ * cba_stereo_points: n caller triples uvd [n][3] (u, v, disparity; fp64) -> xyz [n][3] (fp64) by the geometry {f', cx', cy',
+ * baseline} that cba_stereo_rectify returns: s = B / d, X = (u - cx') s, Y = (v - cy') s, Z = f' s.  d <= 0 or a non-finite input
+ * gives NaN in all three coordinates.  With pose7 (r_T_rect, say), P <- R P + t as in cba_laser_points: the quaternion's matrix
+ * without normalisation, each row summed left to right, then + t.  Nothing is contracted into fused multiply-adds.
+ *
+ * Errors of the matcher and of cba_stereo_points (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL required
+ * pointers (options, out, the handle, the geometry of cba_stereo_points; for n_pairs > 0 left and right; for n > 0 uvd and xyz);
+ * width or height outside [1, CBA_IMAGE_MAX_SIDE]; max_pairs < 1 or max_pairs width height > 2^31 - 1; an option outside its range;
+ * a geometry or pose with a non-finite entry, focal <= 0 or baseline <= 0; a pose at create without a geometry; n_pairs < 0 or
+ * n_pairs > max_pairs; xyz on a handle without geometry; n < 0.  n == 0 and n_pairs == 0 are no work; otherwise no device ->
+ * CBA_ERR_NO_DEVICE. */
+typedef struct cba_stereo_rectify_options {
+    double focal; /* f' (0 or NaN: the mean of the four focal lengths) */
+    double cx;    /* cx' (0 or NaN: (width - 1) / 2) */
+    double cy;    /* cy' (0 or NaN: (height - 1) / 2) */
+} cba_stereo_rectify_options;
+typedef struct cba_stereo_match_options {
+    int32_t min_disparity;      /* lowest disparity searched (default 0) */
+    int32_t num_disparities;    /* D, 1..256 (default 64) */
+    int32_t half_window;        /* r, 1..10 (default 4) */
+    int32_t uniqueness_percent; /* 0..100, 0 = off (default 10) */
+    int32_t lr_max_diff;        /* >= -1, -1 = off (default 1) */
+    int32_t subpixel;           /* 0 / 1 (default 1) */
+} cba_stereo_match_options;
+typedef struct cba_stereo_geometry {
+    double focal, cx, cy; /* f', cx', cy' of the rectified pair */
+    double baseline;      /* B */
+} cba_stereo_geometry;
+void cba_stereo_match_options_default(cba_stereo_match_options* o);
+cba_status cba_stereo_rectify(int32_t camera_model, const double* intr /*[2][10 | 12]*/, const double* c_T_r /*[2][7]*/, int32_t width,
+                              int32_t height, const cba_stereo_rectify_options* opts, double* R /*[2][9]*/, double* new_k5 /*[2][5]*/,
+                              double* baseline, double* r_T_rect /*[7]*/);
+typedef struct cba_stereo_matcher cba_stereo_matcher; /* opaque: options, geometry, device buffers sized at create, one stream */
+cba_status cba_stereo_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_stereo_match_options* opts,
+                                     const cba_stereo_geometry* geometry /*or NULL*/, const double* pose7 /*[7] or NULL*/,
+                                     int32_t device, cba_stereo_matcher** out);
+cba_status cba_stereo_matcher_process(cba_stereo_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right,
+                                      float* disparity /*[n][H][W] or NULL*/, int32_t* cost /*[n][H][W] or NULL*/,
+                                      float* xyz /*[n][H][W][3] or NULL*/);
+void cba_stereo_matcher_destroy(cba_stereo_matcher* h);
+cba_status cba_stereo_points(const cba_stereo_geometry* geometry, const double* pose7 /*[7] or NULL*/, int64_t n,
+                             const double* uvd /*[n][3]*/, double* xyz /*[n][3]*/);
+
 #ifdef __cplusplus
 }
 #endif
