@@ -560,10 +560,12 @@ cba_status cba_reproj_get_params(cba_reproj* h, double* intr, double* cam_pose, 
 
 int64_t cba_reproj_num_observations(const cba_reproj* h) { return h ? reinterpret_cast<const Engine*>(h)->n_obs : 0; }
 
-static void ensure_eval_buffers(Engine& e) {
+// The buffers alone.  Whatever gives one of them new memory clears its fill state (engine.hpp EvalFill): a block from the cache
+// or the runtime holds anything at all where k_eval expects the constant rows.
+static void alloc_eval_buffers(Engine& e) {
     if (e.scalar) {
         const size_t jn = static_cast<size_t>(e.n_tilesA) * (2 + 2 * e.PL) * TILE_A;
-        if (e.Jf.n < jn) alloc_output(e.Jf, jn);
+        if (e.Jf.n < jn) { e.Jf_fill.valid = false; alloc_output(e.Jf, jn); }
         return;
     }
     if (!e.eval_blocked && e.r.n < static_cast<size_t>(2 * e.ld)) e.r.alloc(static_cast<size_t>(2 * e.ld));
@@ -577,8 +579,10 @@ static void ensure_eval_buffers(Engine& e) {
         const size_t nseg = static_cast<size_t>((e.n_tilesA + per - 1) / per);
         if (e.seg_tiles != per || e.Jseg.size() != nseg) {
             e.J.release();
+            e.J_fill.valid = false;
             e.Jseg.clear();
             e.Jseg.resize(nseg);
+            e.Jseg_fill.assign(nseg, EvalFill());
             for (size_t k = 0; k < nseg; ++k) {
                 const int64_t nt = std::min<int64_t>(per, e.n_tilesA - static_cast<int64_t>(k) * per);
                 alloc_output(e.Jseg[k], static_cast<size_t>(nt) * tw);
@@ -587,8 +591,15 @@ static void ensure_eval_buffers(Engine& e) {
         }
         return;
     }
-    if (!e.Jseg.empty()) { e.Jseg.clear(); e.seg_tiles = 0; }
-    if (e.J.n < jn) alloc_output(e.J, jn);
+    if (!e.Jseg.empty()) { e.Jseg.clear(); e.Jseg_fill.clear(); e.seg_tiles = 0; }
+    if (e.J.n < jn) { e.J_fill.valid = false; alloc_output(e.J, jn); }
+}
+
+// ... and their constant Jacobian rows, queued on the engine's stream ahead of the k_eval that relies on them: nothing is
+// launched when the buffers, the layout and the width are those of the last call
+static void ensure_eval_buffers(Engine& e) {
+    alloc_eval_buffers(e);
+    launch_eval_fill(e);
 }
 
 cba_status cba_reproj_eval(cba_reproj* h) {
@@ -662,11 +673,11 @@ static void fetch_blocked_range(Engine& e, int b0, int b1, double* r, double* J)
             const int64_t cnt = std::min<int64_t>(TILE_A, n - s0);
             for (int64_t j = 0; j < cnt; ++j) {
                 const int64_t i = e.blk_offset[b] + s0 + j - base;
-                if (r) { r[2 * i] = buf[j]; r[2 * i + 1] = buf[TILE_A + j]; }
+                if (r) { r[2 * i] = buf[eval_row_slot(P, 0) * TILE_A + j]; r[2 * i + 1] = buf[eval_row_slot(P, 1) * TILE_A + j]; }
                 if (J)
                     for (int k = 0; k < P; ++k) {
-                        J[(2 * i) * P + k] = buf[(2 + k) * TILE_A + j];
-                        J[(2 * i + 1) * P + k] = buf[(2 + P + k) * TILE_A + j];
+                        J[(2 * i) * P + k] = buf[eval_row_slot(P, 2 + k) * TILE_A + j];
+                        J[(2 * i + 1) * P + k] = buf[eval_row_slot(P, 2 + P + k) * TILE_A + j];
                     }
             }
         }
@@ -750,11 +761,11 @@ cba_status cba_reproj_eval_fetch_f32(cba_reproj* h, float* r, float* J) {
                 const int64_t cnt = std::min<int64_t>(TILE_A, n - s0);
                 for (int64_t j = 0; j < cnt; ++j) {
                     const int64_t i = e.blk_offset[b] + s0 + j;
-                    if (r) { r[2 * i] = buf[j]; r[2 * i + 1] = buf[TILE_A + j]; }
+                    if (r) { r[2 * i] = buf[eval_row_slot(P, 0) * TILE_A + j]; r[2 * i + 1] = buf[eval_row_slot(P, 1) * TILE_A + j]; }
                     if (J)
                         for (int k = 0; k < P; ++k) {
-                            J[(2 * i) * P + k] = buf[(2 + k) * TILE_A + j];
-                            J[(2 * i + 1) * P + k] = buf[(2 + P + k) * TILE_A + j];
+                            J[(2 * i) * P + k] = buf[eval_row_slot(P, 2 + k) * TILE_A + j];
+                            J[(2 * i + 1) * P + k] = buf[eval_row_slot(P, 2 + P + k) * TILE_A + j];
                         }
                 }
             }

@@ -11,7 +11,9 @@
 //   J (Mode A output) [n_tilesA][2 + 2P][128]  tile-blocked: for every 128-observation tile one contiguous
 //                                    (2+2P) KiB region = u/v residual rows, then the P Jacobian columns of
 //                                    the u row, then of the v row (streams like a fill; +6 % over whole-array
-//                                    columns r[2][ld], J[2P][ld], which CBA_EVAL_BLOCKED=0 still selects)
+//                                    columns r[2][ld], J[2P][ld], which CBA_EVAL_BLOCKED=0 still selects).
+//                                    Seven of the 2P Jacobian rows are structural constants, written once per
+//                                    buffer and not by k_eval (EvalFill below)
 //   bc                [n_blocks][36] per-block chain constants (reproj_math.hpp BC_*)
 //   sd                [n_cams][36]  Scheimpflug per-camera constants (SD_*)
 //   intr/cam/view/target            parameter blocks, current [0] and trial [1] copies
@@ -214,6 +216,24 @@ constexpr int OPL_B = 32;    // Mode B/R: observations per lane of the SHORTEST 
                              // tile's partial row are paid once per tile; large problems use longer tiles, capi.cpp)
 constexpr int TILE_B = 64 * OPL_B;
 
+// Row slot inside a tile of the blocked Mode A output: logical row (0, 1 residuals; 2 + k the u Jacobian row of local column k;
+// 2 + PL + k the v row) -> which of the tile's 2 + 2 PL runs of 128 holds it.  The kernel, the fill of the constant rows and
+// both fetches go through this one function; the layout is private to them.  Identity: the rows k_eval skips (reproj_math.hpp
+// jac_const) stay where they were, as seven 1 KiB gaps in the tile's run.
+constexpr int eval_row_slot(int PL, int row) { (void)PL; return row; }
+
+// What a Mode A output buffer's constant rows (reproj_math.hpp jac_const) were last filled for.  k_eval does not store those rows,
+// so it may run on a buffer only while `valid` and the layout, width and chain / model it is about to use match; anything that
+// gives the buffer new memory, or lets another writer at it, clears `valid` (capi.cpp ensure_eval_buffers, the ablation launches).
+// Held per handle and per buffer, never per device address: the block cache hands a released block, old contents and all, to
+// whichever handle asks next.
+struct EvalFill {
+    bool valid = false;
+    int blocked = -1, PL = 0, chain = -1, model = -1;
+    bool matches(int b, int pl, int c, int m) const { return valid && blocked == b && PL == pl && chain == c && model == m; }
+    void set(int b, int pl, int c, int m) { valid = true; blocked = b; PL = pl; chain = c; model = m; }
+};
+
 struct Engine {
     // ---- problem -----------------------------------------------------------------------------
     int chain = 0, model = 0;
@@ -245,6 +265,8 @@ struct Engine {
     // obtain; one contiguous block of 59 GB costs 1.7 s, a plain one runs 5-8 % slower).  k_eval is launched once per segment with
     // the segment's tile range and base address: the kernel is unchanged.  Empty when the output is one block (J).
     std::deque<DevBuf<double>> Jseg;
+    EvalFill J_fill, Jf_fill;          // constant rows of J / Jf
+    std::deque<EvalFill> Jseg_fill;    // ... of every segment (same length as Jseg)
     int64_t seg_tiles = 0;  // tiles per segment (the last one may hold fewer)
     double* eval_tile_ptr(int64_t w, int64_t tile_doubles) {  // device address of tile w's output
         return Jseg.empty() ? J.p + w * tile_doubles : Jseg[static_cast<size_t>(w / seg_tiles)].p + (w % seg_tiles) * tile_doubles;
@@ -315,7 +337,8 @@ struct Engine {
 void ensure_f32_buffers(Engine& e);                      // fp32 copies of the observations + float tables
 void launch_block_consts(Engine& e, int which);         // params[which] -> bc, sd
 void launch_camera_consts(Engine& e, int which);        // ... the per-camera part alone (sd)
-void launch_eval(Engine& e);                            // Mode A: r, J at bc/sd
+void launch_eval_fill(Engine& e);                       // Mode A: the constant Jacobian rows of the output buffers that lack them
+void launch_eval(Engine& e);                            // Mode A: r, J at bc/sd (the live rows; needs launch_eval_fill before it)
 void launch_resid(Engine& e);                           // Mode R: blk_s[b] = |r_b|^2
 void warm_reproj_kernels();                              // forces the code object of kernels_reproj.hip to load
 void launch_normal_eq(Engine& e);                       // Mode B: blk_acc[b] = [H | g | s]

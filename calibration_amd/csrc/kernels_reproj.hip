@@ -14,6 +14,8 @@
 // the outputs are unit-stride 16-byte-per-lane (Mode A) or 8-byte-per-lane vector accesses.
 // The arithmetic is reproj_math.hpp (shared with the CPU test build).
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 #include "engine.hpp"
 #include "mode_b.hpp"
@@ -78,6 +80,10 @@ __global__ void k_to_f32(int64_t n, const double* __restrict__ in, float* __rest
 // ---- Mode A -----------------------------------------------------------------------------------
 // Algorithmic HBM traffic per observation: 4 loads + 2 residual stores + 2*P Jacobian stores of
 // 8 bytes = 304 B (P=16) ... 432 B (P=24).  HBM-bound: ~0.3 kFLOP per observation.
+// MOVED per observation and pass: less.  X, Y are deduplicated and cache-resident (16 B read, not 32), and the seven Jacobian
+// rows that are structural constants (reproj_math.hpp jac_const) are written once per buffer by k_eval_fill, not by k_eval:
+// 2 + 2*P - 7 stored rows, 216 B (P=16) ... 344 B (P=24), ~232 B moved at P=16.  The figure bench.py's roofline.frac divides by
+// stays the algorithmic one; roofline.traffic (profiles/pmc_k_eval.json) is the measured one.
 template <typename T> struct Pair;
 template <> struct Pair<double> { typedef double vec __attribute__((ext_vector_type(2))); using ld = double2; };
 template <> struct Pair<float> { typedef float vec __attribute__((ext_vector_type(2))); using ld = float2; };
@@ -90,11 +96,46 @@ __device__ __forceinline__ void store2(T* p, T a, T b) {
     else *reinterpret_cast<typename Pair<T>::vec*>(p) = v;
 }
 
+// f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>): a loop whose index is a constant expression
+template <class F, int... K>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, K...>) { (f(std::integral_constant<int, K>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
+
+// The constant Jacobian rows of a Mode A output buffer (reproj_math.hpp jac_const), whole rows: all 128 slots of every tile
+// (BLK, n = tiles, one wavefront per tile) or the whole column (n = ld, one lane per pair).  k_eval leaves them alone.
+template <typename T, bool BLK>
+__global__ __launch_bounds__(256) void k_eval_fill(int chain, int model, int PL, int64_t n, T* __restrict__ J) {
+    T* o;
+    int64_t stride;  // between rows
+    if (BLK) {
+        const int64_t w = wave_index();
+        if (w >= n) return;
+        o = J + w * (static_cast<int64_t>(2 + 2 * PL) * TILE_A) + 2 * (threadIdx.x & 63);
+        stride = TILE_A;
+    } else {
+        const int64_t i = 2 * (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x);
+        if (i >= n) return;  // ld is even
+        o = J + i;
+        stride = n;
+    }
+    for (int row = 0; row < 2 * PL; ++row) {
+        const int c = jac_const(chain, model, row / PL, row % PL);
+        if (c == JAC_LIVE) continue;
+        const T val = c == JAC_ONE ? T(1) : T(0);
+        store2<false, T>(o + (BLK ? eval_row_slot(PL, 2 + row) : row) * stride, val, val);
+    }
+}
+
 // NT: non-temporal (streaming) stores for r / J, which this kernel never re-reads.
 // ROWS: consecutive tiles handled by one wavefront.
 // BLK: tile-blocked output layout out[tile][2 + 2P][128] (one contiguous 34 KiB region per tile) instead
 // of whole-array columns r[2][ld], J[2P][ld].
 // ABL (timing-only ablations, wrong outputs): 1 = skip the arithmetic (store the loaded values), 2 = skip the loads
+//
+// The Jacobian rows that jac_const() marks constant are NOT stored: k_eval_fill wrote them when the buffer was obtained
+// (launch_eval_fill) and nothing else writes the buffer.  The ablations store every row, constants included, and their launcher
+// marks the buffer's fill invalid.
 //
 // Software pipeline: a wavefront walks ROWS consecutive tiles and issues the 4 observation loads of tile
 // k+1 BEFORE it computes and stores tile k, so the ~2 us load latency under a write-saturated memory
@@ -156,21 +197,25 @@ __global__ __launch_bounds__(256) void k_eval(const Tile* __restrict__ tiles, in
             }
             if (BLK) {
                 T* o = J + w * static_cast<int64_t>((2 + 2 * PL) * TILE_A) + 2 * lane;
-                store2<NT, T>(o, r0[0], r1[0]);
-                store2<NT, T>(o + TILE_A, r0[1], r1[1]);
-#pragma unroll
-                for (int k = 0; k < PL; ++k) {
-                    store2<NT, T>(o + (2 + k) * TILE_A, Ju0[k], Ju1[k]);
-                    store2<NT, T>(o + (2 + PL + k) * TILE_A, Jv0[k], Jv1[k]);
-                }
+                store2<NT, T>(o + eval_row_slot(PL, 0) * TILE_A, r0[0], r1[0]);
+                store2<NT, T>(o + eval_row_slot(PL, 1) * TILE_A, r0[1], r1[1]);
+                static_for<PL>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 0, k) == JAC_LIVE)
+                        store2<NT, T>(o + eval_row_slot(PL, 2 + k) * TILE_A, Ju0[k], Ju1[k]);
+                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 1, k) == JAC_LIVE)
+                        store2<NT, T>(o + eval_row_slot(PL, 2 + PL + k) * TILE_A, Jv0[k], Jv1[k]);
+                });
             } else {
                 store2<NT, T>(r + i0, r0[0], r1[0]);
                 store2<NT, T>(r + ld + i0, r0[1], r1[1]);
-#pragma unroll
-                for (int k = 0; k < PL; ++k) {
-                    store2<NT, T>(J + static_cast<int64_t>(k) * ld + i0, Ju0[k], Ju1[k]);
-                    store2<NT, T>(J + static_cast<int64_t>(PL + k) * ld + i0, Jv0[k], Jv1[k]);
-                }
+                static_for<PL>([&](auto kc) {
+                    constexpr int k = decltype(kc)::value;
+                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 0, k) == JAC_LIVE)
+                        store2<NT, T>(J + static_cast<int64_t>(k) * ld + i0, Ju0[k], Ju1[k]);
+                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 1, k) == JAC_LIVE)
+                        store2<NT, T>(J + static_cast<int64_t>(PL + k) * ld + i0, Jv0[k], Jv1[k]);
+                });
             }
         }
         t = tn; Xv = Xn; Yv = Yn; uv = un; vv = vn;
@@ -475,6 +520,46 @@ void launch_camera_consts(Engine& e, int which) {
 // bc/sd were built from parameter copy e.active; the kernels read the matching intrinsics
 static const double* intr_of(Engine& e) { return e.intr[e.active].p; }
 
+// The constant rows of the buffers the next launch_eval() writes, where they are missing or were made for another layout, width
+// or chain / model (engine.hpp EvalFill).  On the engine's stream, so ahead of that launch.
+template <typename T>
+static void fill_const_rows(Engine& e, EvalFill& f, T* J, int blocked, int64_t n_tiles) {
+    if (f.matches(blocked, e.PL, e.chain, e.model)) return;
+    if (blocked)
+        hipLaunchKernelGGL((k_eval_fill<T, true>), dim3(blocks_for(n_tiles, 4)), dim3(256), 0, e.stream, e.chain, e.model, e.PL, n_tiles, J);
+    else
+        hipLaunchKernelGGL((k_eval_fill<T, false>), dim3(blocks_for(e.ld / 2, 256)), dim3(256), 0, e.stream, e.chain, e.model, e.PL, e.ld, J);
+    CBA_HIP(hipGetLastError());
+    f.set(blocked, e.PL, e.chain, e.model);
+}
+
+void launch_eval_fill(Engine& e) {
+    if (e.n_tilesA == 0) return;
+    if (e.scalar) {
+        fill_const_rows(e, e.Jf_fill, e.Jf.p, 1, e.n_tilesA);
+    } else if (e.Jseg.empty()) {
+        fill_const_rows(e, e.J_fill, e.J.p, e.eval_blocked ? 1 : 0, e.n_tilesA);
+    } else {
+        for (size_t k = 0; k < e.Jseg.size(); ++k) {
+            const int64_t t0 = static_cast<int64_t>(k) * e.seg_tiles;
+            fill_const_rows(e, e.Jseg_fill[k], e.Jseg[k].p, 1, std::min<int64_t>(e.seg_tiles, e.n_tilesA - t0));
+        }
+    }
+}
+
+// k_eval is about to run on buffers whose constant rows are in place (an ablation run does not care: its outputs are wrong anyway)
+static void require_eval_fill(const Engine& e) {
+    bool ok;
+    if (e.eval_ablate) return;
+    if (e.scalar) ok = e.Jf_fill.matches(1, e.PL, e.chain, e.model);
+    else if (e.Jseg.empty()) ok = e.J_fill.matches(e.eval_blocked ? 1 : 0, e.PL, e.chain, e.model);
+    else {
+        ok = e.Jseg_fill.size() == e.Jseg.size();
+        for (size_t k = 0; ok && k < e.Jseg.size(); ++k) ok = e.Jseg_fill[k].matches(1, e.PL, e.chain, e.model);
+    }
+    if (!ok) throw std::logic_error("Mode A output without its constant rows (launch_eval_fill was not called)");
+}
+
 template <int C, int M, bool NT, int ROWS>
 static void launch_eval_v(Engine& e) {
     // one launch per output segment (engine.hpp Jseg: a blocked output above 4 GiB is a few contiguous blocks of whole tiles): the
@@ -490,11 +575,11 @@ static void launch_eval_v(Engine& e) {
 #define CBA_EVAL_ARGS dim3(g), dim3(256), 0, e.stream, e.tilesA.p + t0, nt, e.bc.p, intr_of(e), e.sd.p, e.d_blk_cam.p, e.X.p, \
                       e.Y.p, e.u.p, e.v.p, e.r.p, Jk, e.ld
 #ifdef CBA_EXPERIMENTS  // timing-only ablations of k_eval (outputs are wrong): experiment builds only
-        if (ROWS == 1 && NT && e.eval_blocked && e.eval_ablate == 1)
-            hipLaunchKernelGGL((k_eval<C, M, NT, 1, true, 1>), CBA_EVAL_ARGS);
-        else if (ROWS == 1 && NT && e.eval_blocked && e.eval_ablate == 2)
-            hipLaunchKernelGGL((k_eval<C, M, NT, 1, true, 2>), CBA_EVAL_ARGS);
-        else
+        if (ROWS == 1 && NT && e.eval_blocked && (e.eval_ablate == 1 || e.eval_ablate == 2)) {  // they overwrite the constant rows
+            (e.Jseg.empty() ? e.J_fill : e.Jseg_fill[k]).valid = false;
+            if (e.eval_ablate == 1) hipLaunchKernelGGL((k_eval<C, M, NT, 1, true, 1>), CBA_EVAL_ARGS);
+            else hipLaunchKernelGGL((k_eval<C, M, NT, 1, true, 2>), CBA_EVAL_ARGS);
+        } else
 #endif
         if (e.eval_blocked)
             hipLaunchKernelGGL((k_eval<C, M, NT, ROWS, true>), CBA_EVAL_ARGS);
@@ -513,6 +598,7 @@ static void launch_eval_f32(Engine& e) {  // fp32 study: tile-blocked, non-tempo
 
 void launch_eval(Engine& e) {
     if (e.n_tilesA == 0) return;
+    require_eval_fill(e);
     if (e.scalar) {
 #define CALL(C, M) launch_eval_f32<C, M>(e);
         CBA_DISPATCH(e, CALL)

@@ -247,10 +247,27 @@ CBA_HD void reproj_core(const T* bc, const T* intr, const T* sd, T X, T Y, T uo,
     }
 }
 
+// Structural constants of the Jacobian rows.  Of the intrinsics columns [fx fy cx cy skew ...] reproj_core assigns seven entries
+// as literals (the Jui / Jvi lines above): whatever the observation, the parameters, the pose chain, the camera model and the
+// scalar type, they hold +0 or 1.  jac_const() is the one statement of which: for local column k of the u (row 0) or v (row 1)
+// Jacobian row it answers JAC_LIVE, or the constant the entry always holds (JAC_ZERO, JAC_ONE).  Mode A's kernel skips these
+// rows, its fill kernel writes them once per buffer (kernels_reproj.hip), and tests/test_mode_a_const_rows.py checks the rule
+// against reproj_point.  (Mode B's MomRows below states the same fact in its own terms, together with the duplicated entry.)
+enum { JAC_LIVE = -1, JAC_ZERO = 0, JAC_ONE = 1 };
+constexpr int intr_col_offset(int chain) { return chain == CH_INTRINSIC ? 6 : 12; }  // offset of the intrinsics columns
+constexpr int jac_const(int chain, int model, int row, int k) {
+    (void)model;  // both camera models share the five leading intrinsics entries
+    const int c = k - intr_col_offset(chain);
+    if (c < 0 || c > 4) return JAC_LIVE;
+    if (row == 0) return c == 2 ? JAC_ONE : (c == 1 || c == 3) ? JAC_ZERO : JAC_LIVE;  // u: fx live, fy 0, cx 1, cy 0, skew live
+    return c == 3 ? JAC_ONE : c == 1 ? JAC_LIVE : JAC_ZERO;                            // v: fx 0, fy live, cx 0, cy 1, skew 0
+}
+constexpr int JAC_CONST_ROWS = 7;  // entries of the 2 * PL that jac_const() marks constant
+
 // Residual + Jacobian rows.  Ju/Jv: LocalCols<CHAIN,MODEL>::value entries each, [pose A d(3) t(3) | pose B d(3) t(3) | intr].
 template <int CHAIN, int MODEL, typename T>
 CBA_HD void reproj_point(const T* bc, const T* intr, const T* sd, T X, T Y, T uo, T vo, T* r, T* Ju, T* Jv) {
-    constexpr int OI = CHAIN == CH_INTRINSIC ? 6 : 12;  // offset of the intrinsics columns
+    constexpr int OI = intr_col_offset(CHAIN);
     T P[3], du[3], dv[3];
     reproj_core<MODEL, T>(bc, intr, sd, X, Y, uo, vo, r, P, du, dv, Ju + OI, Jv + OI);
 

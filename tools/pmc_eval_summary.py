@@ -9,7 +9,7 @@ def per_launch(directory, counter):
     f = sorted(glob.glob(os.path.join(directory, "**", "*counter_collection.csv"), recursive=True))[-1]
     by_dispatch, names = {}, set()
     for r in csv.DictReader(open(f)):
-        if "k_eval" in r["Kernel_Name"] and r["Counter_Name"] == counter:
+        if "k_eval<" in r["Kernel_Name"] and r["Counter_Name"] == counter:  # not k_eval_fill (once per buffer, not per pass)
             by_dispatch[r["Dispatch_Id"]] = by_dispatch.get(r["Dispatch_Id"], 0.0) + float(r["Counter_Value"])
             names.add(r["Kernel_Name"][:60])
     vals = list(by_dispatch.values())
