@@ -432,6 +432,52 @@ static void alloc_output(DevBuf<T>& b, size_t count) {
     b.alloc(count);
 }
 
+// tile-blocked layout out[tile][2 + 2P - 1][128] (eval_layout.hpp): the residuals / Jacobian rows of residual blocks [b0, b1) into
+// r / J, indexed from the first observation of block b0.  Both logical entries of the aliased pair are read from the one slot
+// that holds them.  The tiles come over in runs: consecutive tiles of one device buffer, as many as fit a page-locked staging
+// buffer of EVAL_FETCH_CHUNK bytes, per transfer and synchronisation (a tile at a time it was 79 000 of each at 1000 x 10 000).
+// where(w, &run): device address of tile w and how many tiles from w on lie contiguously in its buffer.
+constexpr size_t EVAL_FETCH_CHUNK = size_t(4) << 20;
+template <typename T, class Where>
+static void fetch_tile_runs(Engine& e, int b0, int b1, T* r, T* J, Where where) {
+    const int P = e.PL, C = e.chain;
+    const int64_t tw = eval_tile_width(P);
+    auto tiles_of = [&](int b) { return (e.blk_offset[b + 1] - e.blk_offset[b] + TILE_A - 1) / TILE_A; };
+    int64_t w = 0, w1 = 0;
+    for (int b = 0; b < b0; ++b) w += tiles_of(b);
+    for (int b = b0; b < b1; ++b) w1 += tiles_of(b);
+    w1 += w;
+    if (w == w1) return;
+    const int64_t cap = std::max<int64_t>(1, static_cast<int64_t>(EVAL_FETCH_CHUNK / (sizeof(T) * tw)));
+    PinnedBuf<T> stage;
+    stage.reserve(static_cast<size_t>(std::min(cap, w1 - w) * tw));
+    const int64_t base = e.blk_offset[b0];
+    int b = b0;
+    int64_t s0 = 0;  // the tile about to be unpacked starts at observation s0 of block b
+    while (w < w1) {
+        int64_t run = 0;
+        const T* src = where(w, &run);
+        const int64_t nt = std::min({cap, run, w1 - w});
+        CBA_HIP(hipMemcpyAsync(stage.p, src, sizeof(T) * tw * nt, hipMemcpyDeviceToHost, e.stream));
+        CBA_HIP(hipStreamSynchronize(e.stream));
+        for (int64_t t = 0; t < nt; ++t, s0 += TILE_A) {
+            while (s0 >= e.blk_offset[b + 1] - e.blk_offset[b]) { ++b; s0 = 0; }  // next block that has observations
+            const T* buf = stage.p + t * tw;
+            const int64_t cnt = std::min<int64_t>(TILE_A, e.blk_offset[b + 1] - e.blk_offset[b] - s0);
+            for (int64_t j = 0; j < cnt; ++j) {
+                const int64_t i = e.blk_offset[b] + s0 + j - base;
+                if (r) { r[2 * i] = buf[eval_row_slot(C, P, 0) * TILE_A + j]; r[2 * i + 1] = buf[eval_row_slot(C, P, 1) * TILE_A + j]; }
+                if (J)
+                    for (int k = 0; k < P; ++k) {
+                        J[(2 * i) * P + k] = buf[eval_row_slot(C, P, 2 + k) * TILE_A + j];
+                        J[(2 * i + 1) * P + k] = buf[eval_row_slot(C, P, 2 + P + k) * TILE_A + j];
+                    }
+            }
+        }
+        w += nt;
+    }
+}
+
 extern "C" {
 
 const char* cba_version(void) { return CBA_VERSION_STRING; }
@@ -564,13 +610,13 @@ int64_t cba_reproj_num_observations(const cba_reproj* h) { return h ? reinterpre
 // or the runtime holds anything at all where k_eval expects the constant rows.
 static void alloc_eval_buffers(Engine& e) {
     if (e.scalar) {
-        const size_t jn = static_cast<size_t>(e.n_tilesA) * (2 + 2 * e.PL) * TILE_A;
+        const size_t jn = static_cast<size_t>(e.n_tilesA) * static_cast<size_t>(eval_tile_width(e.PL));
         if (e.Jf.n < jn) { e.Jf_fill.valid = false; alloc_output(e.Jf, jn); }
         return;
     }
     if (!e.eval_blocked && e.r.n < static_cast<size_t>(2 * e.ld)) e.r.alloc(static_cast<size_t>(2 * e.ld));
-    const size_t tw = static_cast<size_t>(2 + 2 * e.PL) * TILE_A;
-    const size_t jn = e.eval_blocked ? static_cast<size_t>(e.n_tilesA) * tw : static_cast<size_t>(2 * e.PL) * e.ld;
+    const size_t tw = static_cast<size_t>(eval_tile_width(e.PL));
+    const size_t jn = e.eval_blocked ? static_cast<size_t>(e.n_tilesA) * tw : static_cast<size_t>(jac_stored_rows(e.PL) - 2) * e.ld;
     // (measured at C3, 59 GB: 15 segments 11.12 ms per pass against 10.66 ms for one plain block - the fifteen launches' ramps and tails
     // cost more than the placement gains: an experiment knob, CBA_EVAL_SEGMENTS=1 in an EXPERIMENTS build)
     static const bool segmented = [] { const char* v = cba_exp_env("CBA_EVAL_SEGMENTS"); return v && atoi(v) != 0; }();
@@ -656,32 +702,13 @@ cba_status cba_reproj_normal_eq_timed(cba_reproj* h, int32_t warmup, int32_t ite
     });
 }
 
-// tile-blocked layout out[tile][2 + 2P][128]: the residuals / Jacobian rows of residual blocks [b0, b1) into r / J, indexed
-// from the first observation of block b0 (walks the host copy of the tile table; one 34-KiB copy per tile)
+// fp64 (fetch_tile_runs, above): the output is one block, or the segments of Jseg
 static void fetch_blocked_range(Engine& e, int b0, int b1, double* r, double* J) {
-    const int P = e.PL;
-    const int64_t tw = static_cast<int64_t>(2 + 2 * P) * TILE_A;
-    std::vector<double> buf(static_cast<size_t>(tw));
-    int64_t w = 0;
-    for (int b = 0; b < b0; ++b) w += (e.blk_offset[b + 1] - e.blk_offset[b] + TILE_A - 1) / TILE_A;
-    const int64_t base = e.blk_offset[b0];
-    for (int b = b0; b < b1; ++b) {
-        const int64_t n = e.blk_offset[b + 1] - e.blk_offset[b];
-        for (int64_t s0 = 0; s0 < n; s0 += TILE_A, ++w) {
-            CBA_HIP(hipMemcpyAsync(buf.data(), e.eval_tile_ptr(w, tw), sizeof(double) * tw, hipMemcpyDeviceToHost, e.stream));
-            CBA_HIP(hipStreamSynchronize(e.stream));
-            const int64_t cnt = std::min<int64_t>(TILE_A, n - s0);
-            for (int64_t j = 0; j < cnt; ++j) {
-                const int64_t i = e.blk_offset[b] + s0 + j - base;
-                if (r) { r[2 * i] = buf[eval_row_slot(P, 0) * TILE_A + j]; r[2 * i + 1] = buf[eval_row_slot(P, 1) * TILE_A + j]; }
-                if (J)
-                    for (int k = 0; k < P; ++k) {
-                        J[(2 * i) * P + k] = buf[eval_row_slot(P, 2 + k) * TILE_A + j];
-                        J[(2 * i + 1) * P + k] = buf[eval_row_slot(P, 2 + P + k) * TILE_A + j];
-                    }
-            }
-        }
-    }
+    const int64_t tw = eval_tile_width(e.PL);
+    fetch_tile_runs<double>(e, b0, b1, r, J, [&](int64_t w, int64_t* run) -> const double* {
+        *run = e.Jseg.empty() ? e.n_tilesA - w : std::min(e.seg_tiles - w % e.seg_tiles, e.n_tilesA - w);
+        return e.eval_tile_ptr(w, tw);
+    });
 }
 
 cba_status cba_reproj_eval_fetch_blocks(cba_reproj* h, int32_t b0, int32_t b1, double* r, double* J) {
@@ -719,14 +746,15 @@ cba_status cba_reproj_eval_fetch(cba_reproj* h, double* r, double* J) {
                 }
         if (J) {
             std::vector<double> row(static_cast<size_t>(e.ld));
-            for (int k = 0; k < 2 * P; ++k) {
-                CBA_HIP(hipMemcpyAsync(row.data(), e.J.p + static_cast<size_t>(k) * e.ld, sizeof(double) * e.ld,
+            for (int k = 0; k < 2 * P; ++k) {  // logical rows: the aliased pair reads its shared column twice
+                const size_t col = static_cast<size_t>(eval_row_slot(e.chain, P, 2 + k) - 2);
+                CBA_HIP(hipMemcpyAsync(row.data(), e.J.p + col * e.ld, sizeof(double) * e.ld,
                                        hipMemcpyDeviceToHost, e.stream));
                 CBA_HIP(hipStreamSynchronize(e.stream));
-                const int uvrow = k / P, col = k % P;
+                const int uvrow = k / P, kk = k % P;
                 for (int b = 0; b < e.n_blocks; ++b)
                     for (int64_t i = e.blk_offset[b]; i < e.blk_offset[b + 1]; ++i)
-                        J[(2 * i + uvrow) * P + col] = row[e.pad_offset[b] + (i - e.blk_offset[b])];
+                        J[(2 * i + uvrow) * P + kk] = row[e.pad_offset[b] + (i - e.blk_offset[b])];
             }
         }
     });
@@ -749,27 +777,11 @@ cba_status cba_reproj_eval_fetch_f32(cba_reproj* h, float* r, float* J) {
         Engine& e = *as_engine(h);
         CBA_HIP(hipSetDevice(e.device));
         if (!e.scalar || e.Jf.n == 0 || !e.eval_done) throw std::runtime_error("no fp32 evaluation available");
-        const int P = e.PL;
-        const int64_t tw = static_cast<int64_t>(2 + 2 * P) * TILE_A;
-        std::vector<float> buf(static_cast<size_t>(tw));
-        int64_t w = 0;
-        for (int b = 0; b < e.n_blocks; ++b) {
-            const int64_t n = e.blk_offset[b + 1] - e.blk_offset[b];
-            for (int64_t s0 = 0; s0 < n; s0 += TILE_A, ++w) {
-                CBA_HIP(hipMemcpyAsync(buf.data(), e.Jf.p + w * tw, sizeof(float) * tw, hipMemcpyDeviceToHost, e.stream));
-                CBA_HIP(hipStreamSynchronize(e.stream));
-                const int64_t cnt = std::min<int64_t>(TILE_A, n - s0);
-                for (int64_t j = 0; j < cnt; ++j) {
-                    const int64_t i = e.blk_offset[b] + s0 + j;
-                    if (r) { r[2 * i] = buf[eval_row_slot(P, 0) * TILE_A + j]; r[2 * i + 1] = buf[eval_row_slot(P, 1) * TILE_A + j]; }
-                    if (J)
-                        for (int k = 0; k < P; ++k) {
-                            J[(2 * i) * P + k] = buf[eval_row_slot(P, 2 + k) * TILE_A + j];
-                            J[(2 * i + 1) * P + k] = buf[eval_row_slot(P, 2 + P + k) * TILE_A + j];
-                        }
-                }
-            }
-        }
+        const int64_t tw = eval_tile_width(e.PL);
+        fetch_tile_runs<float>(e, 0, e.n_blocks, r, J, [&](int64_t w, int64_t* run) -> const float* {
+            *run = e.n_tilesA - w;
+            return e.Jf.p + w * tw;
+        });
     });
 }
 

@@ -8,10 +8,12 @@
 //                                    bitwise identical (the usual case: every view sees the same physical
 //                                    target) share one copy, so the per-observation HBM read drops from 32 B
 //                                    towards 16 B and the shared copy stays L2 / Infinity-Cache resident
-//   J (Mode A output) [n_tilesA][2 + 2P][128]  tile-blocked: for every 128-observation tile one contiguous
-//                                    (2+2P) KiB region = u/v residual rows, then the P Jacobian columns of
+//   J (Mode A output) [n_tilesA][2 + 2P - 1][128]  tile-blocked: for every 128-observation tile one contiguous
+//                                    (2+2P-1) KiB region = u/v residual rows, then the P Jacobian columns of
 //                                    the u row, then of the v row (streams like a fill; +6 % over whole-array
-//                                    columns r[2][ld], J[2P][ld], which CBA_EVAL_BLOCKED=0 still selects).
+//                                    columns r[2][ld], J[2P - 1][ld], which CBA_EVAL_BLOCKED=0 still selects).
+//                                    The v row's fy entry equals the u row's skew entry and lives in that one's
+//                                    slot (eval_layout.hpp eval_row_slot: every access goes through it).
 //                                    Seven of the 2P Jacobian rows are structural constants, written once per
 //                                    buffer and not by k_eval (EvalFill below)
 //   bc                [n_blocks][36] per-block chain constants (reproj_math.hpp BC_*)
@@ -22,6 +24,7 @@
 //   partial           [n_tilesB][NACC]  per-tile Mode B sums;  blk_acc [n_blocks][NACC] per-block sums
 #pragma once
 #include <hip/hip_runtime.h>
+#include "eval_layout.hpp"
 #include "exp_env.hpp"
 
 #include <cstdint>
@@ -211,16 +214,10 @@ struct Tile {          // 32 bytes, read with scalar loads (wave-uniform)
     int64_t reserved;
 };
 
-constexpr int TILE_A = 128;  // Mode A: 64 lanes x 2 adjacent observations
+// TILE_A = 128 (Mode A: 64 lanes x 2 adjacent observations) and the row layout of a Mode A output tile: eval_layout.hpp
 constexpr int OPL_B = 32;    // Mode B/R: observations per lane of the SHORTEST full tile (2048 observations: the wave reduction and the
                              // tile's partial row are paid once per tile; large problems use longer tiles, capi.cpp)
 constexpr int TILE_B = 64 * OPL_B;
-
-// Row slot inside a tile of the blocked Mode A output: logical row (0, 1 residuals; 2 + k the u Jacobian row of local column k;
-// 2 + PL + k the v row) -> which of the tile's 2 + 2 PL runs of 128 holds it.  The kernel, the fill of the constant rows and
-// both fetches go through this one function; the layout is private to them.  Identity: the rows k_eval skips (reproj_math.hpp
-// jac_const) stay where they were, as seven 1 KiB gaps in the tile's run.
-constexpr int eval_row_slot(int PL, int row) { (void)PL; return row; }
 
 // What a Mode A output buffer's constant rows (reproj_math.hpp jac_const) were last filled for.  k_eval does not store those rows,
 // so it may run on a buffer only while `valid` and the layout, width and chain / model it is about to use match; anything that
@@ -281,7 +278,7 @@ struct Engine {
     DevBuf<double> shared_pack[2];
     size_t pk_cam = 0, pk_target = 0, pk_delta = 0, pk_size = 0;  // offsets (doubles) of the windows
     DevBuf<double> intr[2], cam[2], view[2], target[2];
-    int eval_blocked = 1;  // Mode A output layout: 1 tile-blocked out[tile][2+2P][128] (default), 0 whole-array columns
+    int eval_blocked = 1;  // Mode A output layout: 1 tile-blocked out[tile][2+2P-1][128] (default), 0 whole-array columns
     int eval_done = 0, eval_blocked_last = 0;
     int eval_ablate = 0;  // timing-only ablation of k_eval (CBA_EVAL_ABLATE; outputs are wrong when non-zero)
     int eval_variant = 1;  // k_eval variant: bit 0 = non-temporal stores, bits 1.. = log2(tiles per wave)

@@ -81,9 +81,10 @@ __global__ void k_to_f32(int64_t n, const double* __restrict__ in, float* __rest
 // Algorithmic HBM traffic per observation: 4 loads + 2 residual stores + 2*P Jacobian stores of
 // 8 bytes = 304 B (P=16) ... 432 B (P=24).  HBM-bound: ~0.3 kFLOP per observation.
 // MOVED per observation and pass: less.  X, Y are deduplicated and cache-resident (16 B read, not 32), and the seven Jacobian
-// rows that are structural constants (reproj_math.hpp jac_const) are written once per buffer by k_eval_fill, not by k_eval:
-// 2 + 2*P - 7 stored rows, 216 B (P=16) ... 344 B (P=24), ~232 B moved at P=16.  The figure bench.py's roofline.frac divides by
-// stays the algorithmic one; roofline.traffic (profiles/pmc_k_eval.json) is the measured one.
+// rows that are structural constants (reproj_math.hpp jac_const) are written once per buffer by k_eval_fill, not by k_eval, and
+// the v row's fy entry is held in the u row's skew slot (jac_alias, eval_layout.hpp), stored once:
+// 2 + 2*P - 7 - 1 stored rows, 208 B (P=16) ... 336 B (P=24), ~224 B moved at P=16.  The figure bench.py's roofline.frac divides
+// by stays the algorithmic one; roofline.traffic (profiles/pmc_k_eval.json) is the measured one.
 template <typename T> struct Pair;
 template <> struct Pair<double> { typedef double vec __attribute__((ext_vector_type(2))); using ld = double2; };
 template <> struct Pair<float> { typedef float vec __attribute__((ext_vector_type(2))); using ld = float2; };
@@ -104,6 +105,7 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_
 
 // The constant Jacobian rows of a Mode A output buffer (reproj_math.hpp jac_const), whole rows: all 128 slots of every tile
 // (BLK, n = tiles, one wavefront per tile) or the whole column (n = ld, one lane per pair).  k_eval leaves them alone.
+// (The aliased entry, jac_alias, is live: its slot gets no fill.)
 template <typename T, bool BLK>
 __global__ __launch_bounds__(256) void k_eval_fill(int chain, int model, int PL, int64_t n, T* __restrict__ J) {
     T* o;
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(256) void k_eval_fill(int chain, int model, int PL,
     if (BLK) {
         const int64_t w = wave_index();
         if (w >= n) return;
-        o = J + w * (static_cast<int64_t>(2 + 2 * PL) * TILE_A) + 2 * (threadIdx.x & 63);
+        o = J + w * eval_tile_width(PL) + 2 * (threadIdx.x & 63);
         stride = TILE_A;
     } else {
         const int64_t i = 2 * (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x);
@@ -123,23 +125,25 @@ __global__ __launch_bounds__(256) void k_eval_fill(int chain, int model, int PL,
         const int c = jac_const(chain, model, row / PL, row % PL);
         if (c == JAC_LIVE) continue;
         const T val = c == JAC_ONE ? T(1) : T(0);
-        store2<false, T>(o + (BLK ? eval_row_slot(PL, 2 + row) : row) * stride, val, val);
+        const int slot = eval_row_slot(chain, PL, 2 + row);  // a constant entry is never the aliased one: the slot is its own
+        store2<false, T>(o + (BLK ? slot : slot - 2) * stride, val, val);
     }
 }
 
 // NT: non-temporal (streaming) stores for r / J, which this kernel never re-reads.
 // ROWS: consecutive tiles handled by one wavefront.
-// BLK: tile-blocked output layout out[tile][2 + 2P][128] (one contiguous 34 KiB region per tile) instead
-// of whole-array columns r[2][ld], J[2P][ld].
+// BLK: tile-blocked output layout out[tile][2 + 2P - 1][128] (one contiguous 33 KiB region per tile) instead
+// of whole-array columns r[2][ld], J[2P - 1][ld].  Row -> slot / column: eval_row_slot (eval_layout.hpp).
 // ABL (timing-only ablations, wrong outputs): 1 = skip the arithmetic (store the loaded values), 2 = skip the loads
 //
 // The Jacobian rows that jac_const() marks constant are NOT stored: k_eval_fill wrote them when the buffer was obtained
 // (launch_eval_fill) and nothing else writes the buffer.  The ablations store every row, constants included, and their launcher
-// marks the buffer's fill invalid.
+// marks the buffer's fill invalid.  The entry that jac_alias() sends to another one's slot (d v / d fy, held by d u / d skew) is
+// not stored either: the slot it resolves to receives the same bits from the u row.  The ablations store it as well, onto that slot.
 //
 // Software pipeline: a wavefront walks ROWS consecutive tiles and issues the 4 observation loads of tile
 // k+1 BEFORE it computes and stores tile k, so the ~2 us load latency under a write-saturated memory
-// system hides behind 34 KiB of stores instead of stalling the wave (measured: loads are 10 % of the
+// system hides behind a tile's 26 KiB of stores instead of stalling the wave (measured: loads are 10 % of the
 // bytes but cost 15 % of the time when they sit at the head of every wave).
 template <int CHAIN, int MODEL, bool NT, int ROWS, bool BLK, int ABL = 0, typename T = double>
 __global__ __launch_bounds__(256) void k_eval(const Tile* __restrict__ tiles, int64_t n_tiles,
@@ -196,25 +200,23 @@ __global__ __launch_bounds__(256) void k_eval(const Tile* __restrict__ tiles, in
                 reproj_point<CHAIN, MODEL, T>(bcp, ip, sp, Xv.y, Yv.y, uv.y, vv.y, r1, Ju1, Jv1);
             }
             if (BLK) {
-                T* o = J + w * static_cast<int64_t>((2 + 2 * PL) * TILE_A) + 2 * lane;
-                store2<NT, T>(o + eval_row_slot(PL, 0) * TILE_A, r0[0], r1[0]);
-                store2<NT, T>(o + eval_row_slot(PL, 1) * TILE_A, r0[1], r1[1]);
+                T* o = J + w * eval_tile_width(PL) + 2 * lane;
+                store2<NT, T>(o + eval_row_slot(CHAIN, PL, 0) * TILE_A, r0[0], r1[0]);
+                store2<NT, T>(o + eval_row_slot(CHAIN, PL, 1) * TILE_A, r0[1], r1[1]);
                 static_for<PL>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
-                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 0, k) == JAC_LIVE)
-                        store2<NT, T>(o + eval_row_slot(PL, 2 + k) * TILE_A, Ju0[k], Ju1[k]);
-                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 1, k) == JAC_LIVE)
-                        store2<NT, T>(o + eval_row_slot(PL, 2 + PL + k) * TILE_A, Jv0[k], Jv1[k]);
+                    constexpr int su = eval_row_slot(CHAIN, PL, 2 + k), sv = eval_row_slot(CHAIN, PL, 2 + PL + k);
+                    if constexpr (ABL != 0 || eval_row_stored(CHAIN, MODEL, 0, k)) store2<NT, T>(o + su * TILE_A, Ju0[k], Ju1[k]);
+                    if constexpr (ABL != 0 || eval_row_stored(CHAIN, MODEL, 1, k)) store2<NT, T>(o + sv * TILE_A, Jv0[k], Jv1[k]);
                 });
             } else {
                 store2<NT, T>(r + i0, r0[0], r1[0]);
                 store2<NT, T>(r + ld + i0, r0[1], r1[1]);
                 static_for<PL>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
-                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 0, k) == JAC_LIVE)
-                        store2<NT, T>(J + static_cast<int64_t>(k) * ld + i0, Ju0[k], Ju1[k]);
-                    if constexpr (ABL != 0 || jac_const(CHAIN, MODEL, 1, k) == JAC_LIVE)
-                        store2<NT, T>(J + static_cast<int64_t>(PL + k) * ld + i0, Jv0[k], Jv1[k]);
+                    constexpr int64_t cu = eval_row_slot(CHAIN, PL, 2 + k) - 2, cv = eval_row_slot(CHAIN, PL, 2 + PL + k) - 2;
+                    if constexpr (ABL != 0 || eval_row_stored(CHAIN, MODEL, 0, k)) store2<NT, T>(J + cu * ld + i0, Ju0[k], Ju1[k]);
+                    if constexpr (ABL != 0 || eval_row_stored(CHAIN, MODEL, 1, k)) store2<NT, T>(J + cv * ld + i0, Jv0[k], Jv1[k]);
                 });
             }
         }
@@ -564,13 +566,11 @@ template <int C, int M, bool NT, int ROWS>
 static void launch_eval_v(Engine& e) {
     // one launch per output segment (engine.hpp Jseg: a blocked output above 4 GiB is a few contiguous blocks of whole tiles): the
     // kernel indexes its output by the tile number relative to the tile table it is given
-    const int64_t tw = static_cast<int64_t>(2 + 2 * e.PL) * TILE_A;
     const size_t nseg = e.Jseg.empty() ? 1 : e.Jseg.size();
     for (size_t k = 0; k < nseg; ++k) {
         const int64_t t0 = e.Jseg.empty() ? 0 : static_cast<int64_t>(k) * e.seg_tiles;
         const int64_t nt = e.Jseg.empty() ? e.n_tilesA : std::min<int64_t>(e.seg_tiles, e.n_tilesA - t0);
         double* Jk = e.Jseg.empty() ? e.J.p : e.Jseg[k].p;
-        (void)tw;
         const unsigned g = blocks_for(nt, 4 * ROWS);
 #define CBA_EVAL_ARGS dim3(g), dim3(256), 0, e.stream, e.tilesA.p + t0, nt, e.bc.p, intr_of(e), e.sd.p, e.d_blk_cam.p, e.X.p, \
                       e.Y.p, e.u.p, e.v.p, e.r.p, Jk, e.ld

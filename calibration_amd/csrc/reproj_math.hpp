@@ -264,6 +264,23 @@ constexpr int jac_const(int chain, int model, int row, int k) {
 }
 constexpr int JAC_CONST_ROWS = 7;  // entries of the 2 * PL that jac_const() marks constant
 
+// The duplicated entry.  reproj_core assigns Jui[4] (d u / d skew) and Jvi[1] (d v / d fy) the same expression, yd + m0y, for
+// both camera models, every chain and both scalar types: the two are bit-equal.  jac_alias() is the one statement of it: the
+// (row, k) that holds the value of entry (row, k) - the u row's skew column for the v row's fy column, the entry itself for
+// every other one.  Mode A keeps the pair in one slot of its output (eval_layout.hpp eval_row_slot) and stores it once;
+// tests/test_mode_a_alias.py checks the rule against reproj_point.  (Mode B: MomRows below, "not shipped twice".)
+struct JacEntry { int row, k; };
+constexpr JacEntry jac_alias(int chain, int model, int row, int k) {
+    (void)model;  // as for jac_const()
+    const int oi = intr_col_offset(chain);
+    return (row == 1 && k == oi + 1) ? JacEntry{0, oi + 4} : JacEntry{row, k};
+}
+constexpr bool jac_aliased(int chain, int model, int row, int k) {
+    return jac_alias(chain, model, row, k).row != row || jac_alias(chain, model, row, k).k != k;
+}
+constexpr int JAC_ALIASED_ROWS = 1;  // entries of the 2 * PL that jac_alias() sends elsewhere
+constexpr int jac_stored_rows(int PL) { return 2 + 2 * PL - JAC_ALIASED_ROWS; }  // residuals + Jacobian rows Mode A's output holds
+
 // Residual + Jacobian rows.  Ju/Jv: LocalCols<CHAIN,MODEL>::value entries each, [pose A d(3) t(3) | pose B d(3) t(3) | intr].
 template <int CHAIN, int MODEL, typename T>
 CBA_HD void reproj_point(const T* bc, const T* intr, const T* sd, T X, T Y, T uo, T vo, T* r, T* Ju, T* Jv) {
