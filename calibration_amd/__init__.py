@@ -103,6 +103,14 @@ from .stereo import (  # noqa: F401
     rectify_maps,
     stereo_points,
 )
+from .detect import (  # noqa: F401
+    BoardDetection,
+    CornerDetector,
+    CornerOptions,
+    CornerResult,
+    detect_chessboard,
+    order_chessboard,
+)
 from .triangulate import (  # noqa: F401
     TriangulateOptions,
     TriangulationResult,

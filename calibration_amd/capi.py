@@ -189,6 +189,19 @@ class CbaStereoGeometry(C.Structure):
     _fields_ = [("focal", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double)]
 
 
+class CbaCornerOptions(C.Structure):
+    """``cba_corner_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("min_response", C.c_int32),
+        ("nms_radius", C.c_int32),
+        ("cog_radius", C.c_int32),
+        ("refine", C.c_int32),
+        ("refine_half_window", C.c_int32),
+        ("refine_iterations", C.c_int32),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, c_double_p, C.c_int64, C.c_void_p)
 
 
@@ -421,6 +434,13 @@ PROTOTYPES = {
         C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, C.POINTER(C.c_float)]),
     "cba_stereo_matcher_destroy": (None, [C.c_void_p]),
     "cba_stereo_points": (C.c_int32, [C.POINTER(CbaStereoGeometry), c_double_p, C.c_int64, c_double_p, c_double_p]),
+    "cba_corner_options_default": (None, [C.POINTER(CbaCornerOptions)]),
+    "cba_corner_detector_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaCornerOptions), C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_corner_detector_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "cba_corner_detector_destroy": (None, [C.c_void_p]),
+    "cba_chessboard_order": (C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, c_int32_p]),
 }
 
 

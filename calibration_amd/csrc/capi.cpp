@@ -24,6 +24,8 @@
 #include "linescan_math.hpp"
 #include "hom_ransac_math.hpp"
 #include "stereo_math.hpp"
+#include "corner_math.hpp"
+#include "corner_grid.hpp"
 
 using namespace cba;
 
@@ -2131,6 +2133,90 @@ __attribute__((visibility("default"))) cba_status cba_stereo_matcher_process_tim
                                                                                    double* stage_ms) {
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+}
+#endif
+
+// ---- chessboard detection (corner_detect.hip, corner_math.hpp, corner_grid.hpp) ---------------------------------------------------
+void cba_corner_options_default(cba_corner_options* o) {
+    if (!o) return;
+    o->min_response = 400;
+    o->nms_radius = 3;
+    o->cog_radius = 2;
+    o->refine = CBA_CORNER_REFINE_GRADIENT;
+    o->refine_half_window = 5;
+    o->refine_iterations = 5;
+}
+
+cba_status cba_corner_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, const cba_corner_options* opts,
+                                      int32_t device, cba_corner_detector** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!opts) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        if (width < 11 || height < 11) throw std::invalid_argument("width and height must be >= 11");
+        if (max_images < 1) throw std::invalid_argument("max_images must be >= 1");
+        if (static_cast<int64_t>(max_images) * width * height > 0x7fffffff) throw std::invalid_argument("max_images is too large");
+        if (max_corners < 1 || static_cast<int64_t>(max_images) * max_corners > (1 << 28))
+            throw std::invalid_argument("max_corners must be >= 1 and max_images max_corners <= 2^28");
+        if (opts->min_response < 1 || opts->min_response > 10200) throw std::invalid_argument("min_response must be in 1..10200");
+        if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
+        if (opts->cog_radius < 1 || opts->cog_radius > 5) throw std::invalid_argument("cog_radius must be in 1..5");
+        if (opts->refine < CBA_CORNER_REFINE_NONE || opts->refine > CBA_CORNER_REFINE_GRADIENT)
+            throw std::invalid_argument("refine must be NONE, COG or GRADIENT");
+        if (opts->refine_half_window < 1 || opts->refine_half_window > 10) throw std::invalid_argument("refine_half_window must be in 1..10");
+        if (opts->refine_iterations < 1 || opts->refine_iterations > 100) throw std::invalid_argument("refine_iterations must be in 1..100");
+        require_device(device);
+        *out = reinterpret_cast<cba_corner_detector*>(corner_detector_create(width, height, max_images, max_corners, *opts, device));
+    });
+}
+
+static cba_status corner_detector_process_impl(cba_corner_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
+                                               int32_t* out_status, double* out_xy, double* out_angle, int32_t* out_response,
+                                               int32_t* out_flags, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        CornerDetector* d = reinterpret_cast<CornerDetector*>(h);
+        if (n_images < 0 || n_images > corner_detector_max_images(d)) throw std::invalid_argument("n_images must be in [0, max_images]");
+        if (n_images == 0) return;
+        if (!images) throw std::invalid_argument("null argument");
+        corner_detector_process(d, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
+    });
+}
+
+cba_status cba_corner_detector_process(cba_corner_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
+                                       int32_t* out_status, double* out_xy, double* out_angle, int32_t* out_response, int32_t* out_flags) {
+    return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, nullptr);
+}
+
+void cba_corner_detector_destroy(cba_corner_detector* h) { corner_detector_destroy(reinterpret_cast<CornerDetector*>(h)); }
+
+cba_status cba_chessboard_order(int32_t n, const double* xy, const double* angle, int32_t rows, int32_t cols, int32_t* out_index) {
+    return guarded([&] {
+        if (!out_index) throw std::invalid_argument("null argument");
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (rows < 2 || cols < 2 || static_cast<int64_t>(rows) * cols > 65536) throw std::invalid_argument("rows and cols must be >= 2, rows cols <= 65536");
+        if (n > 0 && (!xy || !angle)) throw std::invalid_argument("null argument");
+        if (n > 65536) throw std::invalid_argument("n must be <= 65536");
+        for (int32_t i = 0; i < n; ++i)
+            if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1]) || !std::isfinite(angle[i]))
+                throw std::invalid_argument("corners must be finite");
+        if (!chessboard_order(n, xy, angle, rows, cols, out_index))
+            for (int32_t i = 0; i < rows * cols; ++i) out_index[i] = -1;  // not found
+    });
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_corners.py): cba_corner_detector_process timing its stages on the device (stage_ms [5] = upload,
+// response, peaks, refine, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_corner_detector_process_timed(cba_corner_detector* h, int32_t n_images,
+                                                                                    const uint8_t* images, int32_t* out_count,
+                                                                                    int32_t* out_status, double* out_xy, double* out_angle,
+                                                                                    int32_t* out_response, int32_t* out_flags,
+                                                                                    double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
 }
 #endif
 

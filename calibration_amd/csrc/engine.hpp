@@ -463,6 +463,14 @@ bool stereo_matcher_has_geometry(const StereoMatcher* h);
 void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost,
                             float* xyz, double* stage_ms);
 void stereo_matcher_destroy(StereoMatcher* h) noexcept;
+// corner_detect.hip: the cba_corner_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload,
+// response, peaks, refine, download
+struct CornerDetector;
+CornerDetector* corner_detector_create(int W, int H, int max_images, int max_corners, const cba_corner_options& o, int device);
+int corner_detector_max_images(const CornerDetector* h);
+void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
+                             double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms);
+void corner_detector_destroy(CornerDetector* h) noexcept;
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

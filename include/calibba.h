@@ -1023,6 +1023,95 @@ void cba_stereo_matcher_destroy(cba_stereo_matcher* h);
 cba_status cba_stereo_points(const cba_stereo_geometry* geometry, const double* pose7 /*[7] or NULL*/, int64_t n,
                              const double* uvd /*[n][3]*/, double* xyz /*[n][3]*/);
 
+/* ---- chessboard detection: corners, sub-pixel fit, grid order (no counterpart in the reference, which reads corners from files) ---
+ *
+ * Pictures of a plain chessboard -> the (object_xy, image_uv) lists every other entry point starts from.
+ *
+ * cba_corner_detector: a handle that owns the options, one stream and device buffers sized at create for max_images images of
+ * width x height with up to max_corners corners each; cba_corner_detector_process allocates nothing.  Images are single channel
+ * uint8, [n_images][height][width], rows and images contiguous; float32, colour and a blur before the response are out of scope.
+ * Options:
+ *   min_response        1..10200     lowest response of a peak (>= 1, so a constant image has none)
+ *   nms_radius          1..10        the suppression window is (2 nms_radius + 1)^2
+ *   cog_radius          1..5         the centre-of-gravity window is (2 cog_radius + 1)^2
+ *   refine              CBA_CORNER_REFINE_NONE / _COG / _GRADIENT (GRADIENT starts from the COG result)
+ *   refine_half_window  1..10        w: GRADIENT's window is (2w + 1)^2
+ *   refine_iterations   1..100       GRADIENT's rounds
+ * Rule for one image, W = width, H = height, I(x, y) the pixels:
+ * 1. Response (exact integers).  The ring offsets (dx, dy), n = 0..15, are (0,-5) (2,-5) (3,-3) (5,-2) (5,0) (5,2) (3,3) (2,5) (0,5)
+ *    (-2,5) (-3,3) (-5,2) (-5,0) (-5,-2) (-3,-3) (-2,-5), I_n = I(x + dx_n, y + dy_n).  SR = sum_{n<4} |I_n + I_{n+8} - I_{n+4} -
+ *    I_{n+12}|, DR = sum_{n<8} |I_n - I_{n+8}|, S16 = sum I_n, S5 = I(x, y) + I(x-1, y) + I(x+1, y) + I(x, y-1) + I(x, y+1),
+ *    R = 5 SR - 5 DR - |5 S16 - 16 S5|, in [-30600, 10200].  R is defined for 5 <= x <= W-6, 5 <= y <= H-6 and is 0 elsewhere.
+ * 2. Peaks.  A pixel is a peak when R >= min_response, it lies at least 5 + nms_radius from every border, and inside its
+ *    (2 nms_radius + 1)^2 window R is greater than every response earlier in row-major order and not less than every later one
+ *    (among equal responses the lowest index wins).  The peaks of an image are listed in row-major order.  With more than
+ *    max_corners peaks the first max_corners are kept, status has CBA_CORNER_STATUS_OVERFLOW and count is the true number.
+ * 3. Angle = 0.5 atan2(sum_{n<8} (I_n + I_{n+8}) s_n, sum_{n<8} (I_n + I_{n+8}) c_n) at the peak's pixel, c_n = (dx^2 - dy^2) / (dx^2 +
+ *    dy^2) and s_n = 2 dx dy / (dx^2 + dy^2) (cos and sin of twice the offset's direction; rational, hence the same doubles on every
+ *    host), each sum in fp64 with n ascending and nothing contracted; the device makes the sums, the host the atan2.  The angle is
+ *    the bisector of one quadrant pair modulo pi, x to the right and y down: the edges lie near angle +- pi/4, grid neighbours differ
+ *    by about pi/2 and diagonal neighbours are equal.
+ * 4. Position.  NONE: the peak's pixel.  COG: x = px + sum R+ dx / sum R+ over the (2 cog_radius + 1)^2 window (R+ = max(R, 0);
+ *    exact integer sums, one fp64 division per axis), the same for y.  GRADIENT (the cornerSubPix condition), from the COG result,
+ *    exactly refine_iterations rounds without a convergence test: with (cx, cy) the position, ix = floor(cx), fx = cx - ix (and y
+ *    alike), P(a, b) is the image interpolated at (ix + a + fx, iy + b + fy): top = p00 + fx (p01 - p00), bot = p10 + fx (p11 - p10),
+ *    P = top + fy (bot - top).  For (dx, dy) in the window, row-major: gx = (P(dx+1, dy) - P(dx-1, dy)) / 2, gy alike, weight
+ *    m = exp(-(dx^2 + dy^2) / (2 (w/2)^2)) (made once on the host), gxx = (gx m) gx, gxy = (gx m) gy, gyy = (gy m) gy;
+ *    a += gxx, b += gxy, c += gyy, b1 += gxx dx + gxy dy, b2 += gxy dx + gyy dy; det = a c - b b; the position moves by
+ *    ((c b1 - b b2) / det, (a b2 - b b1) / det).  All in fp64, in this order, nothing contracted.  The rounds end early, the corner
+ *    keeping its last good position, with CBA_CORNER_FLAG_WINDOW when the position or the moved position is closer than w + 2 to a
+ *    border, and with CBA_CORNER_FLAG_DET when not det > 1e-6 (a + c)^2 (further rounds would repeat the same numbers).  A corner
+ *    that ends further than cog_radius + 1 from its peak along x or y gets CBA_CORNER_FLAG_DRIFT.
+ * Outputs of process, each may be NULL: out_count [n] (true number of peaks), out_status [n], out_xy [n][max_corners][2],
+ * out_angle [n][max_corners], out_response [n][max_corners] (R at the peak's pixel), out_flags [n][max_corners].  Entries past the
+ * kept corners are NaN (xy, angle) and 0 (response, flags).  An image's result does not depend on the other images of the call.
+ *
+ * cba_chessboard_order (host, fp64; needs no device): one image's corners xy [n][2], angle [n] and the board's rows x cols INNER
+ * corners -> out_index [rows cols] into the corner list, row-major over (j, i), so that object point (i square, j square) pairs with
+ * corner out_index[j cols + i]; all -1 when the board is not found.
+ *   Neighbours: for a corner the candidates are the corners of opposite polarity, |wrap_pi(angle difference)| > pi/4, within 1.7 x
+ *   the distance of the nearest such corner; slot k = 0..3 takes the nearest candidate whose displacement lies within 35 degrees of
+ *   the direction angle + pi/4 + k pi/2; only mutual links are kept.
+ *   Labels: breadth-first growth assigns integer (i, j); the slot of a neighbour that points back defines the neighbour's frame.
+ *   Components are tried from the corner nearest the centroid of all corners outwards.
+ *   Acceptance: the component has exactly rows cols corners, no corner gets two labels, every cell is filled exactly once and the
+ *   extents are cols x rows after an optional transpose.  Partial boards are out of scope.
+ *   Canonical labelling: i runs along the cols side; the frame is right-handed in image coordinates, cross(mean i-step, mean
+ *   j-step) > 0 with x right and y down; among the labellings that remain (a half turn, or four quarter turns if rows == cols) the
+ *   one whose mean i-step has the largest x component is chosen, ties going to the larger y component.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL options, out, handle, out_index, images for
+ * n_images > 0, xy or angle for n > 0; width or height below 11 or above CBA_IMAGE_MAX_SIDE; max_images < 1 or max_images width
+ * height > 2^31 - 1; max_corners < 1 or max_images max_corners > 2^28; an option outside its range; n_images < 0 or > max_images;
+ * n < 0 or n > 65536; rows or cols < 2 or rows cols > 65536; a non-finite corner.  n_images == 0 is no work; otherwise no device ->
+ * CBA_ERR_NO_DEVICE. */
+#define CBA_CORNER_REFINE_NONE 0
+#define CBA_CORNER_REFINE_COG 1
+#define CBA_CORNER_REFINE_GRADIENT 2
+#define CBA_CORNER_STATUS_OVERFLOW 1 /* more than max_corners peaks: the first max_corners were kept */
+#define CBA_CORNER_FLAG_WINDOW 1     /* GRADIENT: the window would leave the image */
+#define CBA_CORNER_FLAG_DET 2        /* GRADIENT: determinant too small */
+#define CBA_CORNER_FLAG_DRIFT 4      /* GRADIENT: ended further than cog_radius + 1 from the peak */
+typedef struct cba_corner_options {
+    int32_t min_response;       /* 1..10200 (default 400) */
+    int32_t nms_radius;         /* 1..10 (default 3) */
+    int32_t cog_radius;         /* 1..5 (default 2) */
+    int32_t refine;             /* CBA_CORNER_REFINE_* (default GRADIENT) */
+    int32_t refine_half_window; /* w, 1..10 (default 5) */
+    int32_t refine_iterations;  /* 1..100 (default 5) */
+} cba_corner_options;
+void cba_corner_options_default(cba_corner_options* o);
+typedef struct cba_corner_detector cba_corner_detector; /* opaque: options, device buffers sized at create, one stream */
+cba_status cba_corner_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners,
+                                      const cba_corner_options* opts, int32_t device, cba_corner_detector** out);
+cba_status cba_corner_detector_process(cba_corner_detector* h, int32_t n_images, const uint8_t* images,
+                                       int32_t* out_count /*[n] or NULL*/, int32_t* out_status /*[n] or NULL*/,
+                                       double* out_xy /*[n][max_corners][2] or NULL*/, double* out_angle /*[n][max_corners] or NULL*/,
+                                       int32_t* out_response /*[n][max_corners] or NULL*/, int32_t* out_flags /*[n][max_corners] or NULL*/);
+void cba_corner_detector_destroy(cba_corner_detector* h);
+cba_status cba_chessboard_order(int32_t n, const double* xy /*[n][2]*/, const double* angle /*[n]*/, int32_t rows, int32_t cols,
+                                int32_t* out_index /*[rows cols]*/);
+
 #ifdef __cplusplus
 }
 #endif
