@@ -21,6 +21,7 @@
 #include <set>
 
 #include "engine.hpp"
+#include "pipelines.hpp"
 #include "lm_core.hpp"
 #include "lm_state.hpp"
 #include "schur_math.hpp"
@@ -878,7 +879,7 @@ struct HipBackend final : Backend {
         a.blk_acc = e.blk_acc.p; a.blk_w = e.blk_w.p; a.blk_s = e.blk_s.p; a.lmp = lmp_src; a.view = e.view[which].p;
         a.view_scale2 = e.view_scale2.p; a.view_L = e.view_L.p; a.view_y = e.view_y.p; a.view_D = e.view_D.p; a.view_gp = e.view_gp.p;
         a.blk_Z = e.blk_Z.p; a.view_gmax = st.view_gmax.p; a.cam_partial = st.cam_partial.p; a.cam_out = pack_target() + L.cam;
-        if (a.n_costp > 1 && e.cost_part.n < static_cast<size_t>(2 * a.n_costp)) e.cost_part.alloc(static_cast<size_t>(2 * a.n_costp));
+        if (a.n_costp > 1) e.cost_part.ensure(static_cast<size_t>(2 * a.n_costp));
         a.cost_part = e.cost_part.p; a.cost_out = st.stat_dev.p + 4;
         a.syrk_partial = st.syrk_partial.p; a.tiles_tail = st.sys_tiles.p + sw + n; a.view_stats = st.view_stats.p; a.stat_out = st.stat_dev.p;
         hipLaunchKernelGGL(k_sys_stage2, dim3(a.n_cc + a.n_vb + a.n_costp), dim3(256), 0, e.stream, a);

@@ -1,9 +1,9 @@
-// block_cache.cpp — process-wide reuse of device / page-locked blocks and of streams across handles (engine.hpp).
+// block_cache.cpp — process-wide reuse of device / page-locked blocks and of streams across handles (hip_glue.hpp).
 #include <map>
 #include <mutex>
 #include <vector>
 
-#include "engine.hpp"
+#include "hip_glue.hpp"
 
 namespace cba {
 namespace {

@@ -3,7 +3,7 @@
 // runs, so a block's pose is bitwise what cba_estimate_planar_pose_batch gives.  A template, so both translation units may
 // instantiate it.
 #pragma once
-#include "engine.hpp"
+#include "hip_glue.hpp"
 #include "seed_math.hpp"
 
 namespace cba {

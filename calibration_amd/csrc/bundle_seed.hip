@@ -21,7 +21,7 @@
 #include "axxb_pairs.hpp"
 #include "block_pose.hpp"
 #include "bundle_seed_math.hpp"
-#include "engine.hpp"
+#include "pipelines.hpp"
 
 namespace cba {
 
@@ -189,8 +189,7 @@ void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const 
     const int64_t n_rows = row_bound.back(), n_chunks = chunk_bound.back();
     if (n_rows > 0x7fffffffLL) throw std::invalid_argument("too many pose pairs for one launch");
 
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         StageTimer<6> tm(stream, stage_ms != nullptr);  // device events between the stages

@@ -11,9 +11,10 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "camera_math.hpp"
 
 namespace cba {
@@ -29,22 +30,10 @@ struct CamProj {  // one camera of project: intrinsics and Scheimpflug constants
     double sd[SD_SIZE];
 };
 
-int cam_grid(int64_t lanes) {
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(CAM_GRID, (lanes + CAM_BLOCK - 1) / CAM_BLOCK)));
-}
-
 int64_t whole_waves(int64_t lanes) { return (lanes + 63) / 64 * 64; }
 
-// device events of the experiment builds' timing: 0 start, 1 uploaded, 2 kernel done, 3 downloaded
+// device events of the experiment builds' timing: 0 start, 1 uploaded, 2 kernel done, 3 downloaded; stage_ms [3]: upload, kernel, download
 using CamTimer = StageTimer<4>;
-
-// stage_ms [3]: upload, kernel, download
-void cam_report(const CamTimer& tm, double* stage_ms) {
-    if (!stage_ms) return;
-    stage_ms[0] = tm.ms(0, 1);
-    stage_ms[1] = tm.ms(1, 2);
-    stage_ms[2] = tm.ms(2, 3);
-}
 
 }  // namespace
 
@@ -191,18 +180,10 @@ __global__ __launch_bounds__(CAM_BLOCK) void k_cam_apply(int n_images, const int
 }
 
 // ---- host glue -----------------------------------------------------------------------------------------------------------
-static void fill_intr(int model, const double* intr, double* out12, double* sd) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
-    for (int k = 0; k < 12; ++k) out12[k] = k < ni ? intr[k] : 0.0;
-    for (int k = 0; k < SD_SIZE; ++k) sd[k] = 0.0;
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(out12, sd);
-}
-
 void camera_project_gpu(int model, const double* intr, int64_t n, const double* xyz, double* uv, double* stage_ms, int device) {
-    CamProj c{};
-    fill_intr(model, intr, c.intr, c.sd);
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    CamProj c;
+    ls_fill_intr(model, intr, c.intr, c.sd);
+    StreamLease lease(device);
     const hipStream_t s = lease;
     CamTimer tm(s, stage_ms != nullptr);
     DevBuf<double> dxyz, duv;
@@ -211,7 +192,7 @@ void camera_project_gpu(int model, const double* intr, int64_t n, const double* 
     tm.mark(0);
     dxyz.upload(xyz, 3 * static_cast<size_t>(n), s);
     tm.mark(1);
-    const int g = cam_grid((n + 1) / 2);
+    const int g = launch_grid((n + 1) / 2, CAM_BLOCK, CAM_GRID);
     if (model == CAM_SCHEIMPFLUG)
         hipLaunchKernelGGL(k_cam_project<CAM_SCHEIMPFLUG>, dim3(g), dim3(CAM_BLOCK), 0, s, n, dxyz.p, duv.p, c);
     else
@@ -221,18 +202,14 @@ void camera_project_gpu(int model, const double* intr, int64_t n, const double* 
     duv.download(uv, 2 * static_cast<size_t>(n), s);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    cam_report(tm, stage_ms);
+    tm.report(stage_ms);
 }
 
 void camera_unproject_gpu(int model, const double* intr, int n_inv, const double* inv, int64_t n, const double* uv, double* xy,
                           double* stage_ms, int device) {
-    LsCamera c{};
-    c.model = model;
-    c.n_inv = inv ? n_inv : 0;
-    fill_intr(model, intr, c.intr, c.sd);
-    for (int k = 0; k < c.n_inv; ++k) c.inv[k] = inv[k];
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    LsCamera c;
+    ls_fill_camera(model, intr, n_inv, inv, &c);
+    StreamLease lease(device);
     const hipStream_t s = lease;
     CamTimer tm(s, stage_ms != nullptr);
     DevBuf<double> duv, dxy;
@@ -241,37 +218,35 @@ void camera_unproject_gpu(int model, const double* intr, int n_inv, const double
     tm.mark(0);
     duv.upload(uv, 2 * static_cast<size_t>(n), s);
     tm.mark(1);
-    hipLaunchKernelGGL(k_cam_unproject, dim3(cam_grid(n)), dim3(CAM_BLOCK), 0, s, n, duv.p, dxy.p, c);
+    hipLaunchKernelGGL(k_cam_unproject, dim3(launch_grid(n, CAM_BLOCK, CAM_GRID)), dim3(CAM_BLOCK), 0, s, n, duv.p, dxy.p, c);
     CBA_HIP(hipGetLastError());
     tm.mark(2);
     dxy.download(xy, 2 * static_cast<size_t>(n), s);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    cam_report(tm, stage_ms);
+    tm.report(stage_ms);
 }
 
 // The map handle: the maps stay on the device from create to destroy.  Every call ends with its stream synchronised, so nothing is
 // in flight when a buffer grows or goes.
-struct UndistortMap {
-    int device = 0;
-    StreamLease lease;
+struct UndistortMap : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
     int n_cams = 0, W = 0, H = 0;
     DevBuf<float> map_x, map_y;
     DevBuf<uint8_t> src, dst;  // apply's images, kept for the next call of the same size
     DevBuf<int32_t> img_cam;
 };
+static_assert(!std::is_copy_constructible_v<UndistortMap> && !std::is_copy_assignable_v<UndistortMap>, "a handle owns its stream and buffers");
 
 UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, const double* R9, const double* new_k5, int W, int H,
                                    double* stage_ms, int device) {
-    CBA_HIP(hipSetDevice(device));
-    auto m = std::make_unique<UndistortMap>();
-    m->device = device;
+    auto m = std::make_unique<UndistortMap>(device);
     m->n_cams = n_cams; m->W = W; m->H = H;
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
+    const int ni = cam_intr_size(model);
     std::vector<CamMapCam> hc(n_cams);
     for (int c = 0; c < n_cams; ++c) {
         CamMapCam& k = hc[c];
-        fill_intr(model, intr + static_cast<size_t>(c) * ni, k.intr, k.sd);
+        ls_fill_intr(model, intr + static_cast<size_t>(c) * ni, k.intr, k.sd);
         for (int j = 0; j < 9; ++j) k.R[j] = R9 ? R9[9 * static_cast<size_t>(c) + j] : (j % 4 == 0 ? 1.0 : 0.0);
         for (int j = 0; j < 5; ++j) k.kp[j] = new_k5 ? new_k5[5 * static_cast<size_t>(c) + j] : k.intr[j];
     }
@@ -287,7 +262,7 @@ UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, co
     tm.mark(1);
     const int cw = (W + CAM_MAP_PX - 1) / CAM_MAP_PX;
     const int64_t lpc = whole_waves(static_cast<int64_t>(H) * cw);
-    const int g = cam_grid(lpc * n_cams);
+    const int g = launch_grid(lpc * n_cams, CAM_BLOCK, CAM_GRID);
     const bool vec = W % CAM_MAP_PX == 0;
 #define CAM_MAP_LAUNCH(MODEL, VEC)                                                                                              \
     hipLaunchKernelGGL((k_cam_map<MODEL, VEC>), dim3(g), dim3(CAM_BLOCK), 0, s, n_cams, W, H, cw, lpc, dcams.p, m->map_x.p, m->map_y.p)
@@ -301,13 +276,12 @@ UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, co
     tm.mark(2);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));  // dcams goes out of scope
-    cam_report(tm, stage_ms);
+    tm.report(stage_ms);
     return m.release();
 }
 
 void undistort_map_fetch(UndistortMap* m, float* map_x, float* map_y) {
-    CBA_HIP(hipSetDevice(m->device));
-    const hipStream_t s = m->lease;
+    const hipStream_t s = m->begin();
     const size_t npx = static_cast<size_t>(m->W) * m->H * m->n_cams;
     m->map_x.download(map_x, npx, s);
     m->map_y.download(map_y, npx, s);
@@ -317,7 +291,7 @@ void undistort_map_fetch(UndistortMap* m, float* map_x, float* map_y) {
 template <typename T, int CH, int LOAD>
 static void apply_launch(UndistortMap* m, int n_images, int sw, int sh, T border, hipStream_t s) {
     const int64_t lpi = whole_waves(static_cast<int64_t>(m->W) * m->H);
-    hipLaunchKernelGGL((k_cam_apply<T, CH, LOAD>), dim3(cam_grid(lpi * n_images)), dim3(CAM_BLOCK), 0, s, n_images, m->img_cam.p, m->W, m->H,
+    hipLaunchKernelGGL((k_cam_apply<T, CH, LOAD>), dim3(launch_grid(lpi * n_images, CAM_BLOCK, CAM_GRID)), dim3(CAM_BLOCK), 0, s, n_images, m->img_cam.p, m->W, m->H,
                        lpi, sw, sh, reinterpret_cast<const T*>(m->src.p), reinterpret_cast<T*>(m->dst.p), m->map_x.p, m->map_y.p, border);
 }
 
@@ -343,15 +317,14 @@ static int u8_load_shape() {
 
 void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int sw, int sh, int ch, int dtype, double border,
                          const void* src, void* dst, double* stage_ms) {
-    CBA_HIP(hipSetDevice(m->device));
-    const hipStream_t s = m->lease;
+    const hipStream_t s = m->begin();
     const size_t esz = dtype == CBA_DTYPE_F32 ? 4 : 1;
     const size_t src_bytes = static_cast<size_t>(n_images) * sw * sh * ch * esz;
     const size_t dst_bytes = static_cast<size_t>(n_images) * m->W * m->H * ch * esz;
     // the buffers grow before anything is queued on the stream in this call, and the previous call synchronised it
-    if (m->src.n < src_bytes + CAM_SRC_PAD) m->src.alloc(src_bytes + CAM_SRC_PAD);
-    if (m->dst.n < dst_bytes) m->dst.alloc(dst_bytes);
-    if (m->img_cam.n < static_cast<size_t>(n_images)) m->img_cam.alloc(n_images);
+    m->src.ensure(src_bytes + CAM_SRC_PAD);
+    m->dst.ensure(dst_bytes);
+    m->img_cam.ensure(n_images);
     CamTimer tm(s, stage_ms != nullptr);
     tm.mark(0);
     m->img_cam.upload(cam, n_images, s);
@@ -369,15 +342,11 @@ void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int 
     m->dst.download(static_cast<uint8_t*>(dst), dst_bytes, s);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    cam_report(tm, stage_ms);
+    tm.report(stage_ms);
 }
 
 int undistort_map_cams(const UndistortMap* m) { return m->n_cams; }
 
-void undistort_map_destroy(UndistortMap* m) noexcept {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    delete m;
-}
+void undistort_map_destroy(UndistortMap* m) noexcept { destroy_handle(m); }
 
 }  // namespace cba

@@ -70,6 +70,7 @@ struct CamMapCam {
     double R[9];
     double kp[5];  // fx' fy' cx' cy' skew'
 };
+static_assert(sizeof(CamMapCam) == 496, "CamMapCam is read by k_cam_map: its layout is fixed");
 
 // The source pixel of output pixel (up, vp): the projection of P = R^T (x, y, 1), (x, y) = K'^-1 (up, vp) in ls_normalize's order,
 // rounded to nearest float32; NaN in both where the denominator is not positive (or NaN)

@@ -1,96 +1,34 @@
-// capi.cpp — the extern "C" boundary of libcalibba.so (include/calibba.h).
+// capi.cpp — the extern "C" boundary of libcalibba.so (include/calibba.h): the cba_reproj handle and the one-shot solvers.  The batched
+// pipelines' entry points are in capi_pipelines.cpp; what both files share (guarded, the device and argument checks) is in
+// capi_common.hpp.
 //
 // Host-side duties only: validate like the reference, lay observations out in padded SoA, build the
 // wave-tile tables, move buffers, launch kernels, translate C++ exceptions into status codes.
 // There is no CPU arithmetic path: without a HIP device every compute call returns
 // CBA_ERR_NO_DEVICE.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <exception>
-#include <limits>
 #include <mutex>
 #include <thread>
 #include <cstring>
 #include <memory>
-#include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "capi_common.hpp"
 #include "engine.hpp"
+#include "pipelines.hpp"
 #include "structure.hpp"
-#include "linescan_math.hpp"
-#include "hom_ransac_math.hpp"
-#include "stereo_math.hpp"
-#include "corner_math.hpp"
-#include "corner_grid.hpp"
 
 using namespace cba;
 
-static thread_local std::string g_err;
-
-template <typename F>
-static cba_status guarded(F&& f) {
-    try {
-        f();
-        return CBA_OK;
-    } catch (const std::invalid_argument& e) {
-        g_err = e.what();
-        return CBA_ERR_INVALID_ARGUMENT;
-    } catch (const NoDevice& e) {
-        g_err = e.what();
-        return CBA_ERR_NO_DEVICE;
-    } catch (const HipError& e) {
-        g_err = e.what();
-        return CBA_ERR_HIP;
-    } catch (const std::runtime_error& e) {
-        g_err = e.what();
-        return CBA_ERR_RUNTIME;
-    } catch (const std::exception& e) {
-        g_err = e.what();
-        return CBA_ERR_INTERNAL;
-    }
-}
-
-// the device of the entry points that take no handle and no device argument (one process per GPU: cba_set_device(LOCAL_RANK))
-static std::atomic<int> g_default_device{0};
-static int default_device() { return g_default_device.load(); }
-
-// The offset table [n + 1] of a call's groups of observations.  The entry points differ in two policies, kept as they shipped:
-// whether the table must start at 0, and whether a group is limited to INT32_MAX observations (the kernels that count a group in
-// an int need it).  what: "view " / "block " / "" for the message.
-enum : unsigned { OFF_ANY_START = 0, OFF_FROM_ZERO = 1, OFF_INT32_GROUPS = 2 };
-static bool bad_offset_step(const int64_t* off, int i, unsigned policy) {
-    return off[i + 1] < off[i] || ((policy & OFF_INT32_GROUPS) && off[i + 1] - off[i] > 0x7fffffff);
-}
-static void check_offsets(const int64_t* off, int n, const char* what, unsigned policy) {
-    if ((policy & OFF_FROM_ZERO) && off[0] != 0) throw std::invalid_argument(std::string(what) + "offsets must start at 0");
-    for (int i = 0; i < n; ++i)
-        if (bad_offset_step(off, i, policy))
-            throw std::invalid_argument(*what ? std::string("bad ") + what + "offsets" : "offsets must not decrease");
-}
-
-static int device_count() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-// every entry point that needs a device, after its argument checks: the number of visible devices, or CBA_ERR_NO_DEVICE
-static int require_device() {
-    const int n = device_count();
-    if (n <= 0) throw NoDevice("no HIP device visible: libcalibba has no CPU fallback");
-    return n;
-}
-// ... and those that take a device index
-static void require_device(int device) {
-    if (device < 0 || device >= require_device()) throw std::invalid_argument("device index out of range");
-}
+__attribute__((visibility("hidden"))) thread_local std::string g_err;
+__attribute__((visibility("hidden"))) std::atomic<int> g_default_device{0};
 
 Engine::~Engine() {
-    // the buffers below go back to the process-wide cache (engine.hpp): nothing may still be running on them
+    // the buffers below go back to the process-wide cache (hip_glue.hpp): nothing may still be running on them
     if (stream) (void)hipStreamSynchronize(stream);
     rccl_destroy(*this);
     destroy_lm_state(*this);
@@ -1234,990 +1172,5 @@ cba_status cba_estimate_planar_pose_batch(int32_t n_views, const int64_t* view_o
         planar_seed_batch(n_views, view_offset, X, Y, u, v, kmtx5, pose7, default_device());
     });
 }
-
-// ---- laser-plane calibration (linescan.hip) --------------------------------------------------------------------------------
-void cba_plane_fit_options_default(cba_plane_fit_options* o) {
-    if (!o) return;
-    o->use_ransac = 0;  // LineScanPlaneFitOptions (linescan.h:30-33), RansacOptions (ransac.h:23-30)
-    o->max_iters = 1000;
-    o->thresh = 2.0;
-    o->min_inliers = 12;
-    o->refit_on_inliers = 1;
-    o->confidence = 0.99;
-    o->seed = 1234567;
-}
-
-static void check_plane_fit_options(const cba_plane_fit_options* o) {
-    if (!o) throw std::invalid_argument("null options");
-    // max_iters: one lane and 10 partial sums per chunk for each hypothesis (the scoring grid is max_iters / 256 workgroups wide)
-    if (o->use_ransac && (o->max_iters <= 0 || o->max_iters > CBA_PLANE_FIT_MAX_ITERS || !(o->thresh >= 0.0)))
-        throw std::invalid_argument("bad RANSAC options (max_iters must be in [1, CBA_PLANE_FIT_MAX_ITERS], thresh >= 0)");
-}
-
-static cba_status laser_plane_impl(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                                   int32_t n_views, const int64_t* target_offset, const double* X, const double* Y, const double* u,
-                                   const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
-                                   const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* points_xyz,
-                                   uint8_t* inlier_mask, double* stage_ms) {
-    return guarded([&] {
-        if (camera_model != CBA_CAMERA_PINHOLE_BC && camera_model != CBA_CAMERA_SCHEIMPFLUG) throw std::invalid_argument("bad camera model");
-        if (!intr || !target_offset || !laser_offset || !result || (n_views > 0 && (!X || !Y || !u || !v)))
-            throw std::invalid_argument("null argument");
-        if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV)) throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
-        check_plane_fit_options(opts);
-        // validate_observations (linescan.h:39-47)
-        if (n_views < 2) throw std::invalid_argument("At least 2 views are required");
-        if (target_offset[0] != 0 || laser_offset[0] != 0) throw std::invalid_argument("offsets must start at 0");
-        // both tables start at 0; int32 groups of target points, laser pixels unlimited.  A loop of its own: the two tables and the
-        // reference's count check are tested view by view, and the first failing view names the error
-        for (int i = 0; i < n_views; ++i) {
-            if (bad_offset_step(target_offset, i, OFF_INT32_GROUPS) || bad_offset_step(laser_offset, i, 0))
-                throw std::invalid_argument("bad view offsets");
-            if (target_offset[i + 1] - target_offset[i] < 4) throw std::invalid_argument("Each view requires >=4 target correspondences");
-        }
-        if (laser_offset[n_views] > 0 && (!laser_u || !laser_v)) throw std::invalid_argument("null argument");
-        require_device();
-        laser_plane_calibrate(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
-                              laser_v, *opts, result, points_xyz, inlier_mask, stage_ms, default_device());
-    });
-}
-
-cba_status cba_calibrate_laser_plane(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                                     int32_t n_views, const int64_t* target_offset, const double* X, const double* Y, const double* u,
-                                     const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
-                                     const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* points_xyz,
-                                     uint8_t* inlier_mask) {
-    return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
-                            laser_v, opts, result, points_xyz, inlier_mask, nullptr);
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_linescan.py): cba_calibrate_laser_plane without the optional outputs, timing its stages on
-// the device: stage_ms [5] = per-view geometry, laser-point back-projection, the whole plane fit, RANSAC scoring pass 1
-// (moments), RANSAC scoring pass 2 (recount).  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_calibrate_laser_plane_timed(
-    int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int32_t n_views, const int64_t* target_offset,
-    const double* X, const double* Y, const double* u, const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
-    const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
-                            laser_v, opts, result, nullptr, nullptr, stage_ms);
-}
-#endif
-
-cba_status cba_fit_plane(int64_t n, const double* xyz, const cba_plane_fit_options* opts, double* plane, double* inlier_rms,
-                         int64_t* inlier_count, uint8_t* inlier_mask) {
-    return guarded([&] {
-        if (!xyz || !plane || !inlier_rms || !inlier_count) throw std::invalid_argument("null argument");
-        check_plane_fit_options(opts);
-        if (n < 3) throw std::invalid_argument("Not enough points to fit a plane");
-        require_device();
-        plane_fit(n, xyz, *opts, plane, inlier_rms, inlier_count, inlier_mask, default_device());
-    });
-}
-
-// invert_brown_conrady (distortion.h:165-195) -> fit_distortion_full (:231-291) with K = identity: the 882 x n least-squares
-// problem, solved by Householder QR (the reference's JacobiSVD solve; the design has full column rank).
-cba_status cba_invert_brown_conrady(int32_t n, const double* forward, double* inverse) {
-    return guarded([&] {
-        if (!forward || !inverse) throw std::invalid_argument("null argument");
-        if (n < 2) throw std::runtime_error("Insufficient distortion coefficients");
-        const int nr = n - 2, grid = 21, m = 2 * grid * grid;
-        std::vector<double> A(static_cast<size_t>(m) * n), b(m);
-        auto distort = [&](double x, double y, double* xd, double* yd) {
-            const double r2 = x * x + y * y;
-            double radial = 1.0, rpow = r2;
-            for (int i = 0; i < nr; ++i) { radial += forward[i] * rpow; rpow *= r2; }
-            *xd = x * radial + 2.0 * forward[nr] * x * y + forward[nr + 1] * (r2 + 2.0 * x * x);
-            *yd = y * radial + forward[nr] * (r2 + 2.0 * y * y) + 2.0 * forward[nr + 1] * x * y;
-        };
-        int row = 0;
-        for (int i = 0; i < grid; ++i) {
-            const double xu = -1.0 + 2.0 * static_cast<double>(i) / static_cast<double>(grid - 1);
-            for (int j = 0; j < grid; ++j) {
-                const double yu = -1.0 + 2.0 * static_cast<double>(j) / static_cast<double>(grid - 1);
-                double x, y;  // observation: (x, y) = distorted, (u, v) = undistorted
-                distort(xu, yu, &x, &y);
-                const double r2 = x * x + y * y;
-                double* au = &A[static_cast<size_t>(row) * n];
-                double* av = &A[static_cast<size_t>(row + 1) * n];
-                double rpow = r2;
-                for (int k = 0; k < nr; ++k) { au[k] = x * rpow; av[k] = y * rpow; rpow *= r2; }
-                au[nr] = 2.0 * x * y; au[nr + 1] = r2 + 2.0 * x * x;
-                av[nr] = r2 + 2.0 * y * y; av[nr + 1] = 2.0 * x * y;
-                b[row] = xu - x;
-                b[row + 1] = yu - y;
-                row += 2;
-            }
-        }
-        // Householder QR of A (m x n, row-major), applied to b as it goes
-        for (int k = 0; k < n; ++k) {
-            double nrm = 0.0;
-            for (int i = k; i < m; ++i) nrm += A[static_cast<size_t>(i) * n + k] * A[static_cast<size_t>(i) * n + k];
-            nrm = std::sqrt(nrm);
-            if (nrm == 0.0) throw std::runtime_error("rank-deficient distortion fit");
-            const double akk = A[static_cast<size_t>(k) * n + k];
-            const double alpha = akk > 0.0 ? -nrm : nrm;
-            std::vector<double> w(m - k);
-            for (int i = k; i < m; ++i) w[i - k] = A[static_cast<size_t>(i) * n + k];
-            w[0] -= alpha;
-            double ww = 0.0;
-            for (double t : w) ww += t * t;
-            for (int j = k; j < n; ++j) {
-                double d = 0.0;
-                for (int i = k; i < m; ++i) d += w[i - k] * A[static_cast<size_t>(i) * n + j];
-                d = 2.0 * d / ww;
-                for (int i = k; i < m; ++i) A[static_cast<size_t>(i) * n + j] -= d * w[i - k];
-            }
-            double d = 0.0;
-            for (int i = k; i < m; ++i) d += w[i - k] * b[i];
-            d = 2.0 * d / ww;
-            for (int i = k; i < m; ++i) b[i] -= d * w[i - k];
-        }
-        for (int k = n - 1; k >= 0; --k) {
-            double s = b[k];
-            for (int j = k + 1; j < n; ++j) s -= A[static_cast<size_t>(k) * n + j] * inverse[j];
-            inverse[k] = s / A[static_cast<size_t>(k) * n + k];
-        }
-    });
-}
-
-// ---- linear seed of planar intrinsic calibration (hom_ransac.hip, hom_ransac_math.hpp) ----------------------------------------
-void cba_ransac_options_default(cba_ransac_options* o) {
-    if (!o) return;
-    o->max_iters = 1000;  // RansacOptions (ransac.h:23-30)
-    o->thresh = 2.0;
-    o->min_inliers = 12;
-    o->refit_on_inliers = 1;
-    o->confidence = 0.99;
-    o->seed = 1234567;
-}
-
-static void check_views(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v) {
-    if (n_views < 0 || !view_offset) throw std::invalid_argument("null argument");
-    if (n_views > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
-    check_offsets(view_offset, n_views, "view ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
-}
-
-static void check_ransac_options(const cba_ransac_options* o) {
-    // max_iters: one lane per hypothesis; the scoring grid is max_iters / 256 workgroups per view, each writing one candidate record
-    if (o->max_iters < 0 || o->max_iters > CBA_RANSAC_MAX_ITERS || !(o->thresh >= 0.0))
-        throw std::invalid_argument("bad RANSAC options (max_iters must be in [0, CBA_RANSAC_MAX_ITERS], thresh >= 0)");
-}
-
-// estimate_homography (optim/homography.cpp:45-60 with RansacOptions, :31-43 without)
-cba_status cba_estimate_homography_ransac_batch(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y,
-                                                const double* u, const double* v, const cba_ransac_options* opts, double* h9,
-                                                int32_t* success, int32_t* inlier_count, double* symmetric_rms, uint8_t* inlier_mask) {
-    return guarded([&] {
-        check_views(n_views, view_offset, X, Y, u, v);
-        if (!h9 || !success || !inlier_count || !symmetric_rms) throw std::invalid_argument("null argument");
-        if (opts) check_ransac_options(opts);
-        if (n_views == 0) return;
-        require_device();
-        homography_ransac_batch(n_views, view_offset, X, Y, u, v, opts, h9, success, inlier_count, symmetric_rms, inlier_mask,
-                                default_device());
-    });
-}
-
-static cba_status estimate_intrinsics_impl(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u,
-                                           const double* v, int32_t use_ransac, const cba_ransac_options* ransac, const double* bounds_lo5,
-                                           const double* bounds_hi5, int32_t* success, double* kmtx5, int32_t* sanitized,
-                                           int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12, int32_t* pose_ok,
-                                           uint8_t* inlier_mask, double* stage_ms) {
-    return guarded([&] {
-        check_views(n_views, view_offset, X, Y, u, v);
-        if (!success || !kmtx5 || !sanitized) throw std::invalid_argument("null argument");
-        if (n_views > 0 && (!view_ok || !h9 || !forward_rms_px || !rt12 || !pose_ok)) throw std::invalid_argument("null argument");
-        if (!bounds_lo5 != !bounds_hi5) throw std::invalid_argument("bounds_lo5 and bounds_hi5 must both be given or both be NULL");
-        if (use_ransac) {
-            if (!ransac) throw std::invalid_argument("null argument");
-            check_ransac_options(ransac);
-        }
-        *success = 0;
-        *sanitized = 0;
-        for (int k = 0; k < 5; ++k) kmtx5[k] = 0.0;
-        if (n_views == 0) return;  // intrinsicsdlt.cpp:104-106
-        require_device();
-        estimate_intrinsics_gpu(n_views, view_offset, X, Y, u, v, use_ransac ? ransac : nullptr, bounds_lo5, bounds_hi5, success, kmtx5,
-                                sanitized, view_ok, h9, forward_rms_px, rt12, pose_ok, inlier_mask, stage_ms, default_device());
-    });
-}
-
-cba_status cba_estimate_intrinsics(int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u,
-                                   const double* v, int32_t use_ransac, const cba_ransac_options* ransac, const double* bounds_lo5,
-                                   const double* bounds_hi5, int32_t use_skew, int32_t* success, double* kmtx5, int32_t* sanitized,
-                                   int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12, int32_t* pose_ok,
-                                   uint8_t* inlier_mask) {
-    (void)use_skew;  // IntrinsicsEstimOptions::use_skew is not read by estimate_intrinsics
-    return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, bounds_lo5, bounds_hi5, success, kmtx5, sanitized,
-                                    view_ok, h9, forward_rms_px, rt12, pose_ok, inlier_mask, nullptr);
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_intrinsics_seed.py): cba_estimate_intrinsics timing its stages on the device: stage_ms [5] =
-// homographies (the scoring kernel, or the DLT), homographies (selection, h22 rescale, symmetric rms), Zhang + sanitize, poses,
-// total.  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_timed(
-    int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v, int32_t use_ransac,
-    const cba_ransac_options* ransac, int32_t* success, double* kmtx5, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
-    int32_t* pose_ok, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    int32_t sanitized = 0;
-    return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, nullptr, nullptr, success, kmtx5, &sanitized,
-                                    view_ok, h9, forward_rms_px, rt12, pose_ok, nullptr, stage_ms);
-}
-#endif
-
-// zhang_intrinsics_from_hs (zhang.cpp:174-206), compiled for the host from the device header
-cba_status cba_zhang_intrinsics_from_hs(int32_t n, const double* h9, double* kmtx5, int32_t* success) {
-    return guarded([&] {
-        if (n < 0 || (n > 0 && !h9) || !kmtx5 || !success) throw std::invalid_argument("null argument");
-        double G[36] = {};
-        for (int i = 0; i < n; ++i) hr_zhang_accumulate(h9 + 9 * static_cast<int64_t>(i), G);
-        double k5[5];
-        *success = hr_zhang_solve(n, G, k5) ? 1 : 0;
-        if (*success)
-            for (int k = 0; k < 5; ++k) kmtx5[k] = k5[k];
-    });
-}
-
-cba_status cba_pose_from_homography(const double* kmtx5, const double* h9, double* rt12, int32_t* success, double* scale,
-                                    double* cond_check) {
-    return guarded([&] {
-        if (!kmtx5 || !h9 || !rt12 || !success) throw std::invalid_argument("null argument");
-        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 0.0, c = 0.0;
-        *success = hr_pose_from_homography(kmtx5, h9, R, t, &s, &c) ? 1 : 0;
-        if (!*success) {
-            const double id[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            for (int a = 0; a < 9; ++a) R[a] = id[a];
-            t[0] = t[1] = t[2] = 0.0;
-        }
-        for (int a = 0; a < 9; ++a) rt12[a] = R[a];
-        for (int k = 0; k < 3; ++k) rt12[9 + k] = t[k];
-        if (scale) *scale = s;
-        if (cond_check) *cond_check = c;
-    });
-}
-
-cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5, const double* bounds_hi5, double* out5,
-                                   int32_t* modified) {
-    return guarded([&] {
-        if (!kmtx5 || !bounds_lo5 || !bounds_hi5 || !out5 || !modified) throw std::invalid_argument("null argument");
-        *modified = hr_sanitize(kmtx5, bounds_lo5, bounds_hi5, out5) ? 1 : 0;
-    });
-}
-
-
-// ---- linear seed of a multi-camera rig (extrinsic_dlt.hip, extrinsic_dlt_math.hpp) -------------------------------------------
-static cba_status extrinsic_dlt_impl(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
-                                     const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
-                                     const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok,
-                                     double* stage_ms) {
-    return guarded([&] {
-        if (n_cams < 1 || n_views < 1) throw std::runtime_error("Empty views or cameras provided");  // extrinsics.h:31-33
-        if (n_blocks < 0) throw std::invalid_argument("n_blocks must be >= 0");
-        if (!blk_offset || !kmtx5 || !c_T_r || !r_T_t || (n_blocks > 0 && (!blk_view || !blk_cam))) throw std::invalid_argument("null argument");
-        check_offsets(blk_offset, n_blocks, "block ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
-        if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
-        // the (view, camera) -> block table: the averaging order of the device stages comes from it, never from the block order
-        std::vector<int32_t> table(static_cast<size_t>(n_views) * static_cast<size_t>(n_cams), -1);
-        for (int b = 0; b < n_blocks; ++b) {
-            if (blk_view[b] < 0 || blk_view[b] >= n_views) throw std::invalid_argument("block " + std::to_string(b) + ": view index out of range");
-            if (blk_cam[b] < 0 || blk_cam[b] >= n_cams) throw std::invalid_argument("block " + std::to_string(b) + ": camera index out of range");
-            int32_t& slot = table[static_cast<size_t>(blk_view[b]) * static_cast<size_t>(n_cams) + static_cast<size_t>(blk_cam[b])];
-            if (slot >= 0)
-                throw std::invalid_argument("blocks " + std::to_string(slot) + " and " + std::to_string(b) + " share view " +
-                                            std::to_string(blk_view[b]) + " and camera " + std::to_string(blk_cam[b]));
-            slot = b;
-        }
-        if (n_blocks == 0) {  // every pose is the identity (extrinsics.h:55, 65)
-            for (int64_t i = 0; i < n_cams; ++i)
-                for (int k = 0; k < 7; ++k) c_T_r[7 * i + k] = k == 0 ? 1.0 : 0.0;
-            for (int64_t i = 0; i < n_views; ++i)
-                for (int k = 0; k < 7; ++k) r_T_t[7 * i + k] = k == 0 ? 1.0 : 0.0;
-            if (stage_ms)
-                for (int k = 0; k < 4; ++k) stage_ms[k] = 0.0;
-            return;
-        }
-        require_device();
-        extrinsic_dlt_gpu(n_cams, n_views, n_blocks, blk_offset, blk_cam, table.data(), X, Y, u, v, kmtx5, c_T_r, r_T_t, blk_c_T_t, blk_ok,
-                          stage_ms, default_device());
-    });
-}
-
-cba_status cba_estimate_extrinsic_dlt(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
-                                      const int32_t* blk_cam, const double* X, const double* Y, const double* u, const double* v,
-                                      const double* kmtx5, double* c_T_r, double* r_T_t, double* blk_c_T_t, int32_t* blk_ok) {
-    return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, blk_c_T_t, blk_ok,
-                              nullptr);
-}
-
-// ---- seed of the hand-eye and bundle stages (bundle_seed.hip, bundle_seed_math.hpp) ------------------------------------------
-static cba_status bundle_seed_impl(int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g,
-                                   const double* X, const double* Y, const double* u, const double* v, const double* kmtx5,
-                                   double min_angle_deg, const int32_t* given_mask, const double* g_T_c_given, const double* b_T_t_given,
-                                   double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, double* b_T_t, int32_t* target_source,
-                                   double* blk_c_T_t, int32_t* blk_ok, double* stage_ms) {
-    return guarded([&] {
-        if (n_cams < 1) throw std::invalid_argument("n_cams must be >= 1");
-        if (n_blocks < 0) throw std::invalid_argument("n_blocks must be >= 0");
-        if (!(min_angle_deg >= 0.0) || !std::isfinite(min_angle_deg)) throw std::invalid_argument("min_angle_deg must be finite and >= 0");
-        if (!blk_offset || !kmtx5 || !g_T_c || !cam_status || !cam_pairs || !b_T_t || !target_source ||
-            (n_blocks > 0 && (!blk_cam || !blk_b_T_g)))
-            throw std::invalid_argument("null argument");
-        if (given_mask && !g_T_c_given) throw std::invalid_argument("given_mask needs g_T_c_given");
-        check_offsets(blk_offset, n_blocks, "block ", OFF_FROM_ZERO | OFF_INT32_GROUPS);  // from 0, int32 groups
-        if (blk_offset[n_blocks] > 0 && (!X || !Y || !u || !v)) throw std::invalid_argument("null argument");
-        for (int b = 0; b < n_blocks; ++b)
-            if (blk_cam[b] < 0 || blk_cam[b] >= n_cams) throw std::invalid_argument("block " + std::to_string(b) + ": camera index out of range");
-        // each camera's pose list: its blocks of >= 4 points in increasing block index (the reference's SensorAccumulator)
-        std::vector<int32_t> cam_start(static_cast<size_t>(n_cams) + 1, 0), cam_blk;
-        for (int b = 0; b < n_blocks; ++b)
-            if (blk_offset[b + 1] - blk_offset[b] >= 4) ++cam_start[static_cast<size_t>(blk_cam[b]) + 1];
-        for (int c = 0; c < n_cams; ++c) cam_start[c + 1] += cam_start[c];
-        cam_blk.resize(static_cast<size_t>(cam_start[n_cams]));
-        {
-            std::vector<int32_t> fill(cam_start.begin(), cam_start.end() - 1);
-            for (int b = 0; b < n_blocks; ++b)
-                if (blk_offset[b + 1] - blk_offset[b] >= 4) cam_blk[fill[blk_cam[b]]++] = b;
-        }
-        // statuses the host decides; the device overwrites the DLT cameras'
-        for (int c = 0; c < n_cams; ++c) {
-            double* g = g_T_c + 7 * static_cast<int64_t>(c);
-            cam_pairs[c] = 0;
-            if (given_mask && given_mask[c]) {
-                for (int k = 0; k < 7; ++k) g[k] = g_T_c_given[7 * static_cast<int64_t>(c) + k];
-                cam_status[c] = CBA_HANDEYE_GIVEN;
-                continue;
-            }
-            for (int k = 0; k < 7; ++k) g[k] = k == 0 ? 1.0 : 0.0;
-            cam_status[c] = cam_start[c + 1] - cam_start[c] >= 2 ? CBA_HANDEYE_DLT : CBA_HANDEYE_TOO_FEW_VIEWS;
-        }
-        if (b_T_t_given) {
-            for (int k = 0; k < 7; ++k) b_T_t[k] = b_T_t_given[k];
-            *target_source = CBA_TARGET_CONFIG;
-        } else {
-            for (int k = 0; k < 7; ++k) b_T_t[k] = k == 0 ? 1.0 : 0.0;
-            *target_source = cam_start[n_cams] > 0 ? CBA_TARGET_ESTIMATED : CBA_TARGET_IDENTITY;
-        }
-        if (stage_ms)
-            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
-        if (n_blocks == 0) return;  // nothing for a device to do
-        require_device();
-        bundle_seed_gpu(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, cam_start.data(), cam_blk.data(),
-                        g_T_c, cam_status, cam_pairs, b_T_t_given, b_T_t, blk_c_T_t, blk_ok, stage_ms, default_device());
-    });
-}
-
-cba_status cba_estimate_bundle_seed(int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g,
-                                    const double* X, const double* Y, const double* u, const double* v, const double* kmtx5,
-                                    double min_angle_deg, const int32_t* given_mask, const double* g_T_c_given, const double* b_T_t_given,
-                                    double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, double* b_T_t, int32_t* target_source,
-                                    double* blk_c_T_t, int32_t* blk_ok) {
-    return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, given_mask, g_T_c_given,
-                            b_T_t_given, g_T_c, cam_status, cam_pairs, b_T_t, target_source, blk_c_T_t, blk_ok, nullptr);
-}
-
-// ---- distortion fits and the linear intrinsic estimators (distortion_fit.hip, distortion_fit_math.hpp) ----------------------
-static void check_problems(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v) {
-    if (n_problems < 0) throw std::invalid_argument("n_problems must be >= 0");
-    if (n_problems == 0) return;
-    if (!offset) throw std::invalid_argument("null argument");
-    check_offsets(offset, n_problems, "", OFF_FROM_ZERO);  // from 0, groups of any size (the chunked kernels index in int64)
-    if (offset[n_problems] > 0 && (!x || !y || !u || !v)) throw std::invalid_argument("null argument");
-}
-
-static void check_num_radial(int32_t num_radial) {
-    if (num_radial < 0 || num_radial > 3) throw std::invalid_argument("num_radial must be in [0, 3]");
-}
-
-static cba_status fit_distortion_impl(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
-                                      const double* v, const double* kmtx5, int32_t num_radial, int32_t n_fixed, const int32_t* fixed_idx,
-                                      const double* fixed_val, int32_t dual, double* coeffs, double* inverse, int32_t* ok,
-                                      double* residuals, double* stage_ms) {
-    return guarded([&] {
-        check_problems(n_problems, offset, x, y, u, v);
-        check_num_radial(num_radial);
-        const int m = num_radial + 2;
-        if (n_fixed < 0) throw std::invalid_argument("n_fixed must be >= 0");
-        if (n_fixed > 0 && !fixed_idx) throw std::invalid_argument("null argument");
-        int mask = 0;
-        double val[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int i = 0; i < n_fixed; ++i) {
-            const int idx = fixed_idx[i];
-            if (idx < 0 || idx >= m) throw std::invalid_argument("Fixed distortion index out of range");
-            if (mask >> idx & 1) continue;  // the first in input order wins
-            mask |= 1 << idx;
-            val[idx] = fixed_val ? fixed_val[i] : 0.0;
-        }
-        if (dual && !inverse) throw std::invalid_argument("dual needs inverse");
-        if (stage_ms)
-            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
-        if (n_problems == 0) return;
-        if (!kmtx5 || !coeffs || !ok) throw std::invalid_argument("null argument");
-        require_device();
-        distortion_fit_gpu(n_problems, offset, x, y, u, v, kmtx5, num_radial, mask, val, dual != 0, coeffs, inverse, ok, residuals, stage_ms,
-                           default_device());
-    });
-}
-
-cba_status cba_fit_distortion_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
-                                    const double* v, const double* kmtx5, int32_t num_radial, int32_t n_fixed, const int32_t* fixed_idx,
-                                    const double* fixed_val, int32_t dual, double* coeffs, double* inverse, int32_t* ok, double* residuals) {
-    return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, n_fixed, fixed_idx, fixed_val, dual, coeffs, inverse, ok,
-                               residuals, nullptr);
-}
-
-cba_status cba_estimate_intrinsics_linear_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
-                                                const double* u, const double* v, const double* bounds_lo5, const double* bounds_hi5,
-                                                int32_t use_skew, double* kmtx5, int32_t* status, int32_t* fallback) {
-    return guarded([&] {
-        check_problems(n_problems, offset, x, y, u, v);
-        if (!bounds_lo5 != !bounds_hi5) throw std::invalid_argument("bounds_lo5 and bounds_hi5 go together");
-        if (n_problems == 0) return;
-        if (!kmtx5 || !status || !fallback) throw std::invalid_argument("null argument");
-        const double dlo[5] = {0.0, 0.0, 0.0, 0.0, -0.01}, dhi[5] = {2000.0, 2000.0, 1280.0, 720.0, 0.01};  // CalibrationBounds{}
-        require_device();
-        intrinsics_linear_gpu(n_problems, offset, x, y, u, v, bounds_lo5 ? bounds_lo5 : dlo, bounds_hi5 ? bounds_hi5 : dhi, use_skew != 0,
-                              kmtx5, status, fallback, default_device());
-    });
-}
-
-static cba_status linear_iterative_impl(int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u,
-                                        const double* v, int32_t num_radial, int32_t max_iterations, int32_t use_skew, double* kmtx5,
-                                        double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback, double* stage_ms) {
-    return guarded([&] {
-        check_problems(n_problems, offset, x, y, u, v);
-        check_num_radial(num_radial);
-        if (max_iterations > CBA_LINEAR_MAX_ITERATIONS) throw std::invalid_argument("max_iterations above CBA_LINEAR_MAX_ITERATIONS");
-        if (stage_ms)
-            for (int k = 0; k < 6; ++k) stage_ms[k] = 0.0;
-        if (n_problems == 0) return;
-        if (!kmtx5 || !coeffs || !status || !iterations || !fallback) throw std::invalid_argument("null argument");
-        require_device();
-        intrinsics_linear_iterative_gpu(n_problems, offset, x, y, u, v, num_radial, std::max(max_iterations, 0), use_skew != 0, kmtx5, coeffs,
-                                        status, iterations, fallback, stage_ms, default_device());
-    });
-}
-
-cba_status cba_estimate_intrinsics_linear_iterative_batch(int32_t n_problems, const int64_t* offset, const double* x, const double* y,
-                                                          const double* u, const double* v, int32_t num_radial, int32_t max_iterations,
-                                                          int32_t use_skew, double* kmtx5, double* coeffs, int32_t* status,
-                                                          int32_t* iterations, int32_t* fallback) {
-    return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status, iterations,
-                                 fallback, nullptr);
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_extrinsic_seed.py): cba_estimate_extrinsic_dlt timing its stages on the device: stage_ms [4] =
-// block poses, camera averages, target averages, total (uploads excluded).  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_estimate_extrinsic_dlt_timed(
-    int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view, const int32_t* blk_cam,
-    const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r, double* r_T_t, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, nullptr, nullptr,
-                              stage_ms);
-}
-
-// Experiment builds only (tools/bench_bundle_seed.py): cba_estimate_bundle_seed timing its stages on the device: stage_ms [6] =
-// block poses, pass 1 + rotation solve, pass 2 + translation solve, candidates + scan, total, scan alone (uploads excluded).
-// Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_estimate_bundle_seed_timed(
-    int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
-    const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, double* g_T_c, int32_t* cam_status,
-    int32_t* cam_pairs, double* b_T_t, int32_t* target_source, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, nullptr, nullptr, nullptr,
-                            g_T_c, cam_status, cam_pairs, b_T_t, target_source, nullptr, nullptr, stage_ms);
-}
-// Experiment builds only (tools/bench_distortion.py): the distortion fit and the iterative estimator timing their stages on the
-// device: stage_ms [6] = moment passes, chunk sums, uploads, tail, residuals, total without uploads.  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_fit_distortion_batch_timed(
-    int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, const double* kmtx5,
-    int32_t num_radial, int32_t dual, double* coeffs, double* inverse, int32_t* ok, double* residuals, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, 0, nullptr, nullptr, dual, coeffs, inverse, ok, residuals,
-                               stage_ms);
-}
-
-__attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_linear_iterative_batch_timed(
-    int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, int32_t num_radial,
-    int32_t max_iterations, int32_t use_skew, double* kmtx5, double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback,
-    double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status, iterations,
-                                 fallback, stage_ms);
-}
-#endif
-
-// ---- camera models (camera.hip, camera_math.hpp) ----------------------------------------------------------------------------
-static void check_camera(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs) {
-    if (camera_model != CBA_CAMERA_PINHOLE_BC && camera_model != CBA_CAMERA_SCHEIMPFLUG) throw std::invalid_argument("bad camera model");
-    if (!intr) throw std::invalid_argument("null argument");
-    if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV))
-        throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
-}
-
-static void check_side(int32_t s) {
-    if (s < 1 || s > CBA_IMAGE_MAX_SIDE) throw std::invalid_argument("image width and height must be in [1, 32768]");
-}
-
-static cba_status camera_project_impl(int32_t camera_model, const double* intr, int64_t n, const double* xyz, double* uv, double* stage_ms) {
-    return guarded([&] {
-        check_camera(camera_model, intr, 0, nullptr);
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (n == 0) return;
-        if (!xyz || !uv) throw std::invalid_argument("null argument");
-        require_device();
-        camera_project_gpu(camera_model, intr, n, xyz, uv, stage_ms, default_device());
-    });
-}
-
-static cba_status camera_unproject_impl(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                                        int64_t n, const double* uv, double* xy, double* stage_ms) {
-    return guarded([&] {
-        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (n == 0) return;
-        if (!uv || !xy) throw std::invalid_argument("null argument");
-        require_device();
-        camera_unproject_gpu(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, n, uv, xy, stage_ms, default_device());
-    });
-}
-
-cba_status cba_camera_project(int32_t camera_model, const double* intr, int64_t n, const double* xyz, double* uv) {
-    return camera_project_impl(camera_model, intr, n, xyz, uv, nullptr);
-}
-
-cba_status cba_camera_unproject(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int64_t n,
-                                const double* uv, double* xy) {
-    return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, nullptr);
-}
-
-static cba_status undistort_map_create_impl(int32_t camera_model, int32_t n_cams, const double* intr, const double* R, const double* new_k5,
-                                            int32_t width, int32_t height, int32_t device, cba_undistort_map** out, double* stage_ms) {
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null argument");
-        *out = nullptr;
-        check_camera(camera_model, intr, 0, nullptr);
-        if (n_cams < 1) throw std::invalid_argument("n_cams must be >= 1");
-        check_side(width);
-        check_side(height);
-        const int ni = camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10;
-        for (int c = 0; c < n_cams; ++c) {
-            const double* k = new_k5 ? new_k5 + 5 * static_cast<size_t>(c) : intr + static_cast<size_t>(c) * ni;
-            if (k[0] == 0.0 || k[1] == 0.0) throw std::invalid_argument("fx' and fy' must not be 0");
-        }
-        require_device(device);
-        *out = reinterpret_cast<cba_undistort_map*>(undistort_map_create(camera_model, n_cams, intr, R, new_k5, width, height, stage_ms, device));
-    });
-}
-
-cba_status cba_undistort_map_create(int32_t camera_model, int32_t n_cams, const double* intr, const double* R, const double* new_k5,
-                                    int32_t width, int32_t height, int32_t device, cba_undistort_map** out) {
-    return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, nullptr);
-}
-
-cba_status cba_undistort_map_fetch(cba_undistort_map* h, float* map_x, float* map_y) {
-    return guarded([&] {
-        if (!h || !map_x || !map_y) throw std::invalid_argument("null argument");
-        undistort_map_fetch(reinterpret_cast<UndistortMap*>(h), map_x, map_y);
-    });
-}
-
-static cba_status undistort_map_apply_impl(cba_undistort_map* h, int32_t n_images, const int32_t* cam, int32_t src_width, int32_t src_height,
-                                           int32_t channels, int32_t dtype, double border, const void* src, void* dst, double* stage_ms) {
-    return guarded([&] {
-        if (!h) throw std::invalid_argument("null argument");
-        if (n_images < 0) throw std::invalid_argument("n_images must be >= 0");
-        check_side(src_width);
-        check_side(src_height);
-        if (channels < 1 || channels > 4) throw std::invalid_argument("channels must be in 1..4");
-        if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
-        if (n_images == 0) return;
-        if (!cam || !src || !dst) throw std::invalid_argument("null argument");
-        UndistortMap* m = reinterpret_cast<UndistortMap*>(h);
-        const int n_cams = undistort_map_cams(m);
-        for (int i = 0; i < n_images; ++i)
-            if (cam[i] < 0 || cam[i] >= n_cams) throw std::invalid_argument("camera index out of range");
-        undistort_map_apply(m, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
-    });
-}
-
-cba_status cba_undistort_map_apply(cba_undistort_map* h, int32_t n_images, const int32_t* cam, int32_t src_width, int32_t src_height,
-                                   int32_t channels, int32_t dtype, double border, const void* src, void* dst) {
-    return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, nullptr);
-}
-
-void cba_undistort_map_destroy(cba_undistort_map* h) { undistort_map_destroy(reinterpret_cast<UndistortMap*>(h)); }
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_camera.py): the camera entry points timing their stages on the device: stage_ms [3] = upload,
-// kernel, download.  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_camera_project_timed(int32_t camera_model, const double* intr, int64_t n,
-                                                                           const double* xyz, double* uv, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return camera_project_impl(camera_model, intr, n, xyz, uv, stage_ms);
-}
-__attribute__((visibility("default"))) cba_status cba_camera_unproject_timed(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs,
-                                                                             const double* inverse_coeffs, int64_t n, const double* uv,
-                                                                             double* xy, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, stage_ms);
-}
-__attribute__((visibility("default"))) cba_status cba_undistort_map_create_timed(int32_t camera_model, int32_t n_cams, const double* intr,
-                                                                                 const double* R, const double* new_k5, int32_t width,
-                                                                                 int32_t height, int32_t device, cba_undistort_map** out,
-                                                                                 double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, stage_ms);
-}
-__attribute__((visibility("default"))) cba_status cba_undistort_map_apply_timed(cba_undistort_map* h, int32_t n_images, const int32_t* cam,
-                                                                                int32_t src_width, int32_t src_height, int32_t channels,
-                                                                                int32_t dtype, double border, const void* src, void* dst,
-                                                                                double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
-}
-#endif
-
-// ---- multi-camera triangulation (triangulate.hip, tri_math.hpp) ---------------------------------------------------------------
-void cba_triangulate_options_default(cba_triangulate_options* o) {
-    if (!o) return;
-    o->max_iterations = 10;
-    o->step_tolerance = 1e-12;
-    o->min_cams = 2;
-    o->max_reproj_px = std::numeric_limits<double>::infinity();
-}
-
-static cba_status triangulate_impl(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs,
-                                   const double* inverse_coeffs, const double* c_T_r, int64_t n, const double* uv,
-                                   const cba_triangulate_options* opts, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
-                                   double* cov6, int32_t* linearisations, double* stage_ms) {
-    return guarded([&] {
-        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
-        if (n_cams < 2 || n_cams > CBA_TRI_MAX_CAMS) throw std::invalid_argument("n_cams must be in [2, 16]");
-        if (!c_T_r || !opts) throw std::invalid_argument("null argument");
-        const int ni = camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10;
-        for (int c = 0; c < n_cams; ++c)
-            if (intr[static_cast<size_t>(c) * ni] == 0.0 || intr[static_cast<size_t>(c) * ni + 1] == 0.0)
-                throw std::invalid_argument("fx and fy must not be 0");
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (opts->max_iterations < 0) throw std::invalid_argument("max_iterations must be >= 0");
-        if (!(opts->step_tolerance >= 0.0)) throw std::invalid_argument("step_tolerance must be >= 0");
-        if (!(opts->max_reproj_px > 0.0)) throw std::invalid_argument("max_reproj_px must be > 0");
-        if (n == 0) return;
-        if (!uv || !xyz || !status) throw std::invalid_argument("null argument");
-        require_device();
-        triangulate_gpu(camera_model, n_cams, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, c_T_r, n, uv, *opts, xyz, rms_px,
-                        used_mask, status, cov6, linearisations, stage_ms, default_device());
-    });
-}
-
-cba_status cba_triangulate(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                           const double* c_T_r, int64_t n, const double* uv, const cba_triangulate_options* opts, double* xyz,
-                           double* rms_px, uint32_t* used_mask, int32_t* status, double* cov6) {
-    return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px, used_mask, status,
-                            cov6, nullptr, nullptr);
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_triangulate.py): cba_triangulate timing its stages on the device (stage_ms [3] = upload,
-// kernel, download) and returning each point's number of linearisations.  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_triangulate_timed(int32_t camera_model, int32_t n_cams, const double* intr,
-                                                                        int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                                                                        const double* c_T_r, int64_t n, const double* uv,
-                                                                        const cba_triangulate_options* opts, double* xyz, double* rms_px,
-                                                                        uint32_t* used_mask, int32_t* status, double* cov6,
-                                                                        int32_t* linearisations, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px, used_mask, status,
-                            cov6, linearisations, stage_ms);
-}
-#endif
-
-// ---- laser profile scanning (laser_scan.hip, laser_scan_math.hpp) ---------------------------------------------------------------
-void cba_laser_scan_options_default(cba_laser_scan_options* o) {
-    if (!o) return;
-    o->axis = 0;
-    o->roi_begin = 0;
-    o->roi_end = 0;
-    o->half_window = 5;
-    o->floor_level = 0.0;
-    o->min_peak = 1.0;
-}
-
-static void check_laser_plane(const double* plane) {
-    if (!plane) throw std::invalid_argument("null argument");
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(plane[k])) throw std::invalid_argument("the plane must be finite");
-    if (plane[0] == 0.0 && plane[1] == 0.0 && plane[2] == 0.0) throw std::invalid_argument("the plane normal must not be zero");
-}
-
-cba_status cba_laser_points(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                            const double plane[4], int64_t n, const double* uv, int32_t n_frames, const int64_t* frame_offset,
-                            const double* frame_pose7, double* xyz, double* plane_xy) {
-    return guarded([&] {
-        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
-        check_laser_plane(plane);
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (n_frames < 0) throw std::invalid_argument("n_frames must be >= 0");
-        if (frame_pose7 && !frame_offset && n_frames != 1) throw std::invalid_argument("frame_pose7 without frame_offset needs n_frames == 1");
-        if (frame_offset) {
-            check_offsets(frame_offset, n_frames, "frame ", OFF_FROM_ZERO);
-            if (frame_offset[n_frames] != n) throw std::invalid_argument("frame offsets must end at n");
-        }
-        if (n == 0) return;
-        if (!uv || !xyz) throw std::invalid_argument("null argument");
-        require_device();
-        const int64_t single[2] = {0, n};  // one posed frame without a table
-        laser_points_gpu(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, plane, n, uv, n_frames,
-                         frame_pose7 ? (frame_offset ? frame_offset : single) : nullptr, frame_pose7, xyz, plane_xy, default_device());
-    });
-}
-
-cba_status cba_laser_scanner_create(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
-                                    const double plane[4], int32_t width, int32_t height, int32_t max_frames,
-                                    const cba_laser_scan_options* opts, int32_t device, cba_laser_scanner** out) {
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null argument");
-        *out = nullptr;
-        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
-        check_laser_plane(plane);
-        if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        if (max_frames < 1) throw std::invalid_argument("max_frames must be >= 1");
-        if (opts->axis != 0 && opts->axis != 1) throw std::invalid_argument("axis must be 0 or 1");
-        const int32_t side = opts->axis == 0 ? height : width;
-        if (!(opts->roi_begin == 0 && opts->roi_end == 0) && (opts->roi_begin < 0 || opts->roi_end > side || opts->roi_begin >= opts->roi_end))
-            throw std::invalid_argument("the ROI must be a non-empty range inside the image");
-        if (opts->half_window < 0) throw std::invalid_argument("half_window must be >= 0");
-        if (!std::isfinite(opts->floor_level) || !std::isfinite(opts->min_peak))
-            throw std::invalid_argument("floor_level and min_peak must be finite");
-        if (static_cast<int64_t>(max_frames) * std::max(width, height) > 0x7fffffff) throw std::invalid_argument("max_frames is too large");
-        require_device(device);
-        *out = reinterpret_cast<cba_laser_scanner*>(laser_scanner_create(camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0,
-                                                                          inverse_coeffs, plane, width, height, max_frames, *opts, device));
-    });
-}
-
-static cba_status laser_scanner_process_impl(cba_laser_scanner* h, int32_t n_frames, int32_t dtype, const void* images,
-                                             const double* frame_pose7, double* centre, double* amplitude, double* width_px, double* xyz,
-                                             double* stage_ms) {
-    return guarded([&] {
-        if (!h) throw std::invalid_argument("null argument");
-        LaserScanner* sc = reinterpret_cast<LaserScanner*>(h);
-        if (n_frames < 0 || n_frames > laser_scanner_max_frames(sc)) throw std::invalid_argument("n_frames must be in [0, max_frames]");
-        if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
-        if (n_frames == 0) return;
-        if (!images) throw std::invalid_argument("null argument");
-        laser_scanner_process(sc, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
-    });
-}
-
-cba_status cba_laser_scanner_process(cba_laser_scanner* h, int32_t n_frames, int32_t dtype, const void* images, const double* frame_pose7,
-                                     double* centre, double* amplitude, double* width_px, double* xyz) {
-    return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, nullptr);
-}
-
-void cba_laser_scanner_destroy(cba_laser_scanner* h) { laser_scanner_destroy(reinterpret_cast<LaserScanner*>(h)); }
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_laser_scan.py): cba_laser_scanner_process timing its stages on the device (stage_ms [3] = upload,
-// kernel, download).  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_laser_scanner_process_timed(cba_laser_scanner* h, int32_t n_frames, int32_t dtype,
-                                                                                  const void* images, const double* frame_pose7,
-                                                                                  double* centre, double* amplitude, double* width_px,
-                                                                                  double* xyz, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
-}
-#endif
-
-// ---- stereo depth (stereo_match.hip, stereo_math.hpp) ---------------------------------------------------------------------------
-void cba_stereo_match_options_default(cba_stereo_match_options* o) {
-    if (!o) return;
-    o->min_disparity = 0;
-    o->num_disparities = 64;
-    o->half_window = 4;
-    o->uniqueness_percent = 10;
-    o->lr_max_diff = 1;
-    o->subpixel = 1;
-}
-
-cba_status cba_stereo_rectify(int32_t camera_model, const double* intr, const double* c_T_r, int32_t width, int32_t height,
-                              const cba_stereo_rectify_options* opts, double* R, double* new_k5, double* baseline, double* r_T_rect) {
-    return guarded([&] {
-        check_camera(camera_model, intr, 0, nullptr);
-        if (!c_T_r || !opts || !R || !new_k5 || !baseline || !r_T_rect) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        const char* err = stereo_rectify(intr, camera_model == CBA_CAMERA_SCHEIMPFLUG ? 12 : 10, c_T_r, width, height, opts->focal, opts->cx,
-                                         opts->cy, R, new_k5, baseline, r_T_rect);
-        if (err) throw std::invalid_argument(err);
-    });
-}
-
-static void check_stereo_geometry(const cba_stereo_geometry* g, const double* pose7) {
-    if (!std::isfinite(g->focal) || !std::isfinite(g->cx) || !std::isfinite(g->cy) || !std::isfinite(g->baseline))
-        throw std::invalid_argument("the stereo geometry must be finite");
-    if (!(g->focal > 0.0) || !(g->baseline > 0.0)) throw std::invalid_argument("focal and baseline must be > 0");
-    if (pose7)
-        for (int k = 0; k < 7; ++k)
-            if (!std::isfinite(pose7[k])) throw std::invalid_argument("the pose must be finite");
-}
-
-cba_status cba_stereo_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_stereo_match_options* opts,
-                                     const cba_stereo_geometry* geometry, const double* pose7, int32_t device, cba_stereo_matcher** out) {
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null argument");
-        *out = nullptr;
-        if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        if (max_pairs < 1) throw std::invalid_argument("max_pairs must be >= 1");
-        if (static_cast<int64_t>(max_pairs) * width * height > 0x7fffffff) throw std::invalid_argument("max_pairs is too large");
-        if (opts->min_disparity < -32768 || opts->min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
-        if (opts->num_disparities < 1 || opts->num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
-        if (opts->half_window < 1 || opts->half_window > 10) throw std::invalid_argument("half_window must be in 1..10");
-        if (opts->uniqueness_percent < 0 || opts->uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
-        if (opts->lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
-        if (opts->subpixel != 0 && opts->subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
-        if (pose7 && !geometry) throw std::invalid_argument("a pose needs a geometry");
-        if (geometry) check_stereo_geometry(geometry, pose7);
-        require_device(device);
-        *out = reinterpret_cast<cba_stereo_matcher*>(stereo_matcher_create(width, height, max_pairs, *opts, geometry, pose7, device));
-    });
-}
-
-static cba_status stereo_matcher_process_impl(cba_stereo_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right,
-                                              float* disparity, int32_t* cost, float* xyz, double* stage_ms) {
-    return guarded([&] {
-        if (!h) throw std::invalid_argument("null argument");
-        StereoMatcher* m = reinterpret_cast<StereoMatcher*>(h);
-        if (n_pairs < 0 || n_pairs > stereo_matcher_max_pairs(m)) throw std::invalid_argument("n_pairs must be in [0, max_pairs]");
-        if (xyz && !stereo_matcher_has_geometry(m)) throw std::invalid_argument("xyz needs a matcher created with a geometry");
-        if (n_pairs == 0) return;
-        if (!left || !right) throw std::invalid_argument("null argument");
-        stereo_matcher_process(m, n_pairs, left, right, disparity, cost, xyz, stage_ms);
-    });
-}
-
-cba_status cba_stereo_matcher_process(cba_stereo_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right, float* disparity,
-                                      int32_t* cost, float* xyz) {
-    return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, nullptr);
-}
-
-void cba_stereo_matcher_destroy(cba_stereo_matcher* h) { stereo_matcher_destroy(reinterpret_cast<StereoMatcher*>(h)); }
-
-cba_status cba_stereo_points(const cba_stereo_geometry* geometry, const double* pose7, int64_t n, const double* uvd, double* xyz) {
-    return guarded([&] {
-        if (!geometry) throw std::invalid_argument("null argument");
-        check_stereo_geometry(geometry, pose7);
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (n == 0) return;
-        if (!uvd || !xyz) throw std::invalid_argument("null argument");
-        require_device();
-        stereo_points_gpu(*geometry, pose7, n, uvd, xyz, default_device());
-    });
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_stereo.py): cba_stereo_matcher_process timing its stages on the device (stage_ms [3] = upload,
-// kernels, download).  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_stereo_matcher_process_timed(cba_stereo_matcher* h, int32_t n_pairs,
-                                                                                   const uint8_t* left, const uint8_t* right,
-                                                                                   float* disparity, int32_t* cost, float* xyz,
-                                                                                   double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
-}
-#endif
-
-// ---- chessboard detection (corner_detect.hip, corner_math.hpp, corner_grid.hpp) ---------------------------------------------------
-void cba_corner_options_default(cba_corner_options* o) {
-    if (!o) return;
-    o->min_response = 400;
-    o->nms_radius = 3;
-    o->cog_radius = 2;
-    o->refine = CBA_CORNER_REFINE_GRADIENT;
-    o->refine_half_window = 5;
-    o->refine_iterations = 5;
-}
-
-cba_status cba_corner_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, const cba_corner_options* opts,
-                                      int32_t device, cba_corner_detector** out) {
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("null argument");
-        *out = nullptr;
-        if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        if (width < 11 || height < 11) throw std::invalid_argument("width and height must be >= 11");
-        if (max_images < 1) throw std::invalid_argument("max_images must be >= 1");
-        if (static_cast<int64_t>(max_images) * width * height > 0x7fffffff) throw std::invalid_argument("max_images is too large");
-        if (max_corners < 1 || static_cast<int64_t>(max_images) * max_corners > (1 << 28))
-            throw std::invalid_argument("max_corners must be >= 1 and max_images max_corners <= 2^28");
-        if (opts->min_response < 1 || opts->min_response > 10200) throw std::invalid_argument("min_response must be in 1..10200");
-        if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
-        if (opts->cog_radius < 1 || opts->cog_radius > 5) throw std::invalid_argument("cog_radius must be in 1..5");
-        if (opts->refine < CBA_CORNER_REFINE_NONE || opts->refine > CBA_CORNER_REFINE_GRADIENT)
-            throw std::invalid_argument("refine must be NONE, COG or GRADIENT");
-        if (opts->refine_half_window < 1 || opts->refine_half_window > 10) throw std::invalid_argument("refine_half_window must be in 1..10");
-        if (opts->refine_iterations < 1 || opts->refine_iterations > 100) throw std::invalid_argument("refine_iterations must be in 1..100");
-        require_device(device);
-        *out = reinterpret_cast<cba_corner_detector*>(corner_detector_create(width, height, max_images, max_corners, *opts, device));
-    });
-}
-
-static cba_status corner_detector_process_impl(cba_corner_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
-                                               int32_t* out_status, double* out_xy, double* out_angle, int32_t* out_response,
-                                               int32_t* out_flags, double* stage_ms) {
-    return guarded([&] {
-        if (!h) throw std::invalid_argument("null argument");
-        CornerDetector* d = reinterpret_cast<CornerDetector*>(h);
-        if (n_images < 0 || n_images > corner_detector_max_images(d)) throw std::invalid_argument("n_images must be in [0, max_images]");
-        if (n_images == 0) return;
-        if (!images) throw std::invalid_argument("null argument");
-        corner_detector_process(d, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
-    });
-}
-
-cba_status cba_corner_detector_process(cba_corner_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
-                                       int32_t* out_status, double* out_xy, double* out_angle, int32_t* out_response, int32_t* out_flags) {
-    return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, nullptr);
-}
-
-void cba_corner_detector_destroy(cba_corner_detector* h) { corner_detector_destroy(reinterpret_cast<CornerDetector*>(h)); }
-
-cba_status cba_chessboard_order(int32_t n, const double* xy, const double* angle, int32_t rows, int32_t cols, int32_t* out_index) {
-    return guarded([&] {
-        if (!out_index) throw std::invalid_argument("null argument");
-        if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (rows < 2 || cols < 2 || static_cast<int64_t>(rows) * cols > 65536) throw std::invalid_argument("rows and cols must be >= 2, rows cols <= 65536");
-        if (n > 0 && (!xy || !angle)) throw std::invalid_argument("null argument");
-        if (n > 65536) throw std::invalid_argument("n must be <= 65536");
-        for (int32_t i = 0; i < n; ++i)
-            if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1]) || !std::isfinite(angle[i]))
-                throw std::invalid_argument("corners must be finite");
-        if (!chessboard_order(n, xy, angle, rows, cols, out_index))
-            for (int32_t i = 0; i < rows * cols; ++i) out_index[i] = -1;  // not found
-    });
-}
-
-#ifdef CBA_EXPERIMENTS
-// Experiment builds only (tools/bench_corners.py): cba_corner_detector_process timing its stages on the device (stage_ms [5] = upload,
-// response, peaks, refine, download).  Not part of calibba.h.
-__attribute__((visibility("default"))) cba_status cba_corner_detector_process_timed(cba_corner_detector* h, int32_t n_images,
-                                                                                    const uint8_t* images, int32_t* out_count,
-                                                                                    int32_t* out_status, double* out_xy, double* out_angle,
-                                                                                    int32_t* out_response, int32_t* out_flags,
-                                                                                    double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
-}
-#endif
 
 }  // extern "C"

@@ -18,9 +18,10 @@
 // The host halves atan2 of the angle sums after the download.  No scratch, no dynamically indexed private array.
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "corner_math.hpp"
 
 namespace cba {
@@ -233,9 +234,8 @@ __global__ __launch_bounds__(CRN_BLOCK) void k_corner_refine(CornerRefineArgs a)
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
 // The detector: options fixed at create, every buffer (the host staging of the angle sums included) sized for max_images there.  Every
 // call ends with its stream synchronised.
-struct CornerDetector {
-    int device = 0;
-    StreamLease lease;
+struct CornerDetector : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
     cba_corner_options opts;
     int W = 0, H = 0, max_images = 0, max_corners = 0;
     int tiles_x = 0, tiles_y = 0, strips = 0;
@@ -246,11 +246,10 @@ struct CornerDetector {
     std::vector<double> h_sums;
     std::vector<int32_t> h_count;
 };
+static_assert(!std::is_copy_constructible_v<CornerDetector> && !std::is_copy_assignable_v<CornerDetector>, "a handle owns its stream and buffers");
 
 CornerDetector* corner_detector_create(int W, int H, int max_images, int max_corners, const cba_corner_options& o, int device) {
-    CBA_HIP(hipSetDevice(device));
-    auto h = std::make_unique<CornerDetector>();
-    h->device = device;
+    auto h = std::make_unique<CornerDetector>(device);
     h->opts = o;
     h->W = W; h->H = H; h->max_images = max_images; h->max_corners = max_corners;
     h->tiles_x = (W + CRN_TX - 1) / CRN_TX;
@@ -286,8 +285,7 @@ int corner_detector_max_images(const CornerDetector* h) { return h->max_images; 
 // stage_ms [5] (experiment builds): upload, response, peaks, refine, download
 void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
                              double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms) {
-    CBA_HIP(hipSetDevice(h->device));
-    const hipStream_t s = h->lease;
+    const hipStream_t s = h->begin();
     const size_t px = static_cast<size_t>(n_images) * h->W * h->H, slots = static_cast<size_t>(n_images) * h->max_corners;
     StageTimer<6> tm(s, stage_ms != nullptr);
     tm.mark(0);
@@ -313,7 +311,7 @@ void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* ima
     CornerRefineArgs fa{h->img.p, h->resp.p, h->W, h->H, static_cast<int>(slots), h->max_corners, h->opts.cog_radius, h->opts.refine,
                         h->opts.refine_half_window, h->opts.refine_iterations, h->count.p, h->peak_px.p, h->wt.p, h->trig.p, h->xy.p,
                         h->sums.p, h->response.p, h->flags.p};
-    const int fgrid = static_cast<int>(std::max<size_t>(1, std::min<size_t>(CRN_GRID, (slots + CRN_BLOCK - 1) / CRN_BLOCK)));
+    const int fgrid = launch_grid(static_cast<int64_t>(slots), CRN_BLOCK, CRN_GRID);
     hipLaunchKernelGGL(k_corner_refine, dim3(fgrid), dim3(CRN_BLOCK), 0, s, fa);
     CBA_HIP(hipGetLastError());
     tm.mark(4);
@@ -334,14 +332,9 @@ void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* ima
             out_angle[i] = c < kept ? corner_angle(&h->h_sums[2 * i]) : static_cast<double>(NAN);
         }
     }
-    if (stage_ms)
-        for (int k = 0; k < 5; ++k) stage_ms[k] = tm.ms(k, k + 1);
+    tm.report(stage_ms);
 }
 
-void corner_detector_destroy(CornerDetector* h) noexcept {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    delete h;
-}
+void corner_detector_destroy(CornerDetector* h) noexcept { destroy_handle(h); }
 
 }  // namespace cba

@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "distortion_fit_math.hpp"
 #include "wave_reduce.hpp"
 

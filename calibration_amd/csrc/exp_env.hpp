@@ -1,4 +1,4 @@
-// exp_env.hpp - experiment knobs (see the comment at engine.hpp's include of this file): environment variables that are read only
+// exp_env.hpp - experiment knobs (see the comment on the environment switches in hip_glue.hpp, which includes this file): environment variables that are read only
 // by a library built with -DCBA_EXPERIMENTS (make EXPERIMENTS=1), never by the shipped one.
 #pragma once
 #include <cstdlib>

@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "block_pose.hpp"
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "extrinsic_dlt_math.hpp"
 
 namespace cba {
@@ -82,8 +82,7 @@ __global__ __launch_bounds__(EXT_CHUNK) void k_ext_target_avg(int n_views, int n
 void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const int32_t* table,
                        const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r,
                        double* r_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         StageTimer<4> tm(stream, stage_ms != nullptr);  // device events between the stages
@@ -111,12 +110,8 @@ void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk
         if (blk_pose) dP.download(blk_pose, 7 * static_cast<size_t>(n_blocks), stream);
         if (blk_ok) dok.download(blk_ok, n_blocks, stream);
         CBA_HIP(hipStreamSynchronize(stream));
-        if (stage_ms) {  // stage_ms [4]: block poses, camera averages, target averages, total
-            stage_ms[0] = tm.ms(0, 1);
-            stage_ms[1] = tm.ms(1, 2);
-            stage_ms[2] = tm.ms(2, 3);
-            stage_ms[3] = tm.ms(0, 3);
-        }
+        tm.report(stage_ms);  // stage_ms [4]: block poses, camera averages, target averages ...
+        if (stage_ms) stage_ms[3] = tm.ms(0, 3);  // ... and the total
     }
 }
 

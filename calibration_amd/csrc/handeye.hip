@@ -9,7 +9,7 @@
 #include <rccl/rccl.h>
 
 #include "axxb_pairs.hpp"
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "handeye_core.hpp"
 #include "seed_math.hpp"
 

@@ -23,7 +23,7 @@
 #include <cmath>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "hom_ransac_math.hpp"
 
 namespace cba {
@@ -350,8 +350,7 @@ struct HrViews {
 void homography_ransac_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
                              const cba_ransac_options* o, double* h9, int32_t* success, int32_t* inlier_count, double* symmetric_rms,
                              uint8_t* inlier_mask, int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         HrTimer tm(stream, false);
@@ -371,8 +370,7 @@ void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const doub
                              const cba_ransac_options* o, const double* bounds_lo5, const double* bounds_hi5, int32_t* success,
                              double* kmtx5, int32_t* sanitized, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
                              int32_t* pose_ok, uint8_t* inlier_mask, double* stage_ms, int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     double kst[KS_SIZE];
     {

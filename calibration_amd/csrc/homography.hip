@@ -9,7 +9,7 @@
 #include <cmath>
 #include <cstdio>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "hom_math.hpp"
 
 namespace cba {
@@ -43,8 +43,7 @@ void homography_batch(int n_views, const int64_t* view_offset, const double* X, 
         if (n < 4) throw std::invalid_argument("At least 4 correspondences are required.");  // homography.cpp:146-148
         if (n > 0x7fffffff) throw std::invalid_argument("view too large");
     }
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         ObsSoA d;

@@ -25,7 +25,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "laser_scan_math.hpp"
 #include "wave_reduce.hpp"
 
@@ -310,10 +310,6 @@ __global__ __launch_bounds__(LSC_BLOCK) void k_laser_points(int64_t n, const dou
 }
 
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
-static int lsc_grid(int64_t items, int per_block) {
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(LSC_GRID, (items + per_block - 1) / per_block)));
-}
-
 // frame_offset / frame_pose7: both or neither (the caller supplies [0, n] for a single posed frame)
 void laser_points_gpu(int model, const double* intr, int n_inv, const double* inv, const double* plane, int64_t n, const double* uv,
                       int n_frames, const int64_t* frame_offset, const double* frame_pose7, double* xyz, double* plane_xy, int device) {
@@ -324,8 +320,7 @@ void laser_points_gpu(int model, const double* intr, int n_inv, const double* in
         hrt.resize(12 * static_cast<size_t>(n_frames));
         for (int f = 0; f < n_frames; ++f) laser_pose_rt(frame_pose7 + 7 * static_cast<size_t>(f), hrt.data() + 12 * static_cast<size_t>(f));
     }
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t s = lease;
     const size_t np = static_cast<size_t>(n);
     DevBuf<double> duv, dxyz, dpxy, drt;
@@ -338,7 +333,7 @@ void laser_points_gpu(int model, const double* intr, int n_inv, const double* in
         drt.assign(hrt.data(), hrt.size(), s);
         doff.assign(frame_offset, static_cast<size_t>(n_frames) + 1, s);
     }
-    hipLaunchKernelGGL(k_laser_points, dim3(lsc_grid(n, LSC_BLOCK)), dim3(LSC_BLOCK), 0, s, n, duv.p, n_frames, doff.p, drt.p, dxyz.p, dpxy.p, g);
+    hipLaunchKernelGGL(k_laser_points, dim3(launch_grid(n, LSC_BLOCK, LSC_GRID)), dim3(LSC_BLOCK), 0, s, n, duv.p, n_frames, doff.p, drt.p, dxyz.p, dpxy.p, g);
     CBA_HIP(hipGetLastError());
     dxyz.download(xyz, 3 * np, s);
     if (plane_xy) dpxy.download(plane_xy, 2 * np, s);
@@ -347,9 +342,8 @@ void laser_points_gpu(int model, const double* intr, int n_inv, const double* in
 
 // The scanner: camera, plane and options fixed at create, every buffer sized for max_frames there.  Every call ends with its stream
 // synchronised.
-struct LaserScanner {
-    int device = 0;
-    StreamLease lease;
+struct LaserScanner : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
     LaserGeom geom;
     int axis = 0, W = 0, H = 0, max_frames = 0, pb = 0, pe = 0, hw = 0;
     double floor_level = 0.0, min_peak = 0.0;
@@ -359,12 +353,11 @@ struct LaserScanner {
     std::vector<double> h_rt;
     int n_lines() const { return axis == 0 ? W : H; }
 };
+static_assert(!std::is_copy_constructible_v<LaserScanner> && !std::is_copy_assignable_v<LaserScanner>, "a handle owns its stream and buffers");
 
 LaserScanner* laser_scanner_create(int model, const double* intr, int n_inv, const double* inv, const double* plane, int W, int H,
                                    int max_frames, const cba_laser_scan_options& o, int device) {
-    CBA_HIP(hipSetDevice(device));
-    auto h = std::make_unique<LaserScanner>();
-    h->device = device;
+    auto h = std::make_unique<LaserScanner>(device);
     laser_fill_geom(model, intr, n_inv, inv, plane, &h->geom);
     h->axis = o.axis; h->W = W; h->H = H; h->max_frames = max_frames;
     const int side = o.axis == 0 ? H : W;
@@ -388,7 +381,7 @@ template <typename T>
 static void lsc_launch(const LaserScanner& h, const LaserScanArgs& a, hipStream_t s) {
     constexpr int WIDE = 16 / static_cast<int>(sizeof(T)), NARROW = sizeof(T) == 1 ? 4 : 1;
     if (h.axis == 1) {
-        hipLaunchKernelGGL(k_laser_scan_rows<T>, dim3(lsc_grid(static_cast<int64_t>(a.n_frames) * a.H, LSC_WAVES)), dim3(LSC_BLOCK), 0, s, a,
+        hipLaunchKernelGGL(k_laser_scan_rows<T>, dim3(launch_grid(static_cast<int64_t>(a.n_frames) * a.H, LSC_WAVES, LSC_GRID)), dim3(LSC_BLOCK), 0, s, a,
                            h.geom);
     } else if (a.W % WIDE == 0) {  // every row starts on a 16-byte boundary
         const int bpf = (a.W + 64 * WIDE - 1) / (64 * WIDE);
@@ -402,8 +395,7 @@ static void lsc_launch(const LaserScanner& h, const LaserScanArgs& a, hipStream_
 // stage_ms [3] (experiment builds): upload, kernel, download
 void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void* images, const double* frame_pose7, double* centre,
                            double* amplitude, double* width_px, double* xyz, double* stage_ms) {
-    CBA_HIP(hipSetDevice(h->device));
-    const hipStream_t s = h->lease;
+    const hipStream_t s = h->begin();
     const size_t esz = dtype == CBA_DTYPE_F32 ? 4 : 1;
     const size_t L = static_cast<size_t>(n_frames) * h->n_lines(), Lmax = static_cast<size_t>(std::max(h->max_frames, 1)) * h->n_lines();
     StageTimer<4> tm(s, stage_ms != nullptr);
@@ -436,17 +428,9 @@ void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void*
     if (xyz) h->out.download(xyz, 3 * L, s, 3 * Lmax);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    if (stage_ms) {
-        stage_ms[0] = tm.ms(0, 1);
-        stage_ms[1] = tm.ms(1, 2);
-        stage_ms[2] = tm.ms(2, 3);
-    }
+    tm.report(stage_ms);
 }
 
-void laser_scanner_destroy(LaserScanner* h) noexcept {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    delete h;
-}
+void laser_scanner_destroy(LaserScanner* h) noexcept { destroy_handle(h); }
 
 }  // namespace cba

@@ -25,15 +25,10 @@ struct LaserGeom {
     double plane[4];
     double Hp[9];
 };
+static_assert(sizeof(LaserGeom) == 624, "LaserGeom is a kernel argument: its layout is fixed");
 
 CBA_HD void laser_fill_geom(int model, const double* intr, int n_inv, const double* inv, const double* plane, LaserGeom* g) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
-    g->cam.model = model;
-    g->cam.n_inv = inv ? n_inv : 0;
-    for (int j = 0; j < 12; ++j) g->cam.intr[j] = j < ni ? intr[j] : 0.0;
-    for (int j = 0; j < LS_MAX_INV; ++j) g->cam.inv[j] = j < g->cam.n_inv ? inv[j] : 0.0;
-    for (int j = 0; j < SD_SIZE; ++j) g->cam.sd[j] = 0.0;
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(g->cam.intr, g->cam.sd);
+    ls_fill_camera(model, intr, n_inv, inv, &g->cam);
     for (int j = 0; j < 4; ++j) g->plane[j] = plane[j];
     ls_plane_homography(plane, g->Hp);
 }

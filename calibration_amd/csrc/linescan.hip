@@ -20,7 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "linescan_math.hpp"
 
 namespace cba {
@@ -329,8 +329,6 @@ __global__ void k_ls_pick(int H, const int32_t* __restrict__ hstate, const doubl
 // ---- host glue -----------------------------------------------------------------------------------------------------------
 namespace {
 
-int grid_for(int64_t n) { return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(LS_GRID, (n + LS_BLOCK - 1) / LS_BLOCK))); }
-
 // Optional stage timing (cba_calibrate_laser_plane_timed): events recorded between the stages of one call.
 using LsTimer = StageTimer<LS_NSTAGE_MARKS>;
 
@@ -342,7 +340,7 @@ struct PlaneFitter {
 
     void run(hipStream_t stream, int64_t n_cap, const int64_t* dn, const double* px, const double* py, const double* pz,
              const cba_plane_fit_options& o, uint8_t* cmask, LsTimer& tm) {
-        const int G = grid_for(n_cap);
+        const int G = launch_grid(n_cap, LS_BLOCK, LS_GRID);
         part.alloc(6 * static_cast<size_t>(G));
         st.alloc(ST_SIZE);
         st.zero(stream);
@@ -430,23 +428,12 @@ void timings(const LsTimer& t, double* ms) {
 
 }  // namespace
 
-static LsCamera make_ls_camera(int model, const double* intr, int n_inv, const double* inv) {
-    LsCamera c{};
-    c.model = model;
-    c.n_inv = inv ? n_inv : 0;
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
-    for (int k = 0; k < ni; ++k) c.intr[k] = intr[k];
-    for (int k = 0; k < c.n_inv; ++k) c.inv[k] = inv[k];
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(c.intr, c.sd);
-    return c;
-}
-
 void laser_plane_calibrate(int model, const double* intr, int n_inv, const double* inv, int n_views, const int64_t* toff, const double* X, const double* Y, const double* u,
                            const double* v, const int64_t* loff, const double* lu, const double* lv, const cba_plane_fit_options& o,
                            cba_laser_plane_result* res, double* points_xyz, uint8_t* inlier_mask, double* stage_ms, int device) {
-    const LsCamera cam = make_ls_camera(model, intr, n_inv, inv);
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    LsCamera cam;
+    ls_fill_camera(model, intr, n_inv, inv, &cam);
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     const int64_t n_t = toff[n_views], n_l = loff[n_views];
     std::vector<int32_t> ok(n_views);
@@ -476,7 +463,7 @@ void laser_plane_calibrate(int model, const double* intr, int n_inv, const doubl
         CBA_HIP(hipGetLastError());
         tm.mark(MK_V1);
         if (n_l > 0) {
-            hipLaunchKernelGGL(k_ls_points, dim3(grid_for(n_l) * 2), dim3(LS_BLOCK), 0, stream, n_views, n_l, dloff.p, dlu.p, dlv.p, cam,
+            hipLaunchKernelGGL(k_ls_points, dim3(launch_grid(n_l, LS_BLOCK, LS_GRID) * 2), dim3(LS_BLOCK), 0, stream, n_views, n_l, dloff.p, dlu.p, dlv.p, cam,
                                dgeo.p, dok.p, dcoff.p, px.p, py.p, pz.p, points_xyz ? dxyz.p : nullptr);
             CBA_HIP(hipGetLastError());
         }
@@ -516,8 +503,7 @@ void laser_plane_calibrate(int model, const double* intr, int n_inv, const doubl
 
 void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, double* plane, double* rms, int64_t* count, uint8_t* mask,
                int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     double st[ST_SIZE];
     {
@@ -528,7 +514,7 @@ void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, dou
         if (mask) dmask.alloc(n);
         dxyz.assign(xyz, 3 * static_cast<size_t>(n), stream);
         dn.assign(&n, 1, stream);
-        hipLaunchKernelGGL(k_ls_aos_to_soa, dim3(grid_for(n)), dim3(LS_BLOCK), 0, stream, n, dxyz.p, px.p, py.p, pz.p);
+        hipLaunchKernelGGL(k_ls_aos_to_soa, dim3(launch_grid(n, LS_BLOCK, LS_GRID)), dim3(LS_BLOCK), 0, stream, n, dxyz.p, px.p, py.p, pz.p);
         CBA_HIP(hipGetLastError());
         LsTimer tm(stream, false);
         PlaneFitter fit;

@@ -88,6 +88,24 @@ struct LsCamera {
     double inv[LS_MAX_INV];
     double sd[SD_SIZE];
 };
+static_assert(sizeof(LsCamera) == 520, "LsCamera is a kernel argument: its layout is fixed");
+
+constexpr int cam_intr_size(int model) { return model == CAM_SCHEIMPFLUG ? 12 : 10; }
+
+// The intrinsics of one camera as the kernels take them: padded with zeros to 12, and the Scheimpflug constants (zero for the pinhole)
+CBA_HD void ls_fill_intr(int model, const double* intr, double* out12, double* sd) {
+    for (int k = 0; k < 12; ++k) out12[k] = k < cam_intr_size(model) ? intr[k] : 0.0;
+    for (int k = 0; k < SD_SIZE; ++k) sd[k] = 0.0;
+    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(out12, sd);
+}
+
+// inv: n_inv inverse coefficients or NULL (then n_inv is 0); every entry past the ones given is zero
+CBA_HD void ls_fill_camera(int model, const double* intr, int n_inv, const double* inv, LsCamera* c) {
+    c->model = model;
+    c->n_inv = inv ? n_inv : 0;
+    ls_fill_intr(model, intr, c->intr, c->sd);
+    for (int k = 0; k < LS_MAX_INV; ++k) c->inv[k] = k < c->n_inv ? inv[k] : 0.0;
+}
 
 CBA_HD void ls_unproject(const LsCamera& cam, double u, double v, double* x, double* y) {
     if (cam.model == CAM_SCHEIMPFLUG)

@@ -1,0 +1,126 @@
+// pipelines.hpp — the entry points of the one-shot solvers and the batched pipelines, as capi.cpp and capi_pipelines.cpp call them.
+// Each is defined in the .hip file its comment names.
+#pragma once
+#include "../../include/calibba.h"
+#include "hip_glue.hpp"
+
+namespace cba {
+
+void planar_pose_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                       const double* kmtx5, int num_radial, double* pose7, const cba_options* o, cba_summary* summaries,
+                       double* distortion, double* rms, double* cov, int device);
+void homography_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                      double* h9, const cba_options* o, cba_summary* summaries, double* cov64, int device);
+void semidlt_solve(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                   double* kappa5, double* poses7, int num_radial, const double* bounds_lo, const double* bounds_hi,
+                   const int32_t* fixed_idx, const double* fixed_val, int n_fixed, const cba_options* o, cba_summary* summary,
+                   double* distortion, double* view_errors, double* cov, int device);
+void semidlt_solve_sharded(int n_local, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                           int n_views_total, int first_view, double* kappa5, double* poses7, int num_radial, const double* bounds_lo,
+                           const double* bounds_hi, const int32_t* fixed_idx, const double* fixed_val, int n_fixed, const cba_options* o,
+                           cba_summary* summary, double* distortion, double* view_errors, double* cov, int device, cba_allreduce_fn fn,
+                           void* user, void* rccl_comm);
+void dlt_homography_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                          double* H9, int32_t* ok, int device);
+void planar_seed_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                       const double* kmtx5, double* pose7, int device);
+// linescan.hip: calibrate_laser_plane (camera: model, intr, optional inverse coefficients; stage_ms [5] optional timing) and
+// fit_plane_svd / fit_plane_ransac on caller points
+void laser_plane_calibrate(int model, const double* intr, int n_inv, const double* inv, int n_views, const int64_t* toff, const double* X,
+                           const double* Y, const double* u, const double* v, const int64_t* loff, const double* lu, const double* lv,
+                           const cba_plane_fit_options& o, cba_laser_plane_result* res, double* points_xyz, uint8_t* inlier_mask,
+                           double* stage_ms, int device);
+void plane_fit(int64_t n, const double* xyz, const cba_plane_fit_options& o, double* plane, double* rms, int64_t* count, uint8_t* mask,
+               int device);
+// hom_ransac.hip: estimate_homography (RANSAC when o != nullptr, else DLT) of a batch of views, and estimate_intrinsics as one device
+// pipeline (o: RANSAC options or nullptr; bounds optional; inlier_mask, stage_ms [5] optional)
+void homography_ransac_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                             const cba_ransac_options* o, double* h9, int32_t* success, int32_t* inlier_count, double* symmetric_rms,
+                             uint8_t* inlier_mask, int device);
+void estimate_intrinsics_gpu(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
+                             const cba_ransac_options* o, const double* bounds_lo5, const double* bounds_hi5, int32_t* success,
+                             double* kmtx5, int32_t* sanitized, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
+                             int32_t* pose_ok, uint8_t* inlier_mask, double* stage_ms, int device);
+// extrinsic_dlt.hip: estimate_extrinsic_dlt on the blocked layout of cba_optimize_extrinsics; table [n_views][n_cams] = block index or
+// -1 (built and checked by the caller); blk_pose, blk_ok, stage_ms [4] optional
+void extrinsic_dlt_gpu(int n_cams, int n_views, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const int32_t* table,
+                       const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r,
+                       double* r_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
+// bundle_seed.hip: the hand-eye / bundle seed on the blocked layout of cba_optimize_bundle.  cam_start / cam_blk: each camera's list
+// (built and checked by the caller); g_T_c / cam_status in: the given or identity rows and GIVEN / TOO_FEW_VIEWS / DLT (the cameras
+// to estimate), out: the DLT cameras' results; b_T_t written only when b_T_t_given is NULL and some block is listed; blk_pose,
+// blk_ok, stage_ms [6] optional
+void bundle_seed_gpu(int n_cams, int n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
+                     const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, const int32_t* cam_start,
+                     const int32_t* cam_blk, double* g_T_c, int32_t* cam_status, int32_t* cam_pairs, const double* b_T_t_given,
+                     double* b_T_t, double* blk_pose, int32_t* blk_ok, double* stage_ms, int device);
+// distortion_fit.hip: fit_distortion_full / _dual and estimate_intrinsics_linear(_iterative) over a batch of problems (offset
+// [P+1], checked by the caller).  fixed_mask / fixed_val5: the resolved fixed coefficients; residuals, stage_ms [6] optional
+void distortion_fit_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                        const double* kmtx5, int num_radial, int fixed_mask, const double* fixed_val5, bool dual, double* coeffs,
+                        double* inverse, int32_t* ok, double* residuals, double* stage_ms, int device);
+void intrinsics_linear_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                           const double* bounds_lo5, const double* bounds_hi5, int use_skew, double* kmtx5, int32_t* status,
+                           int32_t* fallback, int device);
+void intrinsics_linear_iterative_gpu(int n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v,
+                                     int num_radial, int max_iterations, int use_skew, double* kmtx5, double* coeffs, int32_t* status,
+                                     int32_t* iterations, int32_t* fallback, double* stage_ms, int device);
+// camera.hip: project / unproject of caller points (intr: 10 | 12 entries; inv: n_inv inverse coefficients or NULL) and the
+// undistortion / rectification map handle (checked by the caller; stage_ms [3] optional: upload, kernel, download)
+void camera_project_gpu(int model, const double* intr, int64_t n, const double* xyz, double* uv, double* stage_ms, int device);
+void camera_unproject_gpu(int model, const double* intr, int n_inv, const double* inv, int64_t n, const double* uv, double* xy,
+                          double* stage_ms, int device);
+struct UndistortMap;
+UndistortMap* undistort_map_create(int model, int n_cams, const double* intr, const double* R9, const double* new_k5, int W, int H,
+                                   double* stage_ms, int device);
+void undistort_map_fetch(UndistortMap* m, float* map_x, float* map_y);
+void undistort_map_apply(UndistortMap* m, int n_images, const int32_t* cam, int sw, int sh, int ch, int dtype, double border,
+                         const void* src, void* dst, double* stage_ms);
+void undistort_map_destroy(UndistortMap* m) noexcept;
+int undistort_map_cams(const UndistortMap* m);
+// triangulate.hip: cba_triangulate (checked by the caller; rms_px, used_mask, cov6 optional; linearisations [n] and stage_ms [3] =
+// upload, kernel, download optional: the experiment builds' per-point pass counts and timing)
+void triangulate_gpu(int model, int n_cams, const double* intr, int n_inv, const double* inv, const double* c_T_r, int64_t n,
+                     const double* uv, const cba_triangulate_options& o, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
+                     double* cov6, int32_t* linearisations, double* stage_ms, int device);
+// laser_scan.hip: cba_laser_points and the cba_laser_scanner handle (checked by the caller).  frame_offset [n_frames + 1] and
+// frame_pose7 [n_frames][7]: both or neither; plane_xy optional; stage_ms [3] optional: upload, kernel, download
+void laser_points_gpu(int model, const double* intr, int n_inv, const double* inv, const double* plane, int64_t n, const double* uv,
+                      int n_frames, const int64_t* frame_offset, const double* frame_pose7, double* xyz, double* plane_xy, int device);
+struct LaserScanner;
+LaserScanner* laser_scanner_create(int model, const double* intr, int n_inv, const double* inv, const double* plane, int W, int H,
+                                   int max_frames, const cba_laser_scan_options& o, int device);
+int laser_scanner_max_frames(const LaserScanner* h);
+void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void* images, const double* frame_pose7, double* centre,
+                           double* amplitude, double* width_px, double* xyz, double* stage_ms);
+void laser_scanner_destroy(LaserScanner* h) noexcept;
+// stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
+// disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download
+void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device);
+struct StereoMatcher;
+StereoMatcher* stereo_matcher_create(int W, int H, int max_pairs, const cba_stereo_match_options& o, const cba_stereo_geometry* geom,
+                                     const double* pose7, int device);
+int stereo_matcher_max_pairs(const StereoMatcher* h);
+bool stereo_matcher_has_geometry(const StereoMatcher* h);
+void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost,
+                            float* xyz, double* stage_ms);
+void stereo_matcher_destroy(StereoMatcher* h) noexcept;
+// corner_detect.hip: the cba_corner_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload,
+// response, peaks, refine, download
+struct CornerDetector;
+CornerDetector* corner_detector_create(int W, int H, int max_images, int max_corners, const cba_corner_options& o, int device);
+int corner_detector_max_images(const CornerDetector* h);
+void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
+                             double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms);
+void corner_detector_destroy(CornerDetector* h) noexcept;
+// fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
+// (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
+void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,
+                 cba_allreduce_fn fn = nullptr, void* user = nullptr, int n_ranks = 1, int rank = 0, void* rccl_comm = nullptr);
+void handeye_solve(int n_poses, const double* bTg, const double* cTt, double* pose7, const cba_options* o, cba_summary* s,
+                   double* cov, int device, cba_allreduce_fn fn = nullptr, void* user = nullptr, int n_ranks = 1, int rank = 0,
+                   void* rccl_comm = nullptr);
+void* rccl_comm_create(const uint8_t* id, int n_ranks, int rank);  // backend_hip.hip: ncclCommInitRank on the current device
+void rccl_comm_destroy(void* comm, bool abort);
+
+}  // namespace cba

@@ -10,7 +10,7 @@
 #include <cmath>
 #include <cstdio>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "vp_math.hpp"
 
 namespace cba {
@@ -42,8 +42,7 @@ void planar_pose_batch(int n_views, const int64_t* view_offset, const double* X,
     if (n_views <= 0) throw std::invalid_argument("No observations provided");
     if (num_radial < 0 || num_radial + 2 > VP_MAX_M) throw std::invalid_argument("num_radial must be in [0, 3]");
     if (!view_offset || !X || !Y || !u || !v || !kmtx5 || !pose7 || !o) throw std::invalid_argument("null argument");
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         ObsSoA d;

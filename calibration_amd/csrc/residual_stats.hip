@@ -164,9 +164,9 @@ void residual_stats_launch(Engine& e, double t2) {
     refresh_consts(e);
     const size_t nt = static_cast<size_t>(std::max<int64_t>(1, e.n_tilesB)) * STATS_W;
     const size_t nb = static_cast<size_t>(std::max(1, e.n_blocks)) * STATS_W;
-    if (e.diag_part.n < nt) e.diag_part.alloc(nt);
-    if (e.diag_blk.n < nb) e.diag_blk.alloc(nb);
-    if (e.diag_tot.n < STATS_W) e.diag_tot.alloc(STATS_W);
+    e.diag_part.ensure(nt);
+    e.diag_blk.ensure(nb);
+    e.diag_tot.ensure(STATS_W);
     launch_stats_tiles<false>(e, 0, e.n_tilesB, t2, e.diag_part.p, nullptr, nullptr, nullptr, 0);
     if (e.n_blocks > 0)
         hipLaunchKernelGGL(k_stats_blocks, dim3(static_cast<unsigned>((e.n_blocks + 255) / 256)), dim3(256), 0, e.stream, e.n_blocks,
@@ -194,7 +194,7 @@ void residuals_fetch_range(Engine& e, int b0, int b1, double t2, double* r, uint
     // sized to the requested range (grown, never to the whole problem unless the whole problem is asked for)
     const size_t nt = static_cast<size_t>(std::max<int64_t>(1, tb1 - tb0)) * STATS_W;
     const size_t no = static_cast<size_t>(std::max<int64_t>(2, np));
-    if (e.diag_fpart.n < nt) e.diag_fpart.alloc(nt);
+    e.diag_fpart.ensure(nt);
     if (e.diag_ru.n < no) { e.diag_ru.alloc(no); e.diag_rv.alloc(no); e.diag_keep.alloc(no); }
     launch_stats_tiles<true>(e, tb0, tb1 - tb0, t2, e.diag_fpart.p, e.diag_ru.p, e.diag_rv.p, e.diag_keep.p, p0);
     CBA_HIP(hipGetLastError());

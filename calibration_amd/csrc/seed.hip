@@ -1,7 +1,7 @@
 // seed.hip — batched estimate_planar_pose (src/estimation/linear/planarpose_linear.cpp:54-76) on the GPU: one wavefront
 // per view runs seed_math.hpp::planar_seed_view (three strided passes over the view's points + O(1) per-lane algebra).
 // SURVEY.md §8(f) rank 1 — the per-view seeds that optimize_intrinsics / optimize_intrinsics_semidlt start from.
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "seed_math.hpp"
 
 namespace cba {
@@ -41,8 +41,7 @@ __global__ __launch_bounds__(64 * SEED_WAVES) void k_dlt_homography(int n_views,
 
 void dlt_homography_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
                           double* H9, int32_t* ok, int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         ObsSoA d;
@@ -61,8 +60,7 @@ void dlt_homography_batch(int n_views, const int64_t* view_offset, const double*
 
 void planar_seed_batch(int n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v,
                        const double* kmtx5, double* pose7, int device) {
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t stream = lease;
     {
         ObsSoA d;

@@ -14,7 +14,7 @@
 // rank fills for its own rows and zeroes elsewhere (the all-reduce is then a gather).  The O(#views) arrow / Woodbury step of
 // semidlt_core.hpp runs redundantly and identically on every rank from the identical table.
 #include <rccl/rccl.h>
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "semidlt_core.hpp"
 #include "semidlt_math.hpp"
 

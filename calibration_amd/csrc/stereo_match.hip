@@ -16,9 +16,10 @@
 // Image reads are single bytes inside [0, n_pairs W H); the image buffers are still allocated STM_IMG_PAD bytes longer.
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "stereo_math.hpp"
 
 namespace cba {
@@ -176,22 +177,17 @@ __global__ __launch_bounds__(STM_BLOCK) void k_stereo_points(int64_t n, const do
 }
 
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
-static int stm_grid(int64_t items) {
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(STM_GRID, (items + STM_BLOCK - 1) / STM_BLOCK)));
-}
-
 void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device) {
     StereoGeom g;
     stereo_fill_geom(geom.focal, geom.cx, geom.cy, geom.baseline, pose7, &g);
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t s = lease;
     const size_t np = static_cast<size_t>(n);
     DevBuf<double> duvd, dxyz;
     duvd.alloc(3 * np);
     dxyz.alloc(3 * np);
     duvd.upload(uvd, 3 * np, s);
-    hipLaunchKernelGGL(k_stereo_points, dim3(stm_grid(n)), dim3(STM_BLOCK), 0, s, n, duvd.p, dxyz.p, g);
+    hipLaunchKernelGGL(k_stereo_points, dim3(launch_grid(n, STM_BLOCK, STM_GRID)), dim3(STM_BLOCK), 0, s, n, duvd.p, dxyz.p, g);
     CBA_HIP(hipGetLastError());
     dxyz.download(xyz, 3 * np, s);
     CBA_HIP(hipStreamSynchronize(s));
@@ -199,9 +195,8 @@ void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int
 
 // The matcher: options and geometry fixed at create, every buffer sized for max_pairs there.  Every call ends with its stream
 // synchronised.
-struct StereoMatcher {
-    int device = 0;
-    StreamLease lease;
+struct StereoMatcher : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
     cba_stereo_match_options opts;
     StereoGeom geom;
     bool has_geom = false;
@@ -213,12 +208,11 @@ struct StereoMatcher {
     DevBuf<int32_t> cost;
     DevBuf<int16_t> dl, dr;
 };
+static_assert(!std::is_copy_constructible_v<StereoMatcher> && !std::is_copy_assignable_v<StereoMatcher>, "a handle owns its stream and buffers");
 
 StereoMatcher* stereo_matcher_create(int W, int H, int max_pairs, const cba_stereo_match_options& o, const cba_stereo_geometry* geom,
                                      const double* pose7, int device) {
-    CBA_HIP(hipSetDevice(device));
-    auto h = std::make_unique<StereoMatcher>();
-    h->device = device;
+    auto h = std::make_unique<StereoMatcher>(device);
     h->opts = o;
     h->W = W; h->H = H; h->max_pairs = max_pairs;
     h->has_geom = geom != nullptr;
@@ -255,8 +249,7 @@ bool stereo_matcher_has_geometry(const StereoMatcher* h) { return h->has_geom; }
 // stage_ms [3] (experiment builds): upload, kernels, download
 void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost,
                             float* xyz, double* stage_ms) {
-    CBA_HIP(hipSetDevice(h->device));
-    const hipStream_t s = h->lease;
+    const hipStream_t s = h->begin();
     const size_t px = static_cast<size_t>(n_pairs) * h->W * h->H;
     StageTimer<4> tm(s, stage_ms != nullptr);
     tm.mark(0);
@@ -282,7 +275,7 @@ void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, 
         CBA_HIP(hipGetLastError());
     }
     if (lr || xyz) {
-        hipLaunchKernelGGL(k_stereo_finish, dim3(stm_grid(static_cast<int64_t>(px))), dim3(STM_BLOCK), 0, s, static_cast<int64_t>(px), h->W,
+        hipLaunchKernelGGL(k_stereo_finish, dim3(launch_grid(static_cast<int64_t>(px), STM_BLOCK, STM_GRID)), dim3(STM_BLOCK), 0, s, static_cast<int64_t>(px), h->W,
                            h->H, h->opts.lr_max_diff, h->dl.p, h->dr.p, h->disparity.p, xyz ? h->xyz.p : nullptr, h->geom);
         CBA_HIP(hipGetLastError());
     }
@@ -292,17 +285,9 @@ void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, 
     if (xyz) h->xyz.download(xyz, 3 * px, s);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));
-    if (stage_ms) {
-        stage_ms[0] = tm.ms(0, 1);
-        stage_ms[1] = tm.ms(1, 2);
-        stage_ms[2] = tm.ms(2, 3);
-    }
+    tm.report(stage_ms);
 }
 
-void stereo_matcher_destroy(StereoMatcher* h) noexcept {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    delete h;
-}
+void stereo_matcher_destroy(StereoMatcher* h) noexcept { destroy_handle(h); }
 
 }  // namespace cba

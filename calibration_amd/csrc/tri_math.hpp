@@ -38,6 +38,7 @@ struct TriCamera {
     double t[3];
     double o[3];
 };
+static_assert(sizeof(TriCamera) == 640, "TriCamera is read by k_triangulate: its layout is fixed");
 
 struct TriResult {
     double X[3];
@@ -49,13 +50,7 @@ struct TriResult {
 };
 
 CBA_HD void tri_fill_camera(int model, const double* intr, int n_inv, const double* inv, const double* pose7, TriCamera* k) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
-    k->cam.model = model;
-    k->cam.n_inv = inv ? n_inv : 0;
-    for (int j = 0; j < 12; ++j) k->cam.intr[j] = j < ni ? intr[j] : 0.0;
-    for (int j = 0; j < LS_MAX_INV; ++j) k->cam.inv[j] = j < k->cam.n_inv ? inv[j] : 0.0;
-    for (int j = 0; j < SD_SIZE; ++j) k->cam.sd[j] = 0.0;
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(k->cam.intr, k->cam.sd);
+    ls_fill_camera(model, intr, n_inv, inv, &k->cam);
     quat_to_rotmat(pose7, k->R);
     for (int j = 0; j < 3; ++j) k->t[j] = pose7[4 + j];
     double c[3];

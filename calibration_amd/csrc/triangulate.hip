@@ -10,7 +10,7 @@
 //                              are no atomics, so a point's result does not depend on its neighbours.
 #include <vector>
 
-#include "engine.hpp"
+#include "pipelines.hpp"
 #include "tri_math.hpp"
 
 namespace cba {
@@ -44,13 +44,12 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_triangulate(int64_t n, int n_cams
 void triangulate_gpu(int model, int n_cams, const double* intr, int n_inv, const double* inv, const double* c_T_r, int64_t n,
                      const double* uv, const cba_triangulate_options& o, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
                      double* cov6, int32_t* linearisations, double* stage_ms, int device) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
+    const int ni = cam_intr_size(model);
     std::vector<TriCamera> hc(n_cams);
     for (int c = 0; c < n_cams; ++c)
         tri_fill_camera(model, intr + static_cast<size_t>(c) * ni, n_inv, inv ? inv + static_cast<size_t>(c) * n_inv : nullptr,
                         c_T_r + 7 * static_cast<size_t>(c), &hc[c]);
-    CBA_HIP(hipSetDevice(device));
-    StreamLease lease;
+    StreamLease lease(device);
     const hipStream_t s = lease;
     StageTimer<4> tm(s, stage_ms != nullptr);
     const size_t np = static_cast<size_t>(n);
@@ -90,11 +89,7 @@ void triangulate_gpu(int model, int n_cams, const double* intr, int n_inv, const
     if (linearisations) dlin.download(linearisations, np, s);
     tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));  // hc and the device buffers go out of scope
-    if (stage_ms) {
-        stage_ms[0] = tm.ms(0, 1);
-        stage_ms[1] = tm.ms(1, 2);
-        stage_ms[2] = tm.ms(2, 3);
-    }
+    tm.report(stage_ms);
 }
 
 }  // namespace cba

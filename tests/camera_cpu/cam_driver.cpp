@@ -1,23 +1,17 @@
 // cam_driver.cpp — TEST-ONLY: extern "C" wrappers of camera_math.hpp for ctypes (tests/test_camera_cpu.py).  Each wrapper runs the
 // per-point / per-pixel function the kernels of camera.hip run, in a plain loop.
 #include <cstdint>
+#include <cstring>
 
 #include "../../calibration_amd/csrc/camera_math.hpp"
 
 using namespace cba;
 
-static void fill(int model, const double* intr, double* out12, double* sd) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
-    for (int k = 0; k < 12; ++k) out12[k] = k < ni ? intr[k] : 0.0;
-    for (int k = 0; k < SD_SIZE; ++k) sd[k] = 0.0;
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(out12, sd);
-}
-
 extern "C" {
 
 void cam_project(int model, const double* intr, int64_t n, const double* xyz, double* uv) {
     double in[12], sd[SD_SIZE];
-    fill(model, intr, in, sd);
+    ls_fill_intr(model, intr, in, sd);
     for (int64_t i = 0; i < n; ++i) {
         const double* p = xyz + 3 * i;
         if (model == CAM_SCHEIMPFLUG) cam_project<CAM_SCHEIMPFLUG>(in, sd, p[0], p[1], p[2], uv + 2 * i, uv + 2 * i + 1);
@@ -26,20 +20,32 @@ void cam_project(int model, const double* intr, int64_t n, const double* xyz, do
 }
 
 void cam_unproject(int model, const double* intr, int n_inv, const double* inv, int64_t n, const double* uv, double* xy) {
-    LsCamera c{};
-    c.model = model;
-    c.n_inv = inv ? n_inv : 0;
-    fill(model, intr, c.intr, c.sd);
-    for (int k = 0; k < c.n_inv; ++k) c.inv[k] = inv[k];
+    LsCamera c;
+    ls_fill_camera(model, intr, n_inv, inv, &c);
     for (int64_t i = 0; i < n; ++i) ls_unproject(c, uv[2 * i], uv[2 * i + 1], xy + 2 * i, xy + 2 * i + 1);
+}
+
+// ls_fill_camera on an LsCamera whose every byte was 0xff before (a NaN in each double), member by member; sd_ref: scheimpflug_consts
+// of the 12 numbers the camera ends up with
+void cam_fill_camera(int model, const double* intr, int n_inv, const double* inv, int* model_out, int* n_inv_out, double* intr12,
+                     double* inv16, double* sd, double* sd_ref) {
+    LsCamera c;
+    std::memset(&c, 0xff, sizeof(c));
+    ls_fill_camera(model, intr, n_inv, inv, &c);
+    *model_out = c.model;
+    *n_inv_out = c.n_inv;
+    std::memcpy(intr12, c.intr, sizeof(c.intr));
+    std::memcpy(inv16, c.inv, sizeof(c.inv));
+    std::memcpy(sd, c.sd, sizeof(c.sd));
+    scheimpflug_consts(c.intr, sd_ref);
 }
 
 // maps [n_cams][H][W] of cameras intr [n_cams][10 | 12], R [n_cams][9] or NULL, new_k5 [n_cams][5] or NULL
 void cam_map(int model, int n_cams, const double* intr, const double* R, const double* kp, int W, int H, float* mx, float* my) {
-    const int ni = model == CAM_SCHEIMPFLUG ? 12 : 10;
+    const int ni = cam_intr_size(model);
     for (int c = 0; c < n_cams; ++c) {
         CamMapCam k{};
-        fill(model, intr + c * ni, k.intr, k.sd);
+        ls_fill_intr(model, intr + c * ni, k.intr, k.sd);
         for (int j = 0; j < 9; ++j) k.R[j] = R ? R[9 * c + j] : (j % 4 == 0 ? 1.0 : 0.0);
         for (int j = 0; j < 5; ++j) k.kp[j] = kp ? kp[5 * c + j] : k.intr[j];
         for (int v = 0; v < H; ++v)

@@ -7,12 +7,8 @@
 using namespace cba;
 
 static LsCamera camera(int model, const double* intr, int n_inv, const double* inv) {
-    LsCamera c{};
-    c.model = model;
-    c.n_inv = inv ? n_inv : 0;
-    for (int k = 0; k < (model == CAM_SCHEIMPFLUG ? 12 : 10); ++k) c.intr[k] = intr[k];
-    for (int k = 0; k < c.n_inv; ++k) c.inv[k] = inv[k];
-    if (model == CAM_SCHEIMPFLUG) scheimpflug_consts(c.intr, c.sd);
+    LsCamera c;
+    ls_fill_camera(model, intr, n_inv, inv, &c);
     return c;
 }
 

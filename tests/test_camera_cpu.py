@@ -113,6 +113,33 @@ def test_unproject_matches_restatement_and_linescan_bitwise(camcpu, lscpu, name,
             assert np.abs(xy - xyz[:, :2] / xyz[:, 2:]).max() < 1e-3
 
 
+@pytest.mark.parametrize("name,model,intr", CAMS, ids=[c[0] for c in CAMS])
+@pytest.mark.parametrize("inverse", ["none", "four", "four_null"])
+def test_fill_camera_pads_with_zeros_and_builds_the_constants(camcpu, name, model, intr, inverse):
+    """ls_fill_camera (linescan_math.hpp), the one camera fill of every pipeline: the intrinsics padded to 12, the inverse
+    coefficients given (none when the pointer is null, whatever the count says) padded to 16, the Scheimpflug constants."""
+    intr = np.asarray(intr, float)
+    ni = 12 if model == R.SCHEIMPFLUG else 10
+    assert len(intr) == ni
+    inv = np.array([0.3, -0.07, 1e-3, -2e-4]) if inverse == "four" else None
+    n_inv = 0 if inverse == "none" else 4
+    m, k = C.c_int(-1), C.c_int(-1)
+    intr12, inv16, sd, sd_ref = np.empty(12), np.empty(16), np.empty(36), np.empty(36)
+    camcpu.cam_fill_camera(model, _p(intr), n_inv, None if inv is None else _p(inv), C.byref(m), C.byref(k), _p(intr12), _p(inv16),
+                           _p(sd), _p(sd_ref))
+    assert m.value == model
+    assert k.value == (4 if inv is not None else 0)
+    assert np.array_equal(intr12[:ni], intr)
+    assert intr12[ni:].tobytes() == bytes(8 * (12 - ni))
+    if inv is not None:
+        assert np.array_equal(inv16[:4], inv)
+    assert inv16[k.value:].tobytes() == bytes(8 * (16 - k.value))
+    if model == R.SCHEIMPFLUG:
+        assert sd.tobytes() == sd_ref.tobytes()
+    else:
+        assert sd.tobytes() == bytes(8 * 36)
+
+
 def test_distort_is_project_with_identity_k(camcpu):
     dist = np.array([-0.21, 0.08, -0.012, 0.0011, -0.0007])
     xy = R.points(500, seed=9)[:, :2] / 3.0
