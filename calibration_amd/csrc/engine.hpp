@@ -103,7 +103,7 @@ struct Engine {
     DevBuf<double> bc, sd, aux;  // aux: bundle b_T_g [n_blocks][12]
     // The SHARED parameter blocks of copy k live side by side in shared_pack[k] = [intr | cam poses | target pose | shared step]
     // (intr[k], cam[k], target[k], delta_sh are windows into it): a trial point goes up as ONE copy and is accepted by one
-    // small kernel (backend_hip.hip k_accept).  Declared before its windows.
+    // small kernel (lm_kernels.hpp k_accept).  Declared before its windows.
     DevBuf<double> shared_pack[2];
     size_t pk_cam = 0, pk_target = 0, pk_delta = 0, pk_size = 0;  // offsets (doubles) of the windows
     DevBuf<double> intr[2], cam[2], view[2], target[2];
@@ -188,6 +188,7 @@ void compute_covariance(Engine& e, const cba_options& o, double* cov, bool share
 void compute_covariance_views(Engine& e, const cba_options& o, const int32_t* views, int n_sel, double* view_cov);
 int64_t covariance_dim(const Engine& e);
 int64_t shared_covariance_dim(const Engine& e);
+// collectives.cpp
 void engine_allreduce(Engine& e, double* host_buf, int64_t count);
 void rccl_unique_id(uint8_t* id);
 void rccl_init(Engine& e, const uint8_t* id, int n_ranks, int rank);

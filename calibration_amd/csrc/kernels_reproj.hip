@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "engine.hpp"
+#include "block_reduce.hpp"
 #include "mode_b.hpp"
 #include "reproj_math.hpp"
 #include "wave_reduce.hpp"
@@ -266,55 +267,20 @@ __global__ void k_tile_sum(const double* __restrict__ gate, int n_blocks, int wi
     }
 }
 
-// scalar_out[0] = 1/2 sum_b rho(s_b), scalar_out[1] = sum_b s_b  (single workgroup, fixed order)
+// scalar_out[0] = 1/2 sum_b rho(s_b), scalar_out[1] = sum_b s_b  (single workgroup, fixed order: block_reduce.hpp)
 __global__ __launch_bounds__(256) void k_cost(int n_blocks, const double* __restrict__ blk_s, double huber_delta,
                                               double* __restrict__ out) {
-    __shared__ double sh[2][256];
-    double c = 0.0, ss = 0.0;
-    for (int b = static_cast<int>(threadIdx.x); b < n_blocks; b += 256) {
-        double rho, w;
-        huber(blk_s[b], huber_delta, &rho, &w);
-        c += 0.5 * rho;
-        ss += blk_s[b];
-    }
-    sh[0][threadIdx.x] = c;
-    sh[1][threadIdx.x] = ss;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (static_cast<int>(threadIdx.x) < o) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[0] = sh[0][0]; out[1] = sh[1][0]; }
+    __shared__ double lds[2 * 256];
+    cost_range_body(lds, 0, n_blocks, blk_s, huber_delta, out);
 }
 
 // two-stage form for many blocks (C3: 32 000): every workgroup reduces 2048 blocks to one pair, k_cost_final adds the pairs in
 // order (fixed tree: deterministic)
 __global__ __launch_bounds__(256) void k_cost_partial(int n_blocks, const double* __restrict__ blk_s, double huber_delta,
                                                       double* __restrict__ part) {
-    __shared__ double sh[2][256];
-    double c = 0.0, ss = 0.0;
+    __shared__ double lds[2 * 256];
     const int b0 = blockIdx.x * 2048;
-    const int b1 = b0 + 2048 < n_blocks ? b0 + 2048 : n_blocks;
-    for (int b = b0 + static_cast<int>(threadIdx.x); b < b1; b += 256) {
-        double rho, w;
-        huber(blk_s[b], huber_delta, &rho, &w);
-        c += 0.5 * rho;
-        ss += blk_s[b];
-    }
-    sh[0][threadIdx.x] = c;
-    sh[1][threadIdx.x] = ss;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (static_cast<int>(threadIdx.x) < o) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0][0]; part[2 * blockIdx.x + 1] = sh[1][0]; }
+    cost_range_body(lds, b0, min(b0 + 2048, n_blocks), blk_s, huber_delta, part + 2 * blockIdx.x);
 }
 __global__ void k_cost_final(int n_part, const double* __restrict__ part, double* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -510,7 +476,7 @@ void launch_block_consts(Engine& e, int which) {
     CBA_HIP(hipGetLastError());
 }
 
-// the per-camera part of launch_block_consts alone (the caller has built the block constants itself: backend_hip.hip k_step_head)
+// the per-camera part of launch_block_consts alone (the caller has built the block constants itself: lm_kernels.hpp k_step_head)
 void launch_camera_consts(Engine& e, int which) {
     e.active = which;
     if (e.model == CAM_SCHEIMPFLUG)

@@ -6,9 +6,9 @@
 // (initial radius 1e4, max 1e16, min 1e-32, min_relative_decrease 1e-3, LM diagonal clamp
 // [1e-6, 1e32], jacobi_scaling, monotonic steps, 5 consecutive invalid steps -> FAILURE), the
 // per-residual-block Huber corrector, QuaternionManifold / SubsetManifold / constant blocks and the
-// fx, fy >= 0 projection.  Ceres is a third-party dependency absent from /root/reference: see
-// DESIGN.md "Solver semantics" for the restated rules and the one known deviation (no Armijo
-// line search on bounds-constrained problems).
+// fx, fy >= 0 projection.  Ceres is a third-party dependency absent from the reference's tree: see
+// DESIGN.md "Solver semantics" for the restated rules; the Armijo line search Ceres runs on
+// bounds-constrained problems is line_search.hpp.
 //
 // Exchange pattern: every linear solve exchanges ONE packed buffer (PackLayout).  A trial point is
 // linearised speculatively (Backend::sys_step) so that the step statistics and the next system travel together: an accepted

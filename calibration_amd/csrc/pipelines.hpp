@@ -120,7 +120,7 @@ void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_a
 void handeye_solve(int n_poses, const double* bTg, const double* cTt, double* pose7, const cba_options* o, cba_summary* s,
                    double* cov, int device, cba_allreduce_fn fn = nullptr, void* user = nullptr, int n_ranks = 1, int rank = 0,
                    void* rccl_comm = nullptr);
-void* rccl_comm_create(const uint8_t* id, int n_ranks, int rank);  // backend_hip.hip: ncclCommInitRank on the current device
+void* rccl_comm_create(const uint8_t* id, int n_ranks, int rank);  // collectives.cpp: ncclCommInitRank on the current device
 void rccl_comm_destroy(void* comm, bool abort);
 
 }  // namespace cba

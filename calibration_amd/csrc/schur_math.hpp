@@ -1,5 +1,5 @@
 // schur_math.hpp — per-view / per-block bodies of the Schur-complement step, as
-// __host__ __device__ inline code (the HIP kernels in backend_hip.hip are thin index wrappers;
+// __host__ __device__ inline code (the HIP kernels in lm_kernels.hpp are thin index wrappers;
 // tests/cpu_backend runs the same bodies on the host to check the LM logic without a GPU).
 //
 // Per private view v (pose A of the INTRINSIC / EXTRINSIC chains), with w_b = rho'(s_b) the Huber
@@ -75,7 +75,7 @@ CBA_HD void bwd6(const double* L, double* b) {  // b <- L^-T b
 // Private-view elimination.  Outputs: L (36, lower), y (6), D (6), gp (6), scale2 (6, written when
 // init_scale), Z of every block of the view ([6][PSH] at blk_Z + b*6*PSH), *gmax = the view's
 // contribution to Ceres' gradient max-norm.  Returns false if the damped H_pp is not PD.
-// The elimination of one view in two pieces, so that a wavefront can share it (backend_hip.hip k_schur_view_wave: every lane
+// The elimination of one view in two pieces, so that a wavefront can share it (lm_kernels.hpp k_schur_view_wave: every lane
 // runs the factor part redundantly — it is a latency chain, not work — and the lanes split the Z columns); the serial form below
 // is the same pieces in sequence, so both give bit-identical results.
 //   schur_view_factor: H_pp, g_p, scale, damping, Cholesky, y.  F (36) = the factor, rd (6) = reciprocal pivots, in the caller's
@@ -167,7 +167,7 @@ CBA_HD bool schur_view_body(const SchurDims& d, int nb, const int32_t* blks, con
 //   g_p^T d_p   and   d_p^T H_pp d_p + 2 d_p^T E d_c  =  |rhs|^2 - d_p^T D d_p - 2 rhs^T a,
 // with a = Z d_c, rhs = y + a = -L^T d_p, H_pp = L L^T - D, E = L Z.
 // (two pieces again: a = Z d_c is a sum over the view's blocks and shared columns that a wavefront can split, the rest is a short
-// serial chain — backend_hip.hip k_backsub_wave; the serial form is the two in sequence)
+// serial chain — lm_kernels.hpp k_backsub_wave; the serial form is the two in sequence)
 CBA_HD void backsub_view_finish(bool fixed, const double* a, const double* L, const double* y, const double* D, const double* gp,
                                 const double* x7, double* delta_p, double* xt7, double* out4) {
     double xn = 0.0;
