@@ -94,6 +94,8 @@ from .camera import (  # noqa: F401
     unproject,
 )
 from .stereo import (  # noqa: F401
+    SgmMatcher,
+    SgmOptions,
     StereoGeometry,
     StereoMatcher,
     StereoMatchOptions,

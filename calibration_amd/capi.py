@@ -183,6 +183,22 @@ class CbaStereoMatchOptions(C.Structure):
     ]
 
 
+class CbaSgmOptions(C.Structure):
+    """``cba_sgm_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("min_disparity", C.c_int32),
+        ("num_disparities", C.c_int32),
+        ("p1", C.c_int32),
+        ("p2", C.c_int32),
+        ("paths", C.c_int32),
+        ("uniqueness_percent", C.c_int32),
+        ("lr_max_diff", C.c_int32),
+        ("subpixel", C.c_int32),
+        ("workspace_mb", C.c_int32),
+    ]
+
+
 class CbaStereoGeometry(C.Structure):
     """``cba_stereo_geometry`` (calibba.h)."""
 
@@ -434,6 +450,13 @@ PROTOTYPES = {
         C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, C.POINTER(C.c_float)]),
     "cba_stereo_matcher_destroy": (None, [C.c_void_p]),
     "cba_stereo_points": (C.c_int32, [C.POINTER(CbaStereoGeometry), c_double_p, C.c_int64, c_double_p, c_double_p]),
+    "cba_sgm_options_default": (None, [C.POINTER(CbaSgmOptions)]),
+    "cba_sgm_matcher_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaSgmOptions), C.POINTER(CbaStereoGeometry), c_double_p, C.c_int32,
+                    C.POINTER(C.c_void_p)]),
+    "cba_sgm_matcher_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, C.POINTER(C.c_float)]),
+    "cba_sgm_matcher_destroy": (None, [C.c_void_p]),
     "cba_corner_options_default": (None, [C.POINTER(CbaCornerOptions)]),
     "cba_corner_detector_create": (
         C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaCornerOptions), C.c_int32, C.POINTER(C.c_void_p)]),

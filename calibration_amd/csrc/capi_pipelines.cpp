@@ -1,6 +1,6 @@
 // capi_pipelines.cpp — the extern "C" entry points of the batched pipelines (include/calibba.h): laser-plane calibration, the linear
-// seeds, the distortion fits, the camera models, triangulation, laser scanning, stereo depth and chessboard detection.  Host-side
-// duties only, as in capi.cpp: validate the arguments, find the device, call the pipeline (pipelines.hpp).
+// seeds, the distortion fits, the camera models, triangulation, laser scanning, stereo depth (block and semi-global matching) and
+// chessboard detection.  Host-side duties only, as in capi.cpp: validate the arguments, find the device, call the pipeline (pipelines.hpp).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -918,6 +918,79 @@ __attribute__((visibility("default"))) cba_status cba_stereo_matcher_process_tim
                                                                                    double* stage_ms) {
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+}
+#endif
+
+// ---- semi-global matching (stereo_sgm.hip, sgm_math.hpp) ------------------------------------------------------------------------------
+void cba_sgm_options_default(cba_sgm_options* o) {
+    if (!o) return;
+    o->min_disparity = 0;
+    o->num_disparities = 64;
+    o->p1 = 4;
+    o->p2 = 32;
+    o->paths = 8;
+    o->uniqueness_percent = 10;
+    o->lr_max_diff = 1;
+    o->subpixel = 1;
+    o->workspace_mb = 0;
+}
+
+cba_status cba_sgm_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_sgm_options* opts,
+                                  const cba_stereo_geometry* geometry, const double* pose7, int32_t device, cba_sgm_matcher** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!opts) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        if (max_pairs < 1) throw std::invalid_argument("max_pairs must be >= 1");
+        if (static_cast<int64_t>(max_pairs) * width * height > 0x7fffffff) throw std::invalid_argument("max_pairs is too large");
+        if (opts->min_disparity < -32768 || opts->min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
+        if (opts->num_disparities < 1 || opts->num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
+        if (opts->p2 < 0 || opts->p2 > 1023) throw std::invalid_argument("p2 must be in 0..1023");
+        if (opts->p1 < 0 || opts->p1 > opts->p2) throw std::invalid_argument("p1 must be in 0..p2");
+        if (opts->paths != 4 && opts->paths != 8) throw std::invalid_argument("paths must be 4 or 8");
+        if (opts->uniqueness_percent < 0 || opts->uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
+        if (opts->lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
+        if (opts->subpixel != 0 && opts->subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
+        if (opts->workspace_mb < 0 || opts->workspace_mb > CBA_SGM_MAX_WORKSPACE_MB) throw std::invalid_argument("workspace_mb must be in 0..1048576");
+        if (static_cast<int64_t>(width) * height * opts->num_disparities > CBA_SGM_MAX_VOLUME)
+            throw std::invalid_argument("width height num_disparities must be <= 2^31");
+        if (pose7 && !geometry) throw std::invalid_argument("a pose needs a geometry");
+        if (geometry) check_stereo_geometry(geometry, pose7);
+        require_device(device);
+        *out = reinterpret_cast<cba_sgm_matcher*>(sgm_matcher_create(width, height, max_pairs, *opts, geometry, pose7, device));
+    });
+}
+
+static cba_status sgm_matcher_process_impl(cba_sgm_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right, float* disparity,
+                                           int32_t* cost, float* xyz, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        SgmMatcher* m = reinterpret_cast<SgmMatcher*>(h);
+        if (n_pairs < 0 || n_pairs > sgm_matcher_max_pairs(m)) throw std::invalid_argument("n_pairs must be in [0, max_pairs]");
+        if (xyz && !sgm_matcher_has_geometry(m)) throw std::invalid_argument("xyz needs a matcher created with a geometry");
+        if (n_pairs == 0) return;
+        if (!left || !right) throw std::invalid_argument("null argument");
+        sgm_matcher_process(m, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+    });
+}
+
+cba_status cba_sgm_matcher_process(cba_sgm_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right, float* disparity,
+                                   int32_t* cost, float* xyz) {
+    return sgm_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, nullptr);
+}
+
+void cba_sgm_matcher_destroy(cba_sgm_matcher* h) { sgm_matcher_destroy(reinterpret_cast<SgmMatcher*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_sgm.py): cba_sgm_matcher_process timing its stages on the device (stage_ms [13] = upload, census,
+// cost, the 8 path launches in the order of the rule, selection, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_sgm_matcher_process_timed(cba_sgm_matcher* h, int32_t n_pairs, const uint8_t* left,
+                                                                                const uint8_t* right, float* disparity, int32_t* cost,
+                                                                                float* xyz, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return sgm_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
 }
 #endif
 

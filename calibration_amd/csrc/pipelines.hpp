@@ -105,6 +105,22 @@ bool stereo_matcher_has_geometry(const StereoMatcher* h);
 void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost,
                             float* xyz, double* stage_ms);
 void stereo_matcher_destroy(StereoMatcher* h) noexcept;
+// the finish step both matchers share (k_stereo_finish of stereo_match.hip), queued on s: the left-right check (lr_max_diff >= 0, dr
+// then required) and the points (xyz optional)
+struct StereoGeom;
+void stereo_finish_launch(hipStream_t s, int64_t n_px, int W, int H, int lr_max_diff, const int16_t* dl, const int16_t* dr, float* disparity,
+                          float* xyz, const StereoGeom& g);
+// stereo_sgm.hip: the cba_sgm_matcher handle (checked by the caller).  geom and pose7 optional at create; disparity, cost, xyz optional;
+// stage_ms [SGM_STAGES] optional: upload, census, cost, the 8 path launches, selection, download
+constexpr int SGM_STAGES = 13;
+struct SgmMatcher;
+SgmMatcher* sgm_matcher_create(int W, int H, int max_pairs, const cba_sgm_options& o, const cba_stereo_geometry* geom, const double* pose7,
+                               int device);
+int sgm_matcher_max_pairs(const SgmMatcher* h);
+bool sgm_matcher_has_geometry(const SgmMatcher* h);
+void sgm_matcher_process(SgmMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost, float* xyz,
+                         double* stage_ms);
+void sgm_matcher_destroy(SgmMatcher* h) noexcept;
 // corner_detect.hip: the cba_corner_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload,
 // response, peaks, refine, download
 struct CornerDetector;

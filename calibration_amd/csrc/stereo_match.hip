@@ -11,6 +11,7 @@
 //                          registers only.  RIGHT = false writes disparity, cost and d*; RIGHT = true swaps the roles (other column
 //                          x + d) and writes the left-right map d_R as int16.
 //   k_stereo_finish        one lane per pixel, grid-stride: the left-right check and the pixel's 3D point (stereo_point).
+//                          stereo_finish_launch queues it for the matchers of this file and of stereo_sgm.hip.
 //   k_stereo_points        one lane per caller triple, grid-stride: stereo_point, after k_laser_points.
 // No atomics, no scratch, no dynamically indexed private array; every sum is an exact integer, so results do not depend on the tiling.
 // Image reads are single bytes inside [0, n_pairs W H); the image buffers are still allocated STM_IMG_PAD bytes longer.
@@ -177,6 +178,13 @@ __global__ __launch_bounds__(STM_BLOCK) void k_stereo_points(int64_t n, const do
 }
 
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
+void stereo_finish_launch(hipStream_t s, int64_t n_px, int W, int H, int lr_max_diff, const int16_t* dl, const int16_t* dr, float* disparity,
+                          float* xyz, const StereoGeom& g) {
+    hipLaunchKernelGGL(k_stereo_finish, dim3(launch_grid(n_px, STM_BLOCK, STM_GRID)), dim3(STM_BLOCK), 0, s, n_px, W, H, lr_max_diff, dl, dr,
+                       disparity, xyz, g);
+    CBA_HIP(hipGetLastError());
+}
+
 void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device) {
     StereoGeom g;
     stereo_fill_geom(geom.focal, geom.cx, geom.cy, geom.baseline, pose7, &g);
@@ -275,9 +283,8 @@ void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, 
         CBA_HIP(hipGetLastError());
     }
     if (lr || xyz) {
-        hipLaunchKernelGGL(k_stereo_finish, dim3(launch_grid(static_cast<int64_t>(px), STM_BLOCK, STM_GRID)), dim3(STM_BLOCK), 0, s, static_cast<int64_t>(px), h->W,
-                           h->H, h->opts.lr_max_diff, h->dl.p, h->dr.p, h->disparity.p, xyz ? h->xyz.p : nullptr, h->geom);
-        CBA_HIP(hipGetLastError());
+        stereo_finish_launch(s, static_cast<int64_t>(px), h->W, h->H, h->opts.lr_max_diff, h->dl.p, h->dr.p, h->disparity.p, xyz ? h->xyz.p : nullptr,
+                             h->geom);
     }
     tm.mark(2);
     if (disparity) h->disparity.download(disparity, px, s);

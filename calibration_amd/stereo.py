@@ -3,7 +3,8 @@ reference): calibrated pair -> rectified pair -> dense disparity -> 3D points.
 
 ``rectify`` takes the two cameras and their ``c_T_r`` rows as the rig entry points return them and gives the rectifying rotations, the
 common camera matrix, the baseline and ``r_T_rect``; ``rectify_maps`` builds the ``UndistortMap`` of ``camera.py`` from them;
-``StereoMatcher`` turns rectified uint8 pairs into disparity, cost and points; ``stereo_points`` does the last step for caller
+``StereoMatcher`` (block matching) and ``SgmMatcher`` (semi-global matching, ``cba_sgm_matcher``) turn rectified uint8 pairs into
+disparity, cost and points; ``stereo_points`` does the last step for caller
 (u, v, disparity) triples.  The rules are stated in calibba.h.  Arguments are validated here before the library sees them.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import capi
 from .camera import UndistortMap
-from .capi import CbaStereoGeometry, CbaStereoMatchOptions, CbaStereoRectifyOptions, dptr, i32ptr, u8ptr
+from .capi import CbaSgmOptions, CbaStereoGeometry, CbaStereoMatchOptions, CbaStereoRectifyOptions, dptr, i32ptr, u8ptr
 from .linescan import _camera
 
 
@@ -54,9 +55,25 @@ class StereoMatchOptions:
 
 
 @dataclass
+class SgmOptions:
+    """``cba_sgm_options``: disparities [min_disparity, min_disparity + num_disparities), the path penalties p1 <= p2, 4 or 8 paths,
+    uniqueness margin in percent (0: off), left-right tolerance (-1: off), the sub-pixel parabola step, and the budget of the device
+    volumes in MiB (0: 2048)."""
+    min_disparity: int = 0
+    num_disparities: int = 64
+    p1: int = 4
+    p2: int = 32
+    paths: int = 8
+    uniqueness_percent: int = 10
+    lr_max_diff: int = 1
+    subpixel: bool = True
+    workspace_mb: int = 0
+
+
+@dataclass
 class StereoResult:
     disparity: np.ndarray          # [n][H][W] float32, NaN where there is no valid match
-    cost: np.ndarray               # [n][H][W] int32, C(d*), -1 without an admissible candidate
+    cost: np.ndarray               # [n][H][W] int32, C(d*) (SgmMatcher: S(d*)), -1 without an admissible candidate
     xyz: Optional[np.ndarray]      # [n][H][W][3] float32 (only with a geometry)
 
 
@@ -122,13 +139,18 @@ class StereoMatcher:
     buffers are sized for max_pairs at construction.  geometry: a StereoGeometry, a StereoRectification or [focal, cx, cy, baseline];
     pose: pose7 or 4x4 applied to the points (r_T_rect, say).  Use as a context manager or call ``close()``."""
 
-    def __init__(self, width: int, height: int, max_pairs: int = 1, opts: Optional[StereoMatchOptions] = None, geometry=None, pose=None,
-                 device: int = 0):
+    _FN = "cba_stereo_matcher"  # the handle's create / process / destroy functions
+
+    @staticmethod
+    def _options(o):
+        o = o or StereoMatchOptions()
+        return CbaStereoMatchOptions(int(o.min_disparity), int(o.num_disparities), int(o.half_window), int(o.uniqueness_percent),
+                                     int(o.lr_max_diff), int(bool(o.subpixel)))
+
+    def __init__(self, width: int, height: int, max_pairs: int = 1, opts=None, geometry=None, pose=None, device: int = 0):
         self._h = None
         self._lib = capi.load_library()
-        o = opts or StereoMatchOptions()
-        co = CbaStereoMatchOptions(int(o.min_disparity), int(o.num_disparities), int(o.half_window), int(o.uniqueness_percent),
-                                   int(o.lr_max_diff), int(bool(o.subpixel)))
+        co = self._options(opts)
         if pose is not None and geometry is None:
             raise ValueError("a pose needs a geometry")
         g = None if geometry is None else _geometry(geometry)
@@ -136,8 +158,9 @@ class StereoMatcher:
         self.width, self.height, self.max_pairs = int(width), int(height), int(max_pairs)
         self.has_geometry = g is not None
         h = C.c_void_p()
-        capi.check(self._lib, self._lib.cba_stereo_matcher_create(self.width, self.height, self.max_pairs, C.byref(co),
-                                                                  None if g is None else C.byref(g), dptr(p), int(device), C.byref(h)))
+        create = getattr(self._lib, self._FN + "_create")
+        capi.check(self._lib, create(self.width, self.height, self.max_pairs, C.byref(co), None if g is None else C.byref(g), dptr(p),
+                                     int(device), C.byref(h)))
         self._h = h
 
     def _images(self, a, name):
@@ -168,13 +191,14 @@ class StereoMatcher:
         disp, cost = np.empty(shape, np.float32), np.empty(shape, np.int32)
         xyz = np.empty(shape + (3,), np.float32) if want_xyz else None
         fp = C.POINTER(C.c_float)
-        capi.check(self._lib, self._lib.cba_stereo_matcher_process(self._h, n, u8ptr(L), u8ptr(R), disp.ctypes.data_as(fp), i32ptr(cost),
-                                                                   None if xyz is None else xyz.ctypes.data_as(fp)))
+        process = getattr(self._lib, self._FN + "_process")
+        capi.check(self._lib, process(self._h, n, u8ptr(L), u8ptr(R), disp.ctypes.data_as(fp), i32ptr(cost),
+                                      None if xyz is None else xyz.ctypes.data_as(fp)))
         return StereoResult(disp, cost, xyz)
 
     def close(self):
         if self._h is not None:
-            self._lib.cba_stereo_matcher_destroy(self._h)
+            getattr(self._lib, self._FN + "_destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -188,6 +212,23 @@ class StereoMatcher:
             self.close()
         except Exception:
             pass
+
+
+class SgmMatcher(StereoMatcher):
+    """``cba_sgm_matcher``: semi-global matching on a census cost (the rule is stated in calibba.h).  Same images, geometry, pose,
+    ``process`` and ``StereoResult`` as ``StereoMatcher``; ``cost`` is S(d*).  opts: an ``SgmOptions``."""
+
+    _FN = "cba_sgm_matcher"
+
+    @staticmethod
+    def _options(o):
+        o = o or SgmOptions()
+        if int(o.paths) not in (4, 8):
+            raise ValueError(f"paths must be 4 or 8, got {o.paths}")
+        if not 0 <= int(o.p1) <= int(o.p2):
+            raise ValueError(f"the penalties must satisfy 0 <= p1 <= p2, got p1 = {o.p1}, p2 = {o.p2}")
+        return CbaSgmOptions(int(o.min_disparity), int(o.num_disparities), int(o.p1), int(o.p2), int(o.paths), int(o.uniqueness_percent),
+                             int(o.lr_max_diff), int(bool(o.subpixel)), int(o.workspace_mb))
 
 
 def stereo_points(uvd, geometry, pose=None) -> np.ndarray:
@@ -204,5 +245,5 @@ def stereo_points(uvd, geometry, pose=None) -> np.ndarray:
     return xyz
 
 
-__all__ = ["StereoGeometry", "StereoRectification", "StereoMatchOptions", "StereoResult", "StereoMatcher", "rectify", "rectify_maps",
-           "stereo_points"]
+__all__ = ["StereoGeometry", "StereoRectification", "StereoMatchOptions", "StereoResult", "StereoMatcher", "SgmOptions", "SgmMatcher",
+           "rectify", "rectify_maps", "stereo_points"]

@@ -1023,6 +1023,66 @@ void cba_stereo_matcher_destroy(cba_stereo_matcher* h);
 cba_status cba_stereo_points(const cba_stereo_geometry* geometry, const double* pose7 /*[7] or NULL*/, int64_t n,
                              const double* uvd /*[n][3]*/, double* xyz /*[n][3]*/);
 
+/* ---- semi-global matching: census cost, path sums, the selection of the block matcher (no counterpart in the reference) ---------
+ *
+ * cba_sgm_matcher: a second matcher beside cba_stereo_matcher, for the scenes where a window SAD fails (low texture, depth edges).
+ * Images, geometry, pose, the three outputs and the xyz rule are exactly those of cba_stereo_matcher; the handle owns the options, an
+ * optional geometry, one stream and every device buffer, sized at create; cba_sgm_matcher_process allocates nothing.  Options:
+ *   min_disparity       any int32 with |.| <= 32768       dmin, the lowest disparity searched
+ *   num_disparities     1..256                            D
+ *   p1                  0..p2                             the penalty of a step of one candidate along a path
+ *   p2                  0..1023                           the penalty of a larger step
+ *   paths               4 or 8
+ *   uniqueness_percent  0..100                            0 = off
+ *   lr_max_diff         >= -1                             -1 = off
+ *   subpixel            0 / 1                             the parabola step
+ *   workspace_mb        0..CBA_SGM_MAX_WORKSPACE_MB       the budget of the volumes in MiB, 0 = 2048: the cost and sum volumes are held
+ *                                                         for g = max(1, min(max_pairs, budget / bytes per pair)) pairs at a time
+ * Rule, W = width, H = height, candidates d in [dmin, dmin + D); every quantity is an exact integer:
+ * 1. Census.  Pixels outside an image read 0.  For an image I and a pixel (x, y) the bit of the offset (i, j) is
+ *    b_I(x, y; i, j) = [I(x+i, y+j) < I(x, y)], over the window |i| <= 4, |j| <= 3, (i, j) != (0, 0): 62 bits.  How the bits are packed
+ *    is the implementation's business; only their set matters.
+ * 2. Cost, for every pixel and every candidate: C(x, y, d) = the number of (i, j) with b_L(x, y; i, j) != b_R(x-d, y; i, j); when x - d
+ *    lies outside [0, W-1] all 62 bits of b_R are 0.  0 <= C <= 62.
+ * 3. Paths.  The directions r are (1,0), (-1,0), (0,1), (0,-1) for paths = 4; paths = 8 adds (1,1), (-1,1), (1,-1), (-1,-1).  With
+ *    q = p - r: when q lies outside the image L_r(p, d) = C(p, d); otherwise
+ *      L_r(p, d) = C(p, d) + min( L_r(q, d), L_r(q, d-1) + p1, L_r(q, d+1) + p1, M + p2 ) - M,   M = min over all D candidates k of L_r(q, k),
+ *    the terms d-1 and d+1 taken only when they are candidates.  Hence 0 <= L_r <= 62 + p2, and S = the sum of L_r over the directions
+ *    is at most 8 * 1085 and fits 16 bits.
+ * 4. Selection.  Candidate d is admissible for the left pixel (x, y) when 0 <= x - d <= W-1: no window margin, the census is defined
+ *    everywhere.  Steps 2 to 5 of the rule of cba_stereo_matcher then apply word for word with S for C and this admissibility: no
+ *    admissible candidate gives NaN with cost -1, otherwise d* is the admissible candidate of lowest S, the lowest d among equals;
+ *    uniqueness compares 100 S(d) <= (100 + u) S(d*) over the admissible d with |d - d*| > 1; the right map d_R(x', y) is the d of
+ *    lowest S, the lowest among equals, over the d with 0 <= x' + d <= W-1, its cost being S(x'+d, y, d), and the left pixel is NaN when
+ *    d_R(x - d*, y) differs from d* by more than lr_max_diff; the parabola takes S(d*-1) and S(d*+1) when both are admissible, one
+ *    fp64 division, and the result is rounded once to float32.  The cost output is S(d*), or -1 without an admissible candidate.
+ * 5. A pixel's result depends on its own pair only: not on the other pairs of the call, on workspace_mb or on any tiling.
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): those of cba_stereo_matcher, an option outside its range,
+ * p1 > p2, paths other than 4 or 8, and width height D > CBA_SGM_MAX_VOLUME.  n_pairs == 0 is no work; otherwise no device ->
+ * CBA_ERR_NO_DEVICE. */
+#define CBA_SGM_MAX_VOLUME ((int64_t)1 << 31) /* largest width * height * num_disparities */
+#define CBA_SGM_MAX_WORKSPACE_MB 1048576
+typedef struct cba_sgm_options {
+    int32_t min_disparity;      /* |.| <= 32768 (default 0) */
+    int32_t num_disparities;    /* D, 1..256 (default 64) */
+    int32_t p1;                 /* 0..p2 (default 4) */
+    int32_t p2;                 /* 0..1023 (default 32) */
+    int32_t paths;              /* 4 or 8 (default 8) */
+    int32_t uniqueness_percent; /* 0..100, 0 = off (default 10) */
+    int32_t lr_max_diff;        /* >= -1, -1 = off (default 1) */
+    int32_t subpixel;           /* 0 / 1 (default 1) */
+    int32_t workspace_mb;       /* budget for the volumes; 0 = 2048 (default 0) */
+} cba_sgm_options;
+void cba_sgm_options_default(cba_sgm_options* o);
+typedef struct cba_sgm_matcher cba_sgm_matcher; /* opaque: options, geometry, device buffers sized at create, one stream */
+cba_status cba_sgm_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_sgm_options* opts,
+                                  const cba_stereo_geometry* geometry /*or NULL*/, const double* pose7 /*[7] or NULL*/, int32_t device,
+                                  cba_sgm_matcher** out);
+cba_status cba_sgm_matcher_process(cba_sgm_matcher* h, int32_t n_pairs, const uint8_t* left, const uint8_t* right,
+                                   float* disparity /*[n][H][W] or NULL*/, int32_t* cost /*[n][H][W] or NULL*/,
+                                   float* xyz /*[n][H][W][3] or NULL*/);
+void cba_sgm_matcher_destroy(cba_sgm_matcher* h);
+
 /* ---- chessboard detection: corners, sub-pixel fit, grid order (no counterpart in the reference, which reads corners from files) ---
  *
  * Pictures of a plain chessboard -> the (object_xy, image_uv) lists every other entry point starts from.
