@@ -106,12 +106,18 @@ from .stereo import (  # noqa: F401
     stereo_points,
 )
 from .detect import (  # noqa: F401
+    BlobDetector,
+    BlobOptions,
+    BlobResult,
     BoardDetection,
     CornerDetector,
     CornerOptions,
     CornerResult,
+    circle_centre_bias,
     detect_chessboard,
+    detect_circle_grid,
     order_chessboard,
+    order_circle_grid,
 )
 from .triangulate import (  # noqa: F401
     TriangulateOptions,

@@ -218,6 +218,24 @@ class CbaCornerOptions(C.Structure):
     ]
 
 
+class CbaBlobOptions(C.Structure):
+    """``cba_blob_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("polarity", C.c_int32),
+        ("inner_half", C.c_int32),
+        ("outer_half", C.c_int32),
+        ("min_contrast", C.c_int32),
+        ("nms_radius", C.c_int32),
+        ("max_radius", C.c_int32),
+        ("rounds", C.c_int32),
+        ("reserved", C.c_int32),
+        ("max_fit_error", C.c_double),
+        ("max_axis_ratio", C.c_double),
+        ("min_radius", C.c_double),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, c_double_p, C.c_int64, C.c_void_p)
 
 
@@ -464,6 +482,14 @@ PROTOTYPES = {
         C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
     "cba_corner_detector_destroy": (None, [C.c_void_p]),
     "cba_chessboard_order": (C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, c_int32_p]),
+    "cba_blob_options_default": (None, [C.POINTER(CbaBlobOptions)]),
+    "cba_blob_detector_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaBlobOptions), C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_blob_detector_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "cba_blob_detector_destroy": (None, [C.c_void_p]),
+    "cba_circle_grid_order": (
+        C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
 }
 
 

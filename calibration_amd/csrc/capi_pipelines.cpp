@@ -9,6 +9,8 @@
 #include "capi_common.hpp"
 #include "corner_grid.hpp"
 #include "corner_math.hpp"
+#include "blob_math.hpp"
+#include "circle_grid.hpp"
 #include "hom_ransac_math.hpp"
 #include "linescan_math.hpp"
 #include "pipelines.hpp"
@@ -1075,6 +1077,108 @@ __attribute__((visibility("default"))) cba_status cba_corner_detector_process_ti
                                                                                     double* stage_ms) {
     if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
+}
+#endif
+
+// ---- circle-grid detection (blob_detect.hip, blob_math.hpp, circle_grid.hpp) --------------------------------------------------------
+void cba_blob_options_default(cba_blob_options* o) {
+    if (!o) return;
+    o->polarity = CBA_BLOB_DARK;
+    o->inner_half = 2;
+    o->outer_half = 12;
+    o->min_contrast = 30;
+    o->nms_radius = 4;
+    o->max_radius = 20;
+    o->rounds = 3;
+    o->max_fit_error = 0.2;
+    o->max_axis_ratio = 3.0;
+    o->min_radius = 1.5;
+    o->reserved = 0;
+}
+
+cba_status cba_blob_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_blobs, const cba_blob_options* opts,
+                                    int32_t device, cba_blob_detector** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!opts) throw std::invalid_argument("null argument");
+        check_side(width);
+        check_side(height);
+        if (opts->polarity != CBA_BLOB_DARK && opts->polarity != CBA_BLOB_BRIGHT) throw std::invalid_argument("polarity must be DARK or BRIGHT");
+        if (opts->inner_half < 1 || opts->inner_half > 7) throw std::invalid_argument("inner_half must be in 1..7");
+        if (opts->outer_half <= opts->inner_half || opts->outer_half > 15) throw std::invalid_argument("outer_half must be in inner_half + 1..15");
+        if (opts->min_contrast < 1 || opts->min_contrast > 255) throw std::invalid_argument("min_contrast must be in 1..255");
+        if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
+        if (opts->max_radius < 2 || opts->max_radius > 32) throw std::invalid_argument("max_radius must be in 2..32");
+        if (opts->rounds < 1 || opts->rounds > 8) throw std::invalid_argument("rounds must be in 1..8");
+        if (!(opts->max_fit_error > 0.0) || !(opts->max_axis_ratio >= 1.0) || !(opts->min_radius >= 0.0))
+            throw std::invalid_argument("max_fit_error must be > 0, max_axis_ratio >= 1 and min_radius >= 0");
+        const int side = 2 * (opts->outer_half + opts->nms_radius) + 1;
+        if (width < side || height < side) throw std::invalid_argument("width and height must be >= 2 (outer_half + nms_radius) + 1");
+        if (max_images < 1) throw std::invalid_argument("max_images must be >= 1");
+        if (static_cast<int64_t>(max_images) * width * height > 0x7fffffff) throw std::invalid_argument("max_images is too large");
+        if (max_blobs < 1 || static_cast<int64_t>(max_images) * max_blobs > (1 << 28))
+            throw std::invalid_argument("max_blobs must be >= 1 and max_images max_blobs <= 2^28");
+        require_device(device);
+        *out = reinterpret_cast<cba_blob_detector*>(blob_detector_create(width, height, max_images, max_blobs, *opts, device));
+    });
+}
+
+static cba_status blob_detector_process_impl(cba_blob_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
+                                             int32_t* out_status, double* out_xy, double* out_shape, double* out_fit_error,
+                                             int32_t* out_response, int32_t* out_flags, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        BlobDetector* d = reinterpret_cast<BlobDetector*>(h);
+        if (n_images < 0 || n_images > blob_detector_max_images(d)) throw std::invalid_argument("n_images must be in [0, max_images]");
+        if (n_images == 0) return;
+        if (!images) throw std::invalid_argument("null argument");
+        blob_detector_process(d, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error, out_response, out_flags, stage_ms);
+    });
+}
+
+cba_status cba_blob_detector_process(cba_blob_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status,
+                                     double* out_xy, double* out_shape, double* out_fit_error, int32_t* out_response, int32_t* out_flags) {
+    return blob_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error, out_response, out_flags,
+                                      nullptr);
+}
+
+void cba_blob_detector_destroy(cba_blob_detector* h) { blob_detector_destroy(reinterpret_cast<BlobDetector*>(h)); }
+
+cba_status cba_circle_grid_order(int32_t n, const double* xy, const double* shape, int32_t pattern, int32_t rows, int32_t cols,
+                                 int32_t* out_index, int32_t* out_unique) {
+    return guarded([&] {
+        if (!out_index) throw std::invalid_argument("null argument");
+        if (n < 0) throw std::invalid_argument("n must be >= 0");
+        if (pattern != CBA_CIRCLES_SYMMETRIC && pattern != CBA_CIRCLES_ASYMMETRIC) throw std::invalid_argument("pattern must be SYMMETRIC or ASYMMETRIC");
+        if (rows < 2 || cols < 2 || static_cast<int64_t>(rows) * cols > 65536) throw std::invalid_argument("rows and cols must be >= 2, rows cols <= 65536");
+        if (n > 0 && !xy) throw std::invalid_argument("null argument");
+        if (n > 65536) throw std::invalid_argument("n must be <= 65536");
+        for (int32_t i = 0; i < n; ++i) {
+            if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) throw std::invalid_argument("blobs must be finite");
+            if (!shape) continue;
+            const double* m = shape + 3 * i;
+            if (!std::isfinite(m[0]) || !std::isfinite(m[1]) || !std::isfinite(m[2]) || !(m[0] > 0.0) || !(m[0] * m[2] - m[1] * m[1] > 0.0))
+                throw std::invalid_argument("shapes must be finite and positive definite");
+        }
+        int unique = 0;
+        if (!circle_grid_order(n, xy, shape, pattern, rows, cols, out_index, &unique))
+            for (int32_t i = 0; i < rows * cols; ++i) out_index[i] = -1;  // not found
+        if (out_unique) *out_unique = unique;
+    });
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_blobs.py): cba_blob_detector_process timing its stages on the device (stage_ms [5] = upload,
+// response, peaks, refine, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_blob_detector_process_timed(cba_blob_detector* h, int32_t n_images,
+                                                                                  const uint8_t* images, int32_t* out_count,
+                                                                                  int32_t* out_status, double* out_xy, double* out_shape,
+                                                                                  double* out_fit_error, int32_t* out_response,
+                                                                                  int32_t* out_flags, double* stage_ms) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return blob_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error, out_response, out_flags,
+                                      stage_ms);
 }
 #endif
 

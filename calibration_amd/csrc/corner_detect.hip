@@ -8,11 +8,8 @@
 //                            sample out of them with constant shifts.  The ring samples of a pixel are packed four to a dword: DR is two
 //                            v_sad_u8, S16 four more against zero.  The response leaves as int16 (one 8-byte store per lane when the
 //                            width is a multiple of 4), 0 in the border.
-//   k_corner_peaks<PLACE>    one workgroup per strip of CRN_SH rows of one image walks the strip in row-major chunks of 256 pixels; a
-//                            lane tests its pixel (corner_is_peak), the wavefront ballots, ranks come from popcounts and the four
-//                            wavefront totals from LDS.  PLACE = false leaves the strip's count; k_corner_prefix turns the counts of an
-//                            image into exclusive offsets, the true count and the status; PLACE = true repeats the walk and writes
-//                            each peak's pixel index at offset + rank.  No atomic: the order is row-major by construction.
+//   k_peak_walk, k_peak_prefix  the row-major peak list of peak_walk.hpp (shared with blob_detect.hip), instantiated for int16
+//                            responses, strips of CRN_SH rows and the border CORNER_BORDER.
 //   k_corner_refine          one lane per slot (image, corner), grid-stride: response, COG, GRADIENT, the angle sums
 //                            (corner_refine_one); slots past the kept corners get NaN / 0.
 // The host halves atan2 of the angle sums after the download.  No scratch, no dynamically indexed private array.
@@ -23,6 +20,7 @@
 
 #include "pipelines.hpp"
 #include "corner_math.hpp"
+#include "peak_walk.hpp"
 
 namespace cba {
 
@@ -131,71 +129,6 @@ __global__ __launch_bounds__(CRN_BLOCK) void k_corner_response(CornerRespArgs a)
     }
 }
 
-struct CornerPeakArgs {
-    const int16_t* resp;
-    int W, H, strips, min_response, nms, max_corners;
-    int32_t* strip_count;       // [n_images][strips] (PLACE = false)
-    const int32_t* strip_off;   // [n_images][strips] (PLACE = true)
-    int32_t* peak_px;           // [n_images][max_corners]: y W + x
-};
-
-template <bool PLACE>
-__global__ __launch_bounds__(CRN_BLOCK) void k_corner_peaks(CornerPeakArgs a) {
-    __shared__ int wsum[CRN_BLOCK / 64];
-    const int W = a.W, H = a.H;
-    const int im = static_cast<int>(blockIdx.x) / a.strips, st = static_cast<int>(blockIdx.x) - im * a.strips;
-    const int y0 = st * CRN_SH, npx = min(CRN_SH, H - y0) * W;
-    const int16_t* R = a.resp + static_cast<int64_t>(im) * W * H;
-    const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-    int running = PLACE ? a.strip_off[blockIdx.x] : 0;
-    for (int base = 0; base < npx; base += CRN_BLOCK) {  // uniform over the workgroup
-        const int p = base + tid;
-        bool flag = false;
-        int x = 0, y = 0;
-        if (p < npx) {
-            const int ry = p / W;
-            x = p - ry * W;
-            y = y0 + ry;
-            flag = corner_is_peak(R, W, H, x, y, a.min_response, a.nms);
-        }
-        const unsigned long long m = __ballot(flag);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int v = 0; v < CRN_BLOCK / 64; ++v) {
-            const int c = wsum[v];
-            before += v < wave ? c : 0;
-            total += c;
-        }
-        if constexpr (PLACE) {
-            if (flag) {
-                const int slot = running + before + __popcll(m & ((1ull << lane) - 1ull));
-                if (slot < a.max_corners) a.peak_px[static_cast<int64_t>(im) * a.max_corners + slot] = y * W + x;
-            }
-        }
-        running += total;
-        __syncthreads();
-    }
-    if constexpr (!PLACE) {
-        if (tid == 0) a.strip_count[blockIdx.x] = running;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_corner_prefix(int n_images, int strips, int max_corners, const int32_t* __restrict__ strip_count,
-                                                      int32_t* __restrict__ strip_off, int32_t* __restrict__ count,
-                                                      int32_t* __restrict__ status) {
-    const int im = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-    if (im >= n_images) return;
-    int run = 0;
-    for (int s = 0; s < strips; ++s) {
-        strip_off[im * strips + s] = run;
-        run += strip_count[im * strips + s];
-    }
-    count[im] = run;
-    status[im] = run > max_corners ? CORNER_STATUS_OVERFLOW : 0;
-}
-
 struct CornerRefineArgs {
     const uint8_t* img;
     const int16_t* resp;
@@ -297,16 +230,9 @@ void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* ima
     else hipLaunchKernelGGL(k_corner_response<false>, rgrid, dim3(CRN_BLOCK), 0, s, ra);
     CBA_HIP(hipGetLastError());
     tm.mark(2);
-    CornerPeakArgs pa{h->resp.p, h->W, h->H, h->strips, h->opts.min_response, h->opts.nms_radius, h->max_corners,
-                      h->strip_count.p, h->strip_off.p, h->peak_px.p};
-    const dim3 pgrid(static_cast<unsigned>(n_images * h->strips));
-    hipLaunchKernelGGL(k_corner_peaks<false>, pgrid, dim3(CRN_BLOCK), 0, s, pa);
-    CBA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_corner_prefix, dim3((n_images + 63) / 64), dim3(64), 0, s, n_images, h->strips, h->max_corners, h->strip_count.p,
-                       h->strip_off.p, h->count.p, h->status.p);
-    CBA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_corner_peaks<true>, pgrid, dim3(CRN_BLOCK), 0, s, pa);
-    CBA_HIP(hipGetLastError());
+    PeakArgs<int16_t> pa{h->resp.p, h->W, h->H, h->strips, CORNER_BORDER, h->opts.min_response, h->opts.nms_radius, h->max_corners,
+                         h->strip_count.p, h->strip_off.p, h->peak_px.p};
+    peak_walk_launch<int16_t, CRN_SH>(s, n_images, pa, h->count.p, h->status.p);
     tm.mark(3);
     CornerRefineArgs fa{h->img.p, h->resp.p, h->W, h->H, static_cast<int>(slots), h->max_corners, h->opts.cog_radius, h->opts.refine,
                         h->opts.refine_half_window, h->opts.refine_iterations, h->count.p, h->peak_px.p, h->wt.p, h->trig.p, h->xy.p,

@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "camera_math.hpp"
+#include "peak_walk.hpp"
 
 namespace cba {
 
@@ -21,7 +22,7 @@ constexpr int CORNER_REFINE_NONE = 0, CORNER_REFINE_COG = 1, CORNER_REFINE_GRADI
 constexpr int CORNER_FLAG_WINDOW = 1;    // GRADIENT: the window would leave the image; the last good position is kept
 constexpr int CORNER_FLAG_DET = 2;       // GRADIENT: det <= CORNER_DET_REL (trace)^2; the last good position is kept
 constexpr int CORNER_FLAG_DRIFT = 4;     // GRADIENT: ended further than cog_radius + 1 from its peak (either axis)
-constexpr int CORNER_STATUS_OVERFLOW = 1;
+constexpr int CORNER_STATUS_OVERFLOW = PEAK_STATUS_OVERFLOW;
 constexpr double CORNER_DET_REL = 1e-6;
 
 // ring offset n = 0..15: (0,-5) (2,-5) (3,-3) (5,-2) (5,0) (5,2) (3,3) (2,5) (0,5) (-2,5) (-3,3) (-5,2) (-5,0) (-5,-2) (-3,-3) (-2,-5);
@@ -51,17 +52,7 @@ CBA_HD int corner_response_at(const uint8_t* img, int W, int H, int x, int y) {
 
 // R: one image's responses [H][W]
 CBA_HD bool corner_is_peak(const int16_t* R, int W, int H, int x, int y, int min_response, int nms) {
-    const int b = CORNER_BORDER + nms;
-    if (x < b || y < b || x > W - 1 - b || y > H - 1 - b) return false;
-    const int v = R[y * W + x];
-    if (v < min_response) return false;
-    for (int dy = -nms; dy <= nms; ++dy)
-        for (int dx = -nms; dx <= nms; ++dx) {
-            const int q = R[(y + dy) * W + x + dx];
-            const bool earlier = dy < 0 || (dy == 0 && dx < 0);
-            if (earlier ? q >= v : q > v) return false;  // the pixel itself: q > v is false
-        }
-    return true;
+    return peak_is_max<int16_t>(R, W, H, x, y, min_response, nms, CORNER_BORDER);
 }
 
 // centre of gravity of max(R, 0) over the (2c + 1)^2 window of a peak (R(peak) >= 1, so the sum is positive)

@@ -129,6 +129,14 @@ int corner_detector_max_images(const CornerDetector* h);
 void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
                              double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms);
 void corner_detector_destroy(CornerDetector* h) noexcept;
+// blob_detect.hip: the cba_blob_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload, response,
+// peaks, refine, download
+struct BlobDetector;
+BlobDetector* blob_detector_create(int W, int H, int max_images, int max_blobs, const cba_blob_options& o, int device);
+int blob_detector_max_images(const BlobDetector* h);
+void blob_detector_process(BlobDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
+                           double* out_shape, double* out_fit_error, int32_t* out_response, int32_t* out_flags, double* stage_ms);
+void blob_detector_destroy(BlobDetector* h) noexcept;
 // fn / user / n_ranks / rank: multi-GPU form — this rank's share of the pairs, sums all-reduced through the host callback
 // (rccl_comm: an ncclComm_t over the ranks' devices - the sums are all-reduced on the device instead of through fn)
 void handeye_dlt(int n_poses, const double* bTg, const double* cTt, double min_angle_deg, double* pose7, int device,

@@ -159,5 +159,213 @@ def detect_chessboard(images, rows: int, cols: int, square: float = 1.0, opts: O
     return out
 
 
+# ---- circle grids (cba_blob_detector, cba_circle_grid_order) ---------------------------------------------------------------------------
+BLOB_DARK, BLOB_BRIGHT = 0, 1
+CIRCLES_SYMMETRIC, CIRCLES_ASYMMETRIC = 0, 1
+BLOB_FLAG_WINDOW, BLOB_FLAG_NO_EDGE, BLOB_FLAG_DEGENERATE, BLOB_FLAG_SHAPE, BLOB_FLAG_RATIO, BLOB_FLAG_SIZE, BLOB_FLAG_DUPLICATE = (
+    1, 2, 4, 8, 16, 32, 64)
+
+
+@dataclass
+class BlobOptions:
+    """``cba_blob_options``: polarity, the half sides of the inner and outer box, the lowest contrast of a peak in grey levels, the
+    suppression radius, the longest ray, the centroid rounds and the three limits behind FLAG_SHAPE, FLAG_RATIO and FLAG_SIZE."""
+    polarity: int = BLOB_DARK
+    inner_half: int = 2
+    outer_half: int = 12
+    min_contrast: int = 30
+    nms_radius: int = 4
+    max_radius: int = 20
+    rounds: int = 3
+    max_fit_error: float = 0.2
+    max_axis_ratio: float = 3.0
+    min_radius: float = 1.5
+
+
+@dataclass
+class BlobResult:
+    count: np.ndarray      # [n] int32: the true number of peaks of every image
+    status: np.ndarray     # [n] int32: STATUS_OVERFLOW
+    xy: np.ndarray         # [n][max_blobs][2] float64, NaN past the kept blobs
+    shape: np.ndarray      # [n][max_blobs][3] float64 (m_xx, m_xy, m_yy) of the ellipse {d : d^T M^-1 d = 1}; NaN when flagged early
+    fit_error: np.ndarray  # [n][max_blobs] float64
+    response: np.ndarray   # [n][max_blobs] int32
+    flags: np.ndarray      # [n][max_blobs] int32: BLOB_FLAG_*
+
+    def kept(self, i: int) -> int:
+        return int(min(self.count[i], self.xy.shape[1]))
+
+    @property
+    def semi_axes(self) -> np.ndarray:
+        """[n][max_blobs][2] (major, minor): the square roots of the eigenvalues of M"""
+        h, d = 0.5 * (self.shape[..., 0] + self.shape[..., 2]), 0.5 * (self.shape[..., 0] - self.shape[..., 2])
+        s = np.sqrt(d * d + self.shape[..., 1] ** 2)
+        return np.stack([np.sqrt(h + s), np.sqrt(h - s)], axis=-1)
+
+    @property
+    def angle(self) -> np.ndarray:
+        """[n][max_blobs]: direction of the major axis, in (-pi/2, pi/2], x right and y down"""
+        return 0.5 * np.arctan2(2.0 * self.shape[..., 1], self.shape[..., 0] - self.shape[..., 2])
+
+
+class BlobDetector:
+    """``cba_blob_detector``: uint8 images of one size in, blobs out.  The device buffers are sized for max_images and max_blobs at
+    construction.  Use as a context manager or call ``close()``."""
+
+    def __init__(self, width: int, height: int, max_images: int = 1, max_blobs: int = 1024, opts: Optional[BlobOptions] = None,
+                 device: int = 0):
+        self._h = None
+        self._lib = capi.load_library()
+        o = opts or BlobOptions()
+        bo = capi.CbaBlobOptions(int(o.polarity), int(o.inner_half), int(o.outer_half), int(o.min_contrast), int(o.nms_radius),
+                                 int(o.max_radius), int(o.rounds), 0, float(o.max_fit_error), float(o.max_axis_ratio), float(o.min_radius))
+        self.width, self.height, self.max_images, self.max_blobs = int(width), int(height), int(max_images), int(max_blobs)
+        h = C.c_void_p()
+        capi.check(self._lib, self._lib.cba_blob_detector_create(self.width, self.height, self.max_images, self.max_blobs, C.byref(bo),
+                                                                 int(device), C.byref(h)))
+        self._h = h
+
+    def process(self, images) -> BlobResult:
+        """images: [n][height][width] uint8 (or one [height][width] image)."""
+        if self._h is None:
+            raise ValueError("the detector is closed")
+        img = np.asarray(images)
+        if img.dtype != np.uint8:
+            raise ValueError(f"images must be uint8, got {img.dtype}")
+        if img.ndim == 2:
+            img = img[None]
+        if img.ndim != 3 or img.shape[1:] != (self.height, self.width):
+            raise ValueError(f"images must have shape [n][{self.height}][{self.width}], got {img.shape}")
+        img = np.ascontiguousarray(img)
+        n, m = img.shape[0], self.max_blobs
+        if n > self.max_images:
+            raise ValueError(f"{n} images given, the detector was created for {self.max_images}")
+        count, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        xy, shape, fit = np.full((n, m, 2), np.nan), np.full((n, m, 3), np.nan), np.full((n, m), np.nan)
+        response, flags = np.zeros((n, m), np.int32), np.zeros((n, m), np.int32)
+        capi.check(self._lib, self._lib.cba_blob_detector_process(self._h, n, u8ptr(img), i32ptr(count), i32ptr(status), dptr(xy),
+                                                                  dptr(shape), dptr(fit), i32ptr(response), i32ptr(flags)))
+        return BlobResult(count, status, xy, shape, fit, response, flags)
+
+    def close(self):
+        if self._h is not None:
+            self._lib.cba_blob_detector_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def circle_grid_points(rows: int, cols: int, spacing: float = 1.0, pattern: int = CIRCLES_ASYMMETRIC) -> np.ndarray:
+    """[rows cols][2], row-major over (j, i): SYMMETRIC (i, j) spacing; ASYMMETRIC ((2 i + j mod 2) spacing, j spacing)"""
+    jj, ii = np.divmod(np.arange(rows * cols), cols)
+    x = ii if pattern == CIRCLES_SYMMETRIC else 2 * ii + jj % 2
+    return np.stack([x * float(spacing), jj * float(spacing)], axis=1)
+
+
+def order_circle_grid(xy, shape, pattern: int, rows: int, cols: int):
+    """``cba_circle_grid_order``: one image's blobs xy [n][2] and their shapes [n][3] (or None: the identity metric) -> (index
+    [rows cols] into them, row-major over (j, i), or None when the grid is not found; unique: whether exactly one labelling fits)."""
+    lib = capi.load_library()
+    p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64))
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"xy must have shape [n][2], got {p.shape}")
+    m = None
+    if shape is not None:
+        m = np.ascontiguousarray(np.asarray(shape, dtype=np.float64))
+        if m.shape != (p.shape[0], 3):
+            raise ValueError(f"shape must have shape [{p.shape[0]}][3], got {m.shape}")
+    index = np.full(int(rows) * int(cols) if rows > 0 and cols > 0 else 1, -1, np.int32)
+    unique = np.zeros(1, np.int32)
+    capi.check(lib, lib.cba_circle_grid_order(p.shape[0], dptr(p), None if m is None else dptr(m), int(pattern), int(rows), int(cols),
+                                              i32ptr(index), i32ptr(unique)))
+    return (None, False) if index[0] < 0 else (index, bool(unique[0]))
+
+
+def _dlt_homography(obj: np.ndarray, uv: np.ndarray) -> np.ndarray:
+    """normalised DLT, obj [n][2] -> uv [n][2]"""
+    def norm(p):
+        m = p.mean(axis=0)
+        s = np.sqrt(2.0) / np.linalg.norm(p - m, axis=1).mean()
+        return np.array([[s, 0.0, -s * m[0]], [0.0, s, -s * m[1]], [0.0, 0.0, 1.0]])
+
+    To, Tu = norm(obj), norm(uv)
+    a, b = np.c_[obj, np.ones(len(obj))] @ To.T, np.c_[uv, np.ones(len(uv))] @ Tu.T
+    z = np.zeros_like(a)
+    A = np.concatenate([np.c_[a, z, -b[:, :1] * a], np.c_[z, a, -b[:, 1:2] * a]], axis=0)
+    h = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    Hm = np.linalg.inv(Tu) @ h @ To
+    return Hm / Hm[2, 2]
+
+
+def circle_centre_bias(H, object_xy, radius: float) -> np.ndarray:
+    """The perspective bias of an ellipse's centre, [n][2] px: the circle of ``radius`` round (X, Y) is the conic C, its image under the
+    board-to-image homography H is H^-T C H^-1, and the bias is that conic's centre minus the projection of (X, Y).  Lens distortion
+    is ignored: H is a pinhole map, so with a distorted camera the value is the bias to first order only."""
+    Hm = np.asarray(H, dtype=np.float64).reshape(3, 3)
+    obj = np.asarray(object_xy, dtype=np.float64).reshape(-1, 2)
+    Hi = np.linalg.inv(Hm)
+    X, Y = obj[:, 0], obj[:, 1]
+    one, zero = np.ones_like(X), np.zeros_like(X)
+    Cm = np.stack([np.stack([one, zero, -X], 1), np.stack([zero, one, -Y], 1), np.stack([-X, -Y, X * X + Y * Y - float(radius) ** 2], 1)], 1)
+    Q = Hi.T[None] @ Cm @ Hi[None]
+    centre = np.linalg.solve(Q[:, :2, :2], -Q[:, :2, 2:3])[:, :, 0]
+    p = np.c_[obj, one] @ Hm.T
+    return centre - p[:, :2] / p[:, 2:3]
+
+
+def detect_circle_grid(images, rows: int, cols: int, spacing: float = 1.0, pattern: int = CIRCLES_ASYMMETRIC,
+                       opts: Optional[BlobOptions] = None, circle_radius: Optional[float] = None, max_blobs: int = 1024, device: int = 0):
+    """Blobs of every image on the device, grid order on the host -> (list of BoardDetection, list of unique).  images: [n][H][W]
+    uint8; rows x cols circles at ``spacing``.  Blobs that carry a flag are left out before ordering.  With ``circle_radius`` (in the
+    unit of ``spacing``) the perspective bias of the ellipse centres is subtracted: H from the ordered centres by a normalised DLT,
+    ``circle_centre_bias``, once more with H from the corrected centres.  Lens distortion is ignored in that correction."""
+    img = np.asarray(images)
+    if img.ndim == 2:
+        img = img[None]
+    if img.ndim != 3:
+        raise ValueError(f"images must have shape [n][H][W], got {img.shape}")
+    if rows < 2 or cols < 2:
+        raise ValueError("rows and cols must be >= 2")
+    if pattern not in (CIRCLES_SYMMETRIC, CIRCLES_ASYMMETRIC):
+        raise ValueError("pattern must be CIRCLES_SYMMETRIC or CIRCLES_ASYMMETRIC")
+    if circle_radius is not None and not circle_radius > 0:
+        raise ValueError("circle_radius must be > 0")
+    obj = circle_grid_points(rows, cols, spacing, pattern)
+    out, uniq = [], []
+    if img.shape[0] == 0:
+        return out, uniq
+    with BlobDetector(img.shape[2], img.shape[1], img.shape[0], max_blobs, opts, device) as det:
+        res = det.process(img)
+    for i in range(img.shape[0]):
+        k = res.kept(i)
+        good = np.flatnonzero(res.flags[i, :k] == 0)
+        index, unique = order_circle_grid(res.xy[i, good], res.shape[i, good], pattern, rows, cols) if good.size >= rows * cols else (None, False)
+        if index is None:
+            out.append(BoardDetection(False, np.full((rows * cols, 2), np.nan), obj.copy(), int(res.count[i])))
+        else:
+            uv = res.xy[i, good[index]].copy()
+            if circle_radius is not None:
+                fixed = uv
+                for _ in range(2):
+                    fixed = uv - circle_centre_bias(_dlt_homography(obj, fixed), obj, circle_radius)
+                uv = fixed
+            out.append(BoardDetection(True, uv, obj.copy(), int(res.count[i])))
+        uniq.append(unique)
+    return out, uniq
+
+
 __all__ = ["CornerOptions", "CornerResult", "BoardDetection", "CornerDetector", "order_chessboard", "detect_chessboard", "REFINE_NONE",
-           "REFINE_COG", "REFINE_GRADIENT", "STATUS_OVERFLOW", "FLAG_WINDOW", "FLAG_DET", "FLAG_DRIFT"]
+           "REFINE_COG", "REFINE_GRADIENT", "STATUS_OVERFLOW", "FLAG_WINDOW", "FLAG_DET", "FLAG_DRIFT", "BlobOptions", "BlobResult",
+           "BlobDetector", "order_circle_grid", "detect_circle_grid", "circle_centre_bias", "circle_grid_points", "BLOB_DARK", "BLOB_BRIGHT",
+           "CIRCLES_SYMMETRIC", "CIRCLES_ASYMMETRIC", "BLOB_FLAG_WINDOW", "BLOB_FLAG_NO_EDGE", "BLOB_FLAG_DEGENERATE", "BLOB_FLAG_SHAPE",
+           "BLOB_FLAG_RATIO", "BLOB_FLAG_SIZE", "BLOB_FLAG_DUPLICATE"]

@@ -1172,6 +1172,118 @@ void cba_corner_detector_destroy(cba_corner_detector* h);
 cba_status cba_chessboard_order(int32_t n, const double* xy /*[n][2]*/, const double* angle /*[n]*/, int32_t rows, int32_t cols,
                                 int32_t* out_index /*[rows cols]*/);
 
+/* ---- circle-grid detection: blobs, ellipse centres, grid order (no counterpart in the reference, which reads features from files) --
+ *
+ * Pictures of a symmetric or asymmetric circle grid -> the (object_xy, image_uv) lists every other entry point starts from.
+ *
+ * cba_blob_detector: a handle that owns the options, one stream and device buffers sized at create for max_images images of
+ * width x height with up to max_blobs blobs each; cba_blob_detector_process allocates nothing.  Images are single channel uint8,
+ * [n_images][height][width], rows and images contiguous.
+ * Options:
+ *   polarity        CBA_BLOB_DARK (dark blobs on a bright ground) / CBA_BLOB_BRIGHT
+ *   inner_half      1..7               a: the inner box is (2a + 1)^2
+ *   outer_half      a+1..15            b: the outer box is (2b + 1)^2, the ring is the outer box without the inner one
+ *   min_contrast    1..255             lowest difference of the ring's and the inner box's means, in grey levels
+ *   nms_radius      1..10              the suppression window is (2 nms_radius + 1)^2
+ *   max_radius      2..32              the longest ray, in pixels
+ *   rounds          1..8               centroid rounds
+ *   max_fit_error   > 0                CBA_BLOB_FLAG_SHAPE above it
+ *   max_axis_ratio  >= 1               CBA_BLOB_FLAG_RATIO above it
+ *   min_radius      >= 0               CBA_BLOB_FLAG_SIZE below it
+ * Rule for one image, W = width, H = height, I(x, y) the pixels, taken as 0 outside the image:
+ * 1. Response (exact integers).  S_in = the sum of I over the (2a + 1)^2 box centred on the pixel, S_ring = the sum over the
+ *    (2b + 1)^2 box minus S_in, n_in = (2a + 1)^2, n_ring = (2b + 1)^2 - n_in.  DARK: R = n_in S_ring - n_ring S_in = n_in n_ring (mean
+ *    ring - mean inner); BRIGHT: the negative.  R is 0 closer than b to a border; |R| < 2^31.  The detector keeps R as int32 and S_in
+ *    as uint16 (<= 57375) next to it, so S_ring = (R + n_ring S_in) / n_in (DARK; BRIGHT: (n_ring S_in - R) / n_in) is exact.
+ * 2. Peaks: the rule of cba_corner_detector with the border b.  A pixel is a peak when R >= min_contrast n_in n_ring, it lies at
+ *    least b + nms_radius from every border, and inside its (2 nms_radius + 1)^2 window R is greater than every response earlier in
+ *    row-major order and not less than every later one.  Peaks are listed in row-major order; with more than max_blobs peaks the
+ *    first max_blobs are kept, status has CBA_BLOB_STATUS_OVERFLOW and count is the true number.
+ * 3. Refinement of one peak, in fp64, in this order, nothing contracted; the device uses only + - x /.  Levels, fixed for all
+ *    rounds: lo = S_in / n_in and hi = S_ring / n_ring at the peak, thr = (lo + hi) / 2.  The image at a real position (x, y) with
+ *    0 <= x < W - 1, 0 <= y < H - 1 is bilinear: ix = floor(x), fx = x - ix (y alike), top = p00 + fx (p01 - p00), bot = p10 +
+ *    fx (p11 - p10), I = top + fy (bot - top); a position outside that range sets CBA_BLOB_FLAG_WINDOW.  The directions are d_k =
+ *    (cos 2 pi k / 32, sin 2 pi k / 32), k = 0..31, from a table made on the host.  A round, from the centre c (round 0: the
+ *    peak's pixel): I0 = I(c); if I0 is not on the blob's side of thr (DARK: I0 < thr, BRIGHT: I0 > thr) CBA_BLOB_FLAG_NO_EDGE.  For
+ *    k = 0..31 sample I(c + t d_k), t = 1..max_radius; the edge is the first t whose sample reaches thr (DARK: >=, BRIGHT: <=) and
+ *    lies at r_k = (t - 1) + (thr - I(t-1)) / (I(t) - I(t-1)) (BRIGHT: both differences negated), I(0) = I0; no such t:
+ *    CBA_BLOB_FLAG_NO_EDGE.  The edge points e_k = r_k d_k (relative to c) form a polygon; with cr = x_k y_k+1 - x_k+1 y_k summed over
+ *    k = 0..31 (e_32 = e_0): s2 = sum cr, sx = sum (x_k + x_k+1) cr, sy alike, sxx = sum (x_k^2 + x_k x_k+1 + x_k+1^2) cr, syy alike,
+ *    sxy = sum (x_k y_k+1 + 2 x_k y_k + 2 x_k+1 y_k+1 + x_k+1 y_k) cr.  Not s2 > 0: CBA_BLOB_FLAG_DEGENERATE.  The centroid is g =
+ *    (sx, sy) / (3 s2) and c moves to c + g.  After the last round M = 4 x the central second moments per area: m_xx = 4 (sxx / (6 s2)
+ *    - g_x^2), m_yy alike, m_xy = 4 (sxy / (12 s2) - g_x g_y); not det M > 0: CBA_BLOB_FLAG_DEGENERATE.  {d : d^T M^-1 d = 1} is the
+ *    ellipse with the polygon's moments, and fit_error = max_k |(e_k - g)^T M^-1 (e_k - g) - 1| (a square has 0.5).  Any of the three
+ *    flags ends the blob at its last good centre with NaN shape and fit_error.
+ * 4. Flags from the numbers (set on the host of the library): CBA_BLOB_FLAG_SHAPE when fit_error > max_fit_error; with the semi-axes
+ *    major >= minor, the square roots of M's eigenvalues, CBA_BLOB_FLAG_RATIO when major > max_axis_ratio minor and CBA_BLOB_FLAG_SIZE
+ *    when minor < min_radius; CBA_BLOB_FLAG_DUPLICATE when an earlier blob of the image without any flag has its centre within this
+ *    blob's minor semi-axis (a disc wider than the outer box gives several peaks on its rim that refine to one centre: the first
+ *    stays).
+ * Outputs of process, each may be NULL: out_count [n] (true number of peaks), out_status [n], out_xy [n][max_blobs][2], out_shape
+ * [n][max_blobs][3] = (m_xx, m_xy, m_yy), out_fit_error [n][max_blobs], out_response [n][max_blobs] (R at the peak's pixel),
+ * out_flags [n][max_blobs].  Entries past the kept blobs are NaN (xy, shape, fit_error) and 0 (response, flags).  An image's result
+ * does not depend on the other images of the call.
+ *
+ * cba_circle_grid_order (host, fp64; needs no device): one image's blobs xy [n][2], their shapes [n][3] (NULL: the identity) and the
+ * pattern's rows x cols -> out_index [rows cols] into the blob list, row-major over (j, i); all -1 when the grid is not found.
+ * CBA_CIRCLES_SYMMETRIC places point (j, i) at (i, j) d, CBA_CIRCLES_ASYMMETRIC at ((2 i + j mod 2) d, j d).  Both are square
+ * lattices (pitch d; pitch d sqrt 2 turned by 45 degrees), so one rule links both.
+ *   Metric: from blob c, q_c(v) = v^T M_c^-1 v and cos_c(v, w) = v^T M_c^-1 w / sqrt(q_c(v) q_c(w)): the board's metric to first order.
+ *   Links: blob c's candidates are its up to four nearest blobs by q_c (ties to the lower index) with q_c <= 1.44 x the nearest's
+ *   (1.2 x in distance); a link stays when each blob is a candidate of the other.
+ *   Labels: components are grown breadth first from the blob nearest the centroid of all blobs outwards.  The start's basis is e1 =
+ *   its first link, e2 = its link with the smallest |cos| to e1.  A blob taken from the queue first refreshes its basis: each axis
+ *   is replaced by the link with the largest |cos| to it, signed to point the axis's way, if that exceeds cos 30 degrees.  Then
+ *   every link is a step of +-e1 or +-e2 by the larger |cos|, which must exceed cos 30 degrees or the component is rejected; the
+ *   neighbour gets label + step and inherits the basis.  A blob reached with two different labels rejects the component.
+ *   Acceptance: a component of exactly rows cols blobs; for each of the lattice's eight symmetries (transpose, flip p, flip q) of the
+ *   labels (p, q), mapped to (p - q, p + q) for the asymmetric pattern and shifted to start at 0, the occupied cells must equal the
+ *   pattern's, and the labelling must be right-handed: cross(mean i-step, mean j-step) > 0 with x right and y down.  Exactly one such
+ *   labelling: unique = 1 (the asymmetric pattern with odd rows).  Otherwise the one whose mean i-step has the largest x, then y,
+ *   and unique = 0.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL options, out, handle, out_index, images for n_images > 0
+ * or xy for n > 0; an option outside its range; width or height below 2 (outer_half + nms_radius) + 1 or above CBA_IMAGE_MAX_SIDE;
+ * max_images < 1 or max_images width height > 2^31 - 1; max_blobs < 1 or max_images max_blobs > 2^28; n_images < 0 or > max_images;
+ * n < 0 or > 65536; an unknown pattern; rows or cols < 2 or rows cols > 65536; a non-finite blob or a shape that is not positive
+ * definite.  n_images == 0 is no work; otherwise no device -> CBA_ERR_NO_DEVICE. */
+#define CBA_BLOB_DARK 0
+#define CBA_BLOB_BRIGHT 1
+#define CBA_BLOB_STATUS_OVERFLOW 1 /* more than max_blobs peaks: the first max_blobs were kept */
+#define CBA_BLOB_FLAG_WINDOW 1     /* a sample would leave the image */
+#define CBA_BLOB_FLAG_NO_EDGE 2    /* the centre is not inside the blob, or a ray met no edge by max_radius */
+#define CBA_BLOB_FLAG_DEGENERATE 4 /* polygon area or moment determinant not positive */
+#define CBA_BLOB_FLAG_SHAPE 8      /* fit_error > max_fit_error */
+#define CBA_BLOB_FLAG_RATIO 16     /* major > max_axis_ratio minor */
+#define CBA_BLOB_FLAG_SIZE 32      /* minor < min_radius */
+#define CBA_BLOB_FLAG_DUPLICATE 64 /* an earlier unflagged blob has its centre within the minor semi-axis */
+#define CBA_CIRCLES_SYMMETRIC 0
+#define CBA_CIRCLES_ASYMMETRIC 1
+typedef struct cba_blob_options {
+    int32_t polarity;      /* CBA_BLOB_DARK (default) / CBA_BLOB_BRIGHT */
+    int32_t inner_half;    /* a, 1..7 (default 2) */
+    int32_t outer_half;    /* b, a+1..15 (default 12) */
+    int32_t min_contrast;  /* 1..255 (default 30) */
+    int32_t nms_radius;    /* 1..10 (default 4) */
+    int32_t max_radius;    /* 2..32 (default 20) */
+    int32_t rounds;        /* 1..8 (default 3) */
+    int32_t reserved;      /* keeps the doubles aligned; ignored */
+    double max_fit_error;  /* (default 0.2) */
+    double max_axis_ratio; /* (default 3) */
+    double min_radius;     /* (default 1.5) */
+} cba_blob_options;
+void cba_blob_options_default(cba_blob_options* o);
+typedef struct cba_blob_detector cba_blob_detector; /* opaque: options, device buffers sized at create, one stream */
+cba_status cba_blob_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_blobs, const cba_blob_options* opts,
+                                    int32_t device, cba_blob_detector** out);
+cba_status cba_blob_detector_process(cba_blob_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count /*[n] or NULL*/,
+                                     int32_t* out_status /*[n] or NULL*/, double* out_xy /*[n][max_blobs][2] or NULL*/,
+                                     double* out_shape /*[n][max_blobs][3] or NULL*/, double* out_fit_error /*[n][max_blobs] or NULL*/,
+                                     int32_t* out_response /*[n][max_blobs] or NULL*/, int32_t* out_flags /*[n][max_blobs] or NULL*/);
+void cba_blob_detector_destroy(cba_blob_detector* h);
+cba_status cba_circle_grid_order(int32_t n, const double* xy /*[n][2]*/, const double* shape /*[n][3] or NULL*/, int32_t pattern,
+                                 int32_t rows, int32_t cols, int32_t* out_index /*[rows cols]*/, int32_t* out_unique /*or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
