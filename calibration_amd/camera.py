@@ -76,7 +76,7 @@ def undistort(coeffs, xy, inverse_coeffs=None) -> np.ndarray:
     return unproject(_coeffs(coeffs), xy, inverse_coeffs)
 
 
-class UndistortMap:
+class UndistortMap(capi.Handle):
     """Undistortion / rectification maps of one or more cameras of one model, kept on the device.
 
     ``UndistortMap(cameras, width, height, R=None, new_K=None, device=0)``: cameras is one parameter vector or a list of them;
@@ -84,8 +84,10 @@ class UndistortMap:
     ([fx', fy', cx', cy', skew']; None: each camera's own K).  Map pixel (u', v') of camera c is project_c(R_c^T K'^-1 (u', v', 1)),
     rounded to float32, NaN where the ray does not reach the image side.  Use it as a context manager or call ``close()``."""
 
+    _DESTROY = "cba_undistort_map_destroy"
+
     def __init__(self, cameras, width: int, height: int, R=None, new_K=None, device: int = 0):
-        lib = capi.load_library()
+        out = self._out()
         cams = np.asarray(cameras, dtype=np.float64)
         if cams.ndim == 1:
             cams = cams.reshape(1, -1)
@@ -96,15 +98,11 @@ class UndistortMap:
         Rm = None if R is None else np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(self.n_cams, 9))
         Kn = None if new_K is None else np.ascontiguousarray(np.asarray(new_K, dtype=np.float64).reshape(self.n_cams, 5))
         self.width, self.height = int(width), int(height)
-        self._lib = lib
-        self._h = C.c_void_p()
-        capi.check(lib, lib.cba_undistort_map_create(self.model, self.n_cams, dptr(intr), dptr(Rm), dptr(Kn), self.width, self.height,
-                                                     int(device), C.byref(self._h)))
+        capi.check(self._lib, self._lib.cba_undistort_map_create(self.model, self.n_cams, dptr(intr), dptr(Rm), dptr(Kn), self.width,
+                                                                 self.height, int(device), out))
 
     def _handle(self):
-        if not self._h:
-            raise ValueError("UndistortMap is closed")
-        return self._h
+        return self._require_open("UndistortMap is closed")
 
     def maps(self):
         """(map_x, map_y), each [n_cams][height][width] float32: OpenCV's remap layout."""
@@ -138,23 +136,6 @@ class UndistortMap:
                                                                 float(border), im.ctypes.data_as(C.c_void_p),
                                                                 out.ctypes.data_as(C.c_void_p)))
         return out
-
-    def close(self):
-        if self._h:
-            self._lib.cba_undistort_map_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 __all__ = ["project", "unproject", "distort", "undistort", "UndistortMap"]

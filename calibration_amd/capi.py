@@ -537,6 +537,58 @@ def check(lib, status: int):
     raise CbaError(status, msg)
 
 
+class Handle:
+    """The life cycle of a library handle: ``_lib``, ``_h`` (a ``c_void_p`` a create call fills through ``_out()``; None when none is
+    open) and ``_DESTROY``, the name of the function that frees it.  A subclass whose create call raised closes cleanly."""
+
+    _DESTROY = ""
+    _h = None
+
+    def _out(self, lib=None):
+        """binds the library (default: load_library()); the byref argument of the create call"""
+        self._lib = lib or load_library()
+        self._h = C.c_void_p()
+        return C.byref(self._h)
+
+    def _require_open(self, message: str):
+        if not self._h:
+            raise ValueError(message)
+        return self._h
+
+    def close(self):
+        if self._h:
+            getattr(self._lib, self._DESTROY)(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def u8_batch(a, name: str, height: int, width: int, n_name: str = "n", max_n: Optional[int] = None, count_message: str = "") -> np.ndarray:
+    """A batch of uint8 images [n][height][width] (one [height][width] image is promoted) as a contiguous array.  n_name: how the
+    messages call the first dimension.  With max_n: n <= max_n, else ValueError(count_message.format(n)); the matchers compare their
+    two batches first and check the count themselves."""
+    img = np.asarray(a)
+    if img.dtype != np.uint8:
+        raise ValueError(f"{name} must be uint8, got {img.dtype}")
+    if img.ndim == 2:
+        img = img[None]
+    if img.ndim != 3 or img.shape[1:] != (height, width):
+        raise ValueError(f"{name} must have shape [{n_name}][{height}][{width}], got {img.shape}")
+    if max_n is not None and img.shape[0] > max_n:
+        raise ValueError(count_message.format(img.shape[0]))
+    return np.ascontiguousarray(img)
+
+
 def default_options(lib=None) -> CbaOptions:
     o = CbaOptions()
     (lib or load_library()).cba_options_default(C.byref(o))

@@ -1,14 +1,12 @@
 // blob_detect.hip — circle (blob) detection on the GPU (blob_math.hpp, calibba.h: cba_blob_detector).  One stream and one synchronise
 // per call:
 //   k_blob_response<WIDE>  a workgroup of four wavefronts owns a tile of BLB_TX x BLB_TY pixels of one image and stages the tile and its
-//                          15-pixel halo as bytes in LDS (zeros outside the image).  WIDE (the width is a multiple of 16, so every row
-//                          starts on a 16-byte boundary): 16-byte loads of the aligned vectors that cover the tile; otherwise single
-//                          bytes.  Both stay inside [0, n_images W H).  Horizontal pass: a lane owns 4 adjacent pixels of a staged
-//                          row; the first pixel's two window sums are v_sad_u8 against zero over the masked dwords of the window (a
-//                          loop over LDS with run-time bounds), the other three slide by one byte in and one out; the sums go back to
-//                          LDS as uint16 (8-byte stores).  Vertical pass: a lane owns 4 adjacent pixels of a tile row and adds the
-//                          rows -b .. b of the outer sums and -a .. a of the inner ones (8-byte LDS reads).  R leaves as int32 (one
-//                          16-byte store per lane when the width is a multiple of 4) and S_in as uint16 (one 8-byte store).
+//                          15-pixel halo as bytes in LDS (stage_tile of image_tile.hpp, the whole pitch).  Horizontal pass: a lane
+//                          owns 4 adjacent pixels of a staged row; the first pixel's two window sums are v_sad_u8 against zero over
+//                          the masked dwords of the window (a loop over LDS with run-time bounds), the other three slide by one byte
+//                          in and one out; the sums go back to LDS as uint16 (8-byte stores).  Vertical pass: a lane owns 4 adjacent
+//                          pixels of a tile row and adds the rows -b .. b of the outer sums and -a .. a of the inner ones (8-byte LDS
+//                          reads).  R leaves as int32 and S_in as uint16 (store4).
 //   k_peak_walk, k_peak_prefix  the row-major peak list of peak_walk.hpp (shared with corner_detect.hip), instantiated for int32
 //                          responses, strips of BLB_SH rows and the border outer_half.
 //   k_blob_refine          one lane per slot (image, blob), grid-stride: blob_refine_one; slots past the kept blobs get NaN / 0.
@@ -21,6 +19,7 @@
 
 #include "pipelines.hpp"
 #include "blob_math.hpp"
+#include "image_tile.hpp"
 #include "peak_walk.hpp"
 
 namespace cba {
@@ -63,30 +62,9 @@ __global__ __launch_bounds__(BLB_BLOCK) void k_blob_response(BlobRespArgs a) {
     __shared__ __align__(16) uint8_t tile[BLB_ROWS * BLB_PITCH];
     __shared__ __align__(8) uint16_t hin[BLB_ROWS * BLB_TX], hout[BLB_ROWS * BLB_TX];
     const int W = a.W, H = a.H, ha = a.a, hb = a.b;
-    int blk = blockIdx.x;
-    const int tx = blk % a.tiles_x;
-    blk /= a.tiles_x;
-    const int ty = blk % a.tiles_y, im = blk / a.tiles_y;
-    const int x0 = tx * BLB_TX, y0 = ty * BLB_TY;
-    const int64_t fbase = static_cast<int64_t>(im) * W * H;
+    const auto [x0, y0, im, fbase] = tile_decode<BLB_TX, BLB_TY>(a.tiles_x, a.tiles_y, W, H);
     const int tid = static_cast<int>(threadIdx.x);
-    if constexpr (WIDE) {
-        constexpr int VPR = BLB_PITCH / 16;
-        for (int i = tid; i < BLB_ROWS * VPR; i += BLB_BLOCK) {
-            const int row = i / VPR, v = i - row * VPR;
-            const int y = y0 - BLB_HALO + row, x = x0 - BLB_LEFT + 16 * v;  // x and W are multiples of 16: all in or all out
-            uint4 q = make_uint4(0u, 0u, 0u, 0u);
-            if (y >= 0 && y < H && x >= 0 && x < W) q = *reinterpret_cast<const uint4*>(a.img + fbase + static_cast<int64_t>(y) * W + x);
-            *reinterpret_cast<uint4*>(tile + row * BLB_PITCH + 16 * v) = q;
-        }
-    } else {
-        for (int i = tid; i < BLB_ROWS * BLB_PITCH; i += BLB_BLOCK) {
-            const int row = i / BLB_PITCH, c = i - row * BLB_PITCH;
-            const int y = y0 - BLB_HALO + row, x = x0 - BLB_LEFT + c;
-            const bool in = y >= 0 && y < H && x >= 0 && x < W;
-            tile[i] = in ? a.img[fbase + static_cast<int64_t>(y) * W + x] : uint8_t(0);
-        }
-    }
+    stage_tile<BLB_TX, BLB_TY, BLB_HALO, BLB_LEFT, BLB_PITCH, BLB_BLOCK, WIDE>(tile, a.img, fbase, x0, y0, W, H, tid);  // the whole pitch
     __syncthreads();
     // horizontal sums of the staged rows BLB_HALO - b .. BLB_HALO + BLB_TY - 1 + b, 16 lanes x 4 pixels each
     const int r_lo = BLB_HALO - hb, n_items = (BLB_TY + 2 * hb) * 16;
@@ -137,18 +115,7 @@ __global__ __launch_bounds__(BLB_BLOCK) void k_blob_response(BlobRespArgs a) {
     };
     const int o0 = resp(ob0, in0, x), o1 = resp(ob1, in1, x + 1), o2 = resp(ob2, in2, x + 2), o3 = resp(ob3, in3, x + 3);
     const int64_t at = fbase + static_cast<int64_t>(y) * W + x;
-    int32_t* dst = a.resp + at;
-    uint16_t* dsi = a.s_in + at;
-    if ((W & 3) == 0) {  // x + 3 < W, and the addresses are multiples of 16 and of 8 bytes
-        *reinterpret_cast<int4*>(dst) = make_int4(o0, o1, o2, o3);
-        *reinterpret_cast<uint2*>(dsi) = make_uint2(in0 | in1 << 16, in2 | in3 << 16);
-    } else {
-        dst[0] = o0;
-        dsi[0] = static_cast<uint16_t>(in0);
-        if (x + 1 < W) { dst[1] = o1; dsi[1] = static_cast<uint16_t>(in1); }
-        if (x + 2 < W) { dst[2] = o2; dsi[2] = static_cast<uint16_t>(in2); }
-        if (x + 3 < W) { dst[3] = o3; dsi[3] = static_cast<uint16_t>(in3); }
-    }
+    store4(x, W, Px4<int32_t, int>{a.resp + at, {o0, o1, o2, o3}}, Px4<uint16_t, uint32_t>{a.s_in + at, {in0, in1, in2, in3}});
 }
 
 struct BlobRefineArgs {
@@ -168,14 +135,12 @@ struct BlobRefineArgs {
 
 __global__ __launch_bounds__(BLB_BLOCK) void k_blob_refine(BlobRefineArgs a) {
     for (int i = blockIdx.x * BLB_BLOCK + threadIdx.x; i < a.n_slots; i += gridDim.x * BLB_BLOCK) {
-        const int im = i / a.max_blobs, slot = i - im * a.max_blobs;
+        const SlotAt s = slot_at(i, a.max_blobs, a.count, a.peak_px, a.W, a.H);
         double xy[2] = {NAN, NAN}, shape[3] = {NAN, NAN, NAN}, err = NAN;
         int flags = 0, response = 0;
-        if (slot < min(a.count[im], a.max_blobs)) {
-            const int p = a.peak_px[i], py = p / a.W, px = p - py * a.W;
-            const int64_t fbase = static_cast<int64_t>(im) * a.W * a.H;
-            response = a.resp[fbase + p];
-            flags = blob_refine_one(a.img + fbase, a.W, a.H, px, py, response, a.s_in[fbase + p], a.a, a.b, a.polarity, a.max_radius,
+        if (s.kept) {
+            response = a.resp[s.fbase + s.p];
+            flags = blob_refine_one(a.img + s.fbase, a.W, a.H, s.px, s.py, response, a.s_in[s.fbase + s.p], a.a, a.b, a.polarity, a.max_radius,
                                     a.rounds, a.rays, xy, shape, &err);
         }
         a.xy[2 * i] = xy[0];
@@ -192,47 +157,30 @@ __global__ __launch_bounds__(BLB_BLOCK) void k_blob_refine(BlobRefineArgs a) {
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
 // The detector: options fixed at create, every buffer (the host staging of what the number flags read included) sized for max_images
 // there.  Every call ends with its stream synchronised.
-struct BlobDetector : DeviceHandle {
-    using DeviceHandle::DeviceHandle;
+struct BlobDetector : DetectorFrame {
+    using DetectorFrame::DetectorFrame;
     cba_blob_options opts;
-    int W = 0, H = 0, max_images = 0, max_blobs = 0;
-    int tiles_x = 0, tiles_y = 0, strips = 0;
-    DevBuf<uint8_t> img;
     DevBuf<int32_t> resp;
     DevBuf<uint16_t> s_in;
-    DevBuf<int32_t> strip_count, strip_off, count, status, peak_px, response, flags;
-    DevBuf<double> rays, xy, shape, fit_error;
+    DevBuf<double> rays, shape, fit_error;
     std::vector<double> h_xy, h_shape, h_fit;
-    std::vector<int32_t> h_count, h_flags;
+    std::vector<int32_t> h_flags;
 };
 static_assert(!std::is_copy_constructible_v<BlobDetector> && !std::is_copy_assignable_v<BlobDetector>, "a handle owns its stream and buffers");
 
 BlobDetector* blob_detector_create(int W, int H, int max_images, int max_blobs, const cba_blob_options& o, int device) {
     auto h = std::make_unique<BlobDetector>(device);
     h->opts = o;
-    h->W = W; h->H = H; h->max_images = max_images; h->max_blobs = max_blobs;
-    h->tiles_x = (W + BLB_TX - 1) / BLB_TX;
-    h->tiles_y = (H + BLB_TY - 1) / BLB_TY;
-    h->strips = (H + BLB_SH - 1) / BLB_SH;
+    h->alloc(W, H, max_images, max_blobs, BLB_TX, BLB_TY, BLB_SH);
     const size_t px = static_cast<size_t>(max_images) * W * H, slots = static_cast<size_t>(max_images) * max_blobs;
-    h->img.alloc(px);
     h->resp.alloc(px);
     h->s_in.alloc(px);
-    h->strip_count.alloc(static_cast<size_t>(max_images) * h->strips);
-    h->strip_off.alloc(static_cast<size_t>(max_images) * h->strips);
-    h->count.alloc(max_images);
-    h->status.alloc(max_images);
-    h->peak_px.alloc(slots);
-    h->response.alloc(slots);
-    h->flags.alloc(slots);
-    h->xy.alloc(2 * slots);
     h->shape.alloc(3 * slots);
     h->fit_error.alloc(slots);
     h->h_xy.resize(2 * slots);
     h->h_shape.resize(3 * slots);
     h->h_fit.resize(slots);
     h->h_flags.resize(slots);
-    h->h_count.resize(max_images);
     std::vector<double> rays(2 * BLOB_RAYS);
     blob_ray_table(rays.data());
     const hipStream_t s = h->lease;
@@ -248,48 +196,33 @@ void blob_detector_process(BlobDetector* h, int n_images, const uint8_t* images,
                            double* out_shape, double* out_fit_error, int32_t* out_response, int32_t* out_flags, double* stage_ms) {
     const hipStream_t s = h->begin();
     const cba_blob_options& o = h->opts;
-    const size_t px = static_cast<size_t>(n_images) * h->W * h->H, slots = static_cast<size_t>(n_images) * h->max_blobs;
+    const size_t slots = static_cast<size_t>(n_images) * h->max_items;
     StageTimer<6> tm(s, stage_ms != nullptr);
-    tm.mark(0);
-    h->img.upload(images, px, s);
-    tm.mark(1);
-    BlobRespArgs ra{h->img.p, h->resp.p, h->s_in.p, h->W, h->H, h->tiles_x, h->tiles_y, o.inner_half, o.outer_half, o.polarity};
-    const dim3 rgrid(static_cast<unsigned>(n_images * h->tiles_x * h->tiles_y));
-    if (h->W % 16 == 0) hipLaunchKernelGGL(k_blob_response<true>, rgrid, dim3(BLB_BLOCK), 0, s, ra);
-    else hipLaunchKernelGGL(k_blob_response<false>, rgrid, dim3(BLB_BLOCK), 0, s, ra);
-    CBA_HIP(hipGetLastError());
-    tm.mark(2);
-    PeakArgs<int32_t> pa{h->resp.p, h->W, h->H, h->strips, o.outer_half, blob_threshold(o.inner_half, o.outer_half, o.min_contrast),
-                         o.nms_radius, h->max_blobs, h->strip_count.p, h->strip_off.p, h->peak_px.p};
-    peak_walk_launch<int32_t, BLB_SH>(s, n_images, pa, h->count.p, h->status.p);
-    tm.mark(3);
-    BlobRefineArgs fa{h->img.p, h->resp.p, h->s_in.p, h->W, h->H, static_cast<int>(slots), h->max_blobs, o.inner_half, o.outer_half,
+    const BlobRespArgs ra{h->img.p, h->resp.p, h->s_in.p, h->W, h->H, h->tiles_x, h->tiles_y, o.inner_half, o.outer_half, o.polarity};
+    const PeakArgs<int32_t> pa{h->resp.p, h->W, h->H, h->strips, o.outer_half, blob_threshold(o.inner_half, o.outer_half, o.min_contrast),
+                               o.nms_radius, h->max_items, h->strip_count.p, h->strip_off.p, h->peak_px.p};
+    h->find_peaks<BLB_SH>(tm, s, n_images, images, k_blob_response<true>, k_blob_response<false>, BLB_BLOCK, ra, pa);
+    BlobRefineArgs fa{h->img.p, h->resp.p, h->s_in.p, h->W, h->H, static_cast<int>(slots), h->max_items, o.inner_half, o.outer_half,
                       o.polarity, o.max_radius, o.rounds, h->count.p, h->peak_px.p, h->rays.p, h->xy.p, h->shape.p, h->fit_error.p,
                       h->response.p, h->flags.p};
-    const int fgrid = launch_grid(static_cast<int64_t>(slots), BLB_BLOCK, BLB_GRID);
-    hipLaunchKernelGGL(k_blob_refine, dim3(fgrid), dim3(BLB_BLOCK), 0, s, fa);
+    hipLaunchKernelGGL(k_blob_refine, dim3(launch_grid(static_cast<int64_t>(slots), BLB_BLOCK, BLB_GRID)), dim3(BLB_BLOCK), 0, s, fa);
     CBA_HIP(hipGetLastError());
-    tm.mark(4);
-    h->count.download(h->h_count.data(), n_images, s);
-    if (out_status) h->status.download(out_status, n_images, s);
+    h->fetch_counts(tm, s, n_images, out_status);
     if (out_response) h->response.download(out_response, slots, s);
     h->xy.download(h->h_xy.data(), 2 * slots, s);
     h->shape.download(h->h_shape.data(), 3 * slots, s);
     h->fit_error.download(h->h_fit.data(), slots, s);
     h->flags.download(h->h_flags.data(), slots, s);
-    tm.mark(5);
-    CBA_HIP(hipStreamSynchronize(s));
+    h->finish(tm, s, n_images, out_count, stage_ms);
     for (int im = 0; im < n_images; ++im) {
-        if (out_count) out_count[im] = h->h_count[im];
-        const size_t at = static_cast<size_t>(im) * h->max_blobs;
-        blob_number_flags(std::min(h->h_count[im], h->max_blobs), &h->h_xy[2 * at], &h->h_shape[3 * at], &h->h_fit[at], o.max_fit_error,
+        const size_t at = static_cast<size_t>(im) * h->max_items;
+        blob_number_flags(std::min(h->h_count[im], h->max_items), &h->h_xy[2 * at], &h->h_shape[3 * at], &h->h_fit[at], o.max_fit_error,
                           o.max_axis_ratio, o.min_radius, &h->h_flags[at]);
     }
     if (out_xy) std::copy(h->h_xy.begin(), h->h_xy.begin() + 2 * slots, out_xy);
     if (out_shape) std::copy(h->h_shape.begin(), h->h_shape.begin() + 3 * slots, out_shape);
     if (out_fit_error) std::copy(h->h_fit.begin(), h->h_fit.begin() + slots, out_fit_error);
     if (out_flags) std::copy(h->h_flags.begin(), h->h_flags.begin() + slots, out_flags);
-    tm.report(stage_ms);
 }
 
 void blob_detector_destroy(BlobDetector* h) noexcept { destroy_handle(h); }

@@ -18,6 +18,15 @@
 
 using namespace cba;
 
+#ifdef CBA_EXPERIMENTS
+// a _timed entry point: its stage_ms must not be NULL
+template <typename F>
+static cba_status timed(const double* stage_ms, F&& call) {
+    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
+    return call();
+}
+#endif
+
 extern "C" {
 
 // ---- checks shared by the sections below --------------------------------------------------------------------------------------
@@ -25,12 +34,34 @@ extern "C" {
 static void check_camera(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs) {
     if (camera_model != CBA_CAMERA_PINHOLE_BC && camera_model != CBA_CAMERA_SCHEIMPFLUG) throw std::invalid_argument("bad camera model");
     if (!intr) throw std::invalid_argument("null argument");
-    if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV))
-        throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
+    if (inverse_coeffs && (n_inverse_coeffs < 2 || n_inverse_coeffs > LS_MAX_INV)) throw std::invalid_argument("n_inverse_coeffs must be in [2, 16]");
+}
+static void check_sides(int32_t w, int32_t h) {
+    if (std::min(w, h) < 1 || std::max(w, h) > CBA_IMAGE_MAX_SIDE) throw std::invalid_argument("image width and height must be in [1, 32768]");
 }
 
-static void check_side(int32_t s) {
-    if (s < 1 || s > CBA_IMAGE_MAX_SIDE) throw std::invalid_argument("image width and height must be in [1, 32768]");
+// the sizes of a handle for batches of images; name: "max_images" / "max_pairs".  The detectors check their sides first and their
+// options before the rest, so they call check_sides themselves as well: here it then passes.
+static void check_image_batch(int32_t width, int32_t height, int32_t max_n, const char* name) {
+    check_sides(width, height);
+    if (max_n < 1) throw std::invalid_argument(std::string(name) + " must be >= 1");
+    if (static_cast<int64_t>(max_n) * width * height > 0x7fffffff) throw std::invalid_argument(std::string(name) + " is too large");
+}
+
+// the peak list of a detector; name: "max_corners" / "max_blobs"
+static void check_peak_capacity(int32_t max_images, int32_t max_items, const char* name) {
+    if (max_items < 1 || static_cast<int64_t>(max_images) * max_items > (1 << 28))
+        throw std::invalid_argument(std::string(name) + " must be >= 1 and max_images " + name + " <= 2^28");
+}
+
+// The start of a handle's process call, after the null-handle test: n in [0, max_n] (what: "frames" / "pairs" / "images"), then the
+// call's own check (other: its message when it fails, else nullptr), then false when n == 0 leaves nothing to do, then the images.
+static bool check_batch_call(int32_t n, int32_t max_n, const char* what, const char* other, bool have_images) {
+    if (n < 0 || n > max_n) throw std::invalid_argument(std::string("n_") + what + " must be in [0, max_" + what + "]");
+    if (other) throw std::invalid_argument(other);
+    if (n == 0) return false;
+    if (!have_images) throw std::invalid_argument("null argument");
+    return true;
 }
 
 // ---- laser-plane calibration (linescan.hip) --------------------------------------------------------------------------------
@@ -97,9 +128,8 @@ __attribute__((visibility("default"))) cba_status cba_calibrate_laser_plane_time
     int32_t camera_model, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs, int32_t n_views, const int64_t* target_offset,
     const double* X, const double* Y, const double* u, const double* v, const int64_t* laser_offset, const double* laser_u, const double* laser_v,
     const cba_plane_fit_options* opts, cba_laser_plane_result* result, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v, laser_offset, laser_u,
-                            laser_v, opts, result, nullptr, nullptr, stage_ms);
+    return timed(stage_ms, [&] { return laser_plane_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n_views, target_offset, X, Y, u, v,
+                                                         laser_offset, laser_u, laser_v, opts, result, nullptr, nullptr, stage_ms); });
 }
 #endif
 
@@ -260,10 +290,9 @@ __attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_timed(
     int32_t n_views, const int64_t* view_offset, const double* X, const double* Y, const double* u, const double* v, int32_t use_ransac,
     const cba_ransac_options* ransac, int32_t* success, double* kmtx5, int32_t* view_ok, double* h9, double* forward_rms_px, double* rt12,
     int32_t* pose_ok, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
     int32_t sanitized = 0;
-    return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, nullptr, nullptr, success, kmtx5, &sanitized,
-                                    view_ok, h9, forward_rms_px, rt12, pose_ok, nullptr, stage_ms);
+    return timed(stage_ms, [&] { return estimate_intrinsics_impl(n_views, view_offset, X, Y, u, v, use_ransac, ransac, nullptr, nullptr, success, kmtx5,
+                                                                 &sanitized, view_ok, h9, forward_rms_px, rt12, pose_ok, nullptr, stage_ms); });
 }
 #endif
 
@@ -305,7 +334,6 @@ cba_status cba_sanitize_intrinsics(const double* kmtx5, const double* bounds_lo5
         *modified = hr_sanitize(kmtx5, bounds_lo5, bounds_hi5, out5) ? 1 : 0;
     });
 }
-
 
 // ---- linear seed of a multi-camera rig (extrinsic_dlt.hip, extrinsic_dlt_math.hpp) -------------------------------------------
 static cba_status extrinsic_dlt_impl(int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view,
@@ -513,9 +541,8 @@ cba_status cba_estimate_intrinsics_linear_iterative_batch(int32_t n_problems, co
 __attribute__((visibility("default"))) cba_status cba_estimate_extrinsic_dlt_timed(
     int32_t n_cams, int32_t n_views, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_view, const int32_t* blk_cam,
     const double* X, const double* Y, const double* u, const double* v, const double* kmtx5, double* c_T_r, double* r_T_t, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t, nullptr, nullptr,
-                              stage_ms);
+    return timed(stage_ms, [&] { return extrinsic_dlt_impl(n_cams, n_views, n_blocks, blk_offset, blk_view, blk_cam, X, Y, u, v, kmtx5, c_T_r, r_T_t,
+                                                           nullptr, nullptr, stage_ms); });
 }
 
 // Experiment builds only (tools/bench_bundle_seed.py): cba_estimate_bundle_seed timing its stages on the device: stage_ms [6] =
@@ -525,27 +552,24 @@ __attribute__((visibility("default"))) cba_status cba_estimate_bundle_seed_timed
     int32_t n_cams, int32_t n_blocks, const int64_t* blk_offset, const int32_t* blk_cam, const double* blk_b_T_g, const double* X,
     const double* Y, const double* u, const double* v, const double* kmtx5, double min_angle_deg, double* g_T_c, int32_t* cam_status,
     int32_t* cam_pairs, double* b_T_t, int32_t* target_source, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, nullptr, nullptr, nullptr,
-                            g_T_c, cam_status, cam_pairs, b_T_t, target_source, nullptr, nullptr, stage_ms);
+    return timed(stage_ms, [&] { return bundle_seed_impl(n_cams, n_blocks, blk_offset, blk_cam, blk_b_T_g, X, Y, u, v, kmtx5, min_angle_deg, nullptr, nullptr,
+                                                         nullptr, g_T_c, cam_status, cam_pairs, b_T_t, target_source, nullptr, nullptr, stage_ms); });
 }
 // Experiment builds only (tools/bench_distortion.py): the distortion fit and the iterative estimator timing their stages on the
 // device: stage_ms [6] = moment passes, chunk sums, uploads, tail, residuals, total without uploads.  Not part of calibba.h.
 __attribute__((visibility("default"))) cba_status cba_fit_distortion_batch_timed(
     int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, const double* kmtx5,
     int32_t num_radial, int32_t dual, double* coeffs, double* inverse, int32_t* ok, double* residuals, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, 0, nullptr, nullptr, dual, coeffs, inverse, ok, residuals,
-                               stage_ms);
+    return timed(stage_ms, [&] { return fit_distortion_impl(n_problems, offset, x, y, u, v, kmtx5, num_radial, 0, nullptr, nullptr, dual, coeffs, inverse,
+                                                            ok, residuals, stage_ms); });
 }
 
 __attribute__((visibility("default"))) cba_status cba_estimate_intrinsics_linear_iterative_batch_timed(
     int32_t n_problems, const int64_t* offset, const double* x, const double* y, const double* u, const double* v, int32_t num_radial,
     int32_t max_iterations, int32_t use_skew, double* kmtx5, double* coeffs, int32_t* status, int32_t* iterations, int32_t* fallback,
     double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status, iterations,
-                                 fallback, stage_ms);
+    return timed(stage_ms, [&] { return linear_iterative_impl(n_problems, offset, x, y, u, v, num_radial, max_iterations, use_skew, kmtx5, coeffs, status,
+                                                              iterations, fallback, stage_ms); });
 }
 #endif
 
@@ -589,8 +613,7 @@ static cba_status undistort_map_create_impl(int32_t camera_model, int32_t n_cams
         *out = nullptr;
         check_camera(camera_model, intr, 0, nullptr);
         if (n_cams < 1) throw std::invalid_argument("n_cams must be >= 1");
-        check_side(width);
-        check_side(height);
+        check_sides(width, height);
         const int ni = cam_intr_size(camera_model);
         for (int c = 0; c < n_cams; ++c) {
             const double* k = new_k5 ? new_k5 + 5 * static_cast<size_t>(c) : intr + static_cast<size_t>(c) * ni;
@@ -618,8 +641,7 @@ static cba_status undistort_map_apply_impl(cba_undistort_map* h, int32_t n_image
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         if (n_images < 0) throw std::invalid_argument("n_images must be >= 0");
-        check_side(src_width);
-        check_side(src_height);
+        check_sides(src_width, src_height);
         if (channels < 1 || channels > 4) throw std::invalid_argument("channels must be in 1..4");
         if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
         if (n_images == 0) return;
@@ -644,28 +666,24 @@ void cba_undistort_map_destroy(cba_undistort_map* h) { undistort_map_destroy(rei
 // kernel, download.  Not part of calibba.h.
 __attribute__((visibility("default"))) cba_status cba_camera_project_timed(int32_t camera_model, const double* intr, int64_t n,
                                                                            const double* xyz, double* uv, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return camera_project_impl(camera_model, intr, n, xyz, uv, stage_ms);
+    return timed(stage_ms, [&] { return camera_project_impl(camera_model, intr, n, xyz, uv, stage_ms); });
 }
 __attribute__((visibility("default"))) cba_status cba_camera_unproject_timed(int32_t camera_model, const double* intr, int32_t n_inverse_coeffs,
                                                                              const double* inverse_coeffs, int64_t n, const double* uv,
                                                                              double* xy, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, stage_ms);
+    return timed(stage_ms, [&] { return camera_unproject_impl(camera_model, intr, n_inverse_coeffs, inverse_coeffs, n, uv, xy, stage_ms); });
 }
 __attribute__((visibility("default"))) cba_status cba_undistort_map_create_timed(int32_t camera_model, int32_t n_cams, const double* intr,
                                                                                  const double* R, const double* new_k5, int32_t width,
                                                                                  int32_t height, int32_t device, cba_undistort_map** out,
                                                                                  double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, stage_ms);
+    return timed(stage_ms, [&] { return undistort_map_create_impl(camera_model, n_cams, intr, R, new_k5, width, height, device, out, stage_ms); });
 }
 __attribute__((visibility("default"))) cba_status cba_undistort_map_apply_timed(cba_undistort_map* h, int32_t n_images, const int32_t* cam,
                                                                                 int32_t src_width, int32_t src_height, int32_t channels,
                                                                                 int32_t dtype, double border, const void* src, void* dst,
                                                                                 double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms);
+    return timed(stage_ms, [&] { return undistort_map_apply_impl(h, n_images, cam, src_width, src_height, channels, dtype, border, src, dst, stage_ms); });
 }
 #endif
 
@@ -718,9 +736,8 @@ __attribute__((visibility("default"))) cba_status cba_triangulate_timed(int32_t 
                                                                         const cba_triangulate_options* opts, double* xyz, double* rms_px,
                                                                         uint32_t* used_mask, int32_t* status, double* cov6,
                                                                         int32_t* linearisations, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px, used_mask, status,
-                            cov6, linearisations, stage_ms);
+    return timed(stage_ms, [&] { return triangulate_impl(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, n, uv, opts, xyz, rms_px,
+                                                         used_mask, status, cov6, linearisations, stage_ms); });
 }
 #endif
 
@@ -773,8 +790,7 @@ cba_status cba_laser_scanner_create(int32_t camera_model, const double* intr, in
         check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
         check_laser_plane(plane);
         if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
+        check_sides(width, height);
         if (max_frames < 1) throw std::invalid_argument("max_frames must be >= 1");
         if (opts->axis != 0 && opts->axis != 1) throw std::invalid_argument("axis must be 0 or 1");
         const int32_t side = opts->axis == 0 ? height : width;
@@ -796,10 +812,8 @@ static cba_status laser_scanner_process_impl(cba_laser_scanner* h, int32_t n_fra
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         LaserScanner* sc = reinterpret_cast<LaserScanner*>(h);
-        if (n_frames < 0 || n_frames > laser_scanner_max_frames(sc)) throw std::invalid_argument("n_frames must be in [0, max_frames]");
-        if (dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32) throw std::invalid_argument("unknown dtype");
-        if (n_frames == 0) return;
-        if (!images) throw std::invalid_argument("null argument");
+        const char* bad_dtype = dtype != CBA_DTYPE_U8 && dtype != CBA_DTYPE_F32 ? "unknown dtype" : nullptr;
+        if (!check_batch_call(n_frames, laser_scanner_max_frames(sc), "frames", bad_dtype, images != nullptr)) return;
         laser_scanner_process(sc, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
     });
 }
@@ -818,8 +832,7 @@ __attribute__((visibility("default"))) cba_status cba_laser_scanner_process_time
                                                                                   const void* images, const double* frame_pose7,
                                                                                   double* centre, double* amplitude, double* width_px,
                                                                                   double* xyz, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms);
+    return timed(stage_ms, [&] { return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms); });
 }
 #endif
 
@@ -839,15 +852,19 @@ cba_status cba_stereo_rectify(int32_t camera_model, const double* intr, const do
     return guarded([&] {
         check_camera(camera_model, intr, 0, nullptr);
         if (!c_T_r || !opts || !R || !new_k5 || !baseline || !r_T_rect) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
+        check_sides(width, height);
         const char* err = stereo_rectify(intr, cam_intr_size(camera_model), c_T_r, width, height, opts->focal, opts->cx,
                                          opts->cy, R, new_k5, baseline, r_T_rect);
         if (err) throw std::invalid_argument(err);
     });
 }
 
+// g == NULL: no geometry, which a pose cannot go with (the matchers; cba_stereo_points requires g before it calls)
 static void check_stereo_geometry(const cba_stereo_geometry* g, const double* pose7) {
+    if (!g) {
+        if (pose7) throw std::invalid_argument("a pose needs a geometry");
+        return;
+    }
     if (!std::isfinite(g->focal) || !std::isfinite(g->cx) || !std::isfinite(g->cy) || !std::isfinite(g->baseline))
         throw std::invalid_argument("the stereo geometry must be finite");
     if (!(g->focal > 0.0) || !(g->baseline > 0.0)) throw std::invalid_argument("focal and baseline must be > 0");
@@ -856,24 +873,29 @@ static void check_stereo_geometry(const cba_stereo_geometry* g, const double* po
             if (!std::isfinite(pose7[k])) throw std::invalid_argument("the pose must be finite");
 }
 
+// the disparity options both matchers have, in two parts: each matcher checks options of its own between them, in the order it shipped
+static void check_disparity_range(int32_t min_disparity, int32_t num_disparities) {
+    if (min_disparity < -32768 || min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
+    if (num_disparities < 1 || num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
+}
+static void check_disparity_selection(int32_t uniqueness_percent, int32_t lr_max_diff, int32_t subpixel) {
+    if (uniqueness_percent < 0 || uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
+    if (lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
+    if (subpixel != 0 && subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
+}
+static const char NO_GEOMETRY[] = "xyz needs a matcher created with a geometry";
+
 cba_status cba_stereo_matcher_create(int32_t width, int32_t height, int32_t max_pairs, const cba_stereo_match_options* opts,
                                      const cba_stereo_geometry* geometry, const double* pose7, int32_t device, cba_stereo_matcher** out) {
     return guarded([&] {
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
         if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        if (max_pairs < 1) throw std::invalid_argument("max_pairs must be >= 1");
-        if (static_cast<int64_t>(max_pairs) * width * height > 0x7fffffff) throw std::invalid_argument("max_pairs is too large");
-        if (opts->min_disparity < -32768 || opts->min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
-        if (opts->num_disparities < 1 || opts->num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
+        check_image_batch(width, height, max_pairs, "max_pairs");
+        check_disparity_range(opts->min_disparity, opts->num_disparities);
         if (opts->half_window < 1 || opts->half_window > 10) throw std::invalid_argument("half_window must be in 1..10");
-        if (opts->uniqueness_percent < 0 || opts->uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
-        if (opts->lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
-        if (opts->subpixel != 0 && opts->subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
-        if (pose7 && !geometry) throw std::invalid_argument("a pose needs a geometry");
-        if (geometry) check_stereo_geometry(geometry, pose7);
+        check_disparity_selection(opts->uniqueness_percent, opts->lr_max_diff, opts->subpixel);
+        check_stereo_geometry(geometry, pose7);
         require_device(device);
         *out = reinterpret_cast<cba_stereo_matcher*>(stereo_matcher_create(width, height, max_pairs, *opts, geometry, pose7, device));
     });
@@ -884,10 +906,8 @@ static cba_status stereo_matcher_process_impl(cba_stereo_matcher* h, int32_t n_p
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         StereoMatcher* m = reinterpret_cast<StereoMatcher*>(h);
-        if (n_pairs < 0 || n_pairs > stereo_matcher_max_pairs(m)) throw std::invalid_argument("n_pairs must be in [0, max_pairs]");
-        if (xyz && !stereo_matcher_has_geometry(m)) throw std::invalid_argument("xyz needs a matcher created with a geometry");
-        if (n_pairs == 0) return;
-        if (!left || !right) throw std::invalid_argument("null argument");
+        const char* no_geometry = xyz && !stereo_matcher_has_geometry(m) ? NO_GEOMETRY : nullptr;
+        if (!check_batch_call(n_pairs, stereo_matcher_max_pairs(m), "pairs", no_geometry, left && right)) return;
         stereo_matcher_process(m, n_pairs, left, right, disparity, cost, xyz, stage_ms);
     });
 }
@@ -918,8 +938,7 @@ __attribute__((visibility("default"))) cba_status cba_stereo_matcher_process_tim
                                                                                    const uint8_t* left, const uint8_t* right,
                                                                                    float* disparity, int32_t* cost, float* xyz,
                                                                                    double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+    return timed(stage_ms, [&] { return stereo_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms); });
 }
 #endif
 
@@ -943,23 +962,16 @@ cba_status cba_sgm_matcher_create(int32_t width, int32_t height, int32_t max_pai
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
         if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
-        if (max_pairs < 1) throw std::invalid_argument("max_pairs must be >= 1");
-        if (static_cast<int64_t>(max_pairs) * width * height > 0x7fffffff) throw std::invalid_argument("max_pairs is too large");
-        if (opts->min_disparity < -32768 || opts->min_disparity > 32768) throw std::invalid_argument("|min_disparity| must be <= 32768");
-        if (opts->num_disparities < 1 || opts->num_disparities > 256) throw std::invalid_argument("num_disparities must be in 1..256");
+        check_image_batch(width, height, max_pairs, "max_pairs");
+        check_disparity_range(opts->min_disparity, opts->num_disparities);
         if (opts->p2 < 0 || opts->p2 > 1023) throw std::invalid_argument("p2 must be in 0..1023");
         if (opts->p1 < 0 || opts->p1 > opts->p2) throw std::invalid_argument("p1 must be in 0..p2");
         if (opts->paths != 4 && opts->paths != 8) throw std::invalid_argument("paths must be 4 or 8");
-        if (opts->uniqueness_percent < 0 || opts->uniqueness_percent > 100) throw std::invalid_argument("uniqueness_percent must be in 0..100");
-        if (opts->lr_max_diff < -1) throw std::invalid_argument("lr_max_diff must be >= -1");
-        if (opts->subpixel != 0 && opts->subpixel != 1) throw std::invalid_argument("subpixel must be 0 or 1");
+        check_disparity_selection(opts->uniqueness_percent, opts->lr_max_diff, opts->subpixel);
         if (opts->workspace_mb < 0 || opts->workspace_mb > CBA_SGM_MAX_WORKSPACE_MB) throw std::invalid_argument("workspace_mb must be in 0..1048576");
         if (static_cast<int64_t>(width) * height * opts->num_disparities > CBA_SGM_MAX_VOLUME)
             throw std::invalid_argument("width height num_disparities must be <= 2^31");
-        if (pose7 && !geometry) throw std::invalid_argument("a pose needs a geometry");
-        if (geometry) check_stereo_geometry(geometry, pose7);
+        check_stereo_geometry(geometry, pose7);
         require_device(device);
         *out = reinterpret_cast<cba_sgm_matcher*>(sgm_matcher_create(width, height, max_pairs, *opts, geometry, pose7, device));
     });
@@ -970,10 +982,8 @@ static cba_status sgm_matcher_process_impl(cba_sgm_matcher* h, int32_t n_pairs, 
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         SgmMatcher* m = reinterpret_cast<SgmMatcher*>(h);
-        if (n_pairs < 0 || n_pairs > sgm_matcher_max_pairs(m)) throw std::invalid_argument("n_pairs must be in [0, max_pairs]");
-        if (xyz && !sgm_matcher_has_geometry(m)) throw std::invalid_argument("xyz needs a matcher created with a geometry");
-        if (n_pairs == 0) return;
-        if (!left || !right) throw std::invalid_argument("null argument");
+        const char* no_geometry = xyz && !sgm_matcher_has_geometry(m) ? NO_GEOMETRY : nullptr;
+        if (!check_batch_call(n_pairs, sgm_matcher_max_pairs(m), "pairs", no_geometry, left && right)) return;
         sgm_matcher_process(m, n_pairs, left, right, disparity, cost, xyz, stage_ms);
     });
 }
@@ -991,8 +1001,7 @@ void cba_sgm_matcher_destroy(cba_sgm_matcher* h) { sgm_matcher_destroy(reinterpr
 __attribute__((visibility("default"))) cba_status cba_sgm_matcher_process_timed(cba_sgm_matcher* h, int32_t n_pairs, const uint8_t* left,
                                                                                 const uint8_t* right, float* disparity, int32_t* cost,
                                                                                 float* xyz, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return sgm_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms);
+    return timed(stage_ms, [&] { return sgm_matcher_process_impl(h, n_pairs, left, right, disparity, cost, xyz, stage_ms); });
 }
 #endif
 
@@ -1013,13 +1022,10 @@ cba_status cba_corner_detector_create(int32_t width, int32_t height, int32_t max
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
         if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
+        check_sides(width, height);
         if (width < 11 || height < 11) throw std::invalid_argument("width and height must be >= 11");
-        if (max_images < 1) throw std::invalid_argument("max_images must be >= 1");
-        if (static_cast<int64_t>(max_images) * width * height > 0x7fffffff) throw std::invalid_argument("max_images is too large");
-        if (max_corners < 1 || static_cast<int64_t>(max_images) * max_corners > (1 << 28))
-            throw std::invalid_argument("max_corners must be >= 1 and max_images max_corners <= 2^28");
+        check_image_batch(width, height, max_images, "max_images");
+        check_peak_capacity(max_images, max_corners, "max_corners");
         if (opts->min_response < 1 || opts->min_response > 10200) throw std::invalid_argument("min_response must be in 1..10200");
         if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
         if (opts->cog_radius < 1 || opts->cog_radius > 5) throw std::invalid_argument("cog_radius must be in 1..5");
@@ -1038,9 +1044,7 @@ static cba_status corner_detector_process_impl(cba_corner_detector* h, int32_t n
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         CornerDetector* d = reinterpret_cast<CornerDetector*>(h);
-        if (n_images < 0 || n_images > corner_detector_max_images(d)) throw std::invalid_argument("n_images must be in [0, max_images]");
-        if (n_images == 0) return;
-        if (!images) throw std::invalid_argument("null argument");
+        if (!check_batch_call(n_images, corner_detector_max_images(d), "images", nullptr, images != nullptr)) return;
         corner_detector_process(d, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
     });
 }
@@ -1075,8 +1079,8 @@ __attribute__((visibility("default"))) cba_status cba_corner_detector_process_ti
                                                                                     int32_t* out_status, double* out_xy, double* out_angle,
                                                                                     int32_t* out_response, int32_t* out_flags,
                                                                                     double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response, out_flags, stage_ms);
+    return timed(stage_ms, [&] { return corner_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_angle, out_response,
+                                                                     out_flags, stage_ms); });
 }
 #endif
 
@@ -1102,8 +1106,7 @@ cba_status cba_blob_detector_create(int32_t width, int32_t height, int32_t max_i
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
         if (!opts) throw std::invalid_argument("null argument");
-        check_side(width);
-        check_side(height);
+        check_sides(width, height);
         if (opts->polarity != CBA_BLOB_DARK && opts->polarity != CBA_BLOB_BRIGHT) throw std::invalid_argument("polarity must be DARK or BRIGHT");
         if (opts->inner_half < 1 || opts->inner_half > 7) throw std::invalid_argument("inner_half must be in 1..7");
         if (opts->outer_half <= opts->inner_half || opts->outer_half > 15) throw std::invalid_argument("outer_half must be in inner_half + 1..15");
@@ -1115,10 +1118,8 @@ cba_status cba_blob_detector_create(int32_t width, int32_t height, int32_t max_i
             throw std::invalid_argument("max_fit_error must be > 0, max_axis_ratio >= 1 and min_radius >= 0");
         const int side = 2 * (opts->outer_half + opts->nms_radius) + 1;
         if (width < side || height < side) throw std::invalid_argument("width and height must be >= 2 (outer_half + nms_radius) + 1");
-        if (max_images < 1) throw std::invalid_argument("max_images must be >= 1");
-        if (static_cast<int64_t>(max_images) * width * height > 0x7fffffff) throw std::invalid_argument("max_images is too large");
-        if (max_blobs < 1 || static_cast<int64_t>(max_images) * max_blobs > (1 << 28))
-            throw std::invalid_argument("max_blobs must be >= 1 and max_images max_blobs <= 2^28");
+        check_image_batch(width, height, max_images, "max_images");
+        check_peak_capacity(max_images, max_blobs, "max_blobs");
         require_device(device);
         *out = reinterpret_cast<cba_blob_detector*>(blob_detector_create(width, height, max_images, max_blobs, *opts, device));
     });
@@ -1130,9 +1131,7 @@ static cba_status blob_detector_process_impl(cba_blob_detector* h, int32_t n_ima
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         BlobDetector* d = reinterpret_cast<BlobDetector*>(h);
-        if (n_images < 0 || n_images > blob_detector_max_images(d)) throw std::invalid_argument("n_images must be in [0, max_images]");
-        if (n_images == 0) return;
-        if (!images) throw std::invalid_argument("null argument");
+        if (!check_batch_call(n_images, blob_detector_max_images(d), "images", nullptr, images != nullptr)) return;
         blob_detector_process(d, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error, out_response, out_flags, stage_ms);
     });
 }
@@ -1176,9 +1175,8 @@ __attribute__((visibility("default"))) cba_status cba_blob_detector_process_time
                                                                                   int32_t* out_status, double* out_xy, double* out_shape,
                                                                                   double* out_fit_error, int32_t* out_response,
                                                                                   int32_t* out_flags, double* stage_ms) {
-    if (!stage_ms) { g_err = "null argument"; return CBA_ERR_INVALID_ARGUMENT; }
-    return blob_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error, out_response, out_flags,
-                                      stage_ms);
+    return timed(stage_ms, [&] { return blob_detector_process_impl(h, n_images, images, out_count, out_status, out_xy, out_shape, out_fit_error,
+                                                                   out_response, out_flags, stage_ms); });
 }
 #endif
 

@@ -1,13 +1,11 @@
 // corner_detect.hip — chessboard corner detection on the GPU (corner_math.hpp, calibba.h: cba_corner_detector).  One stream and one
 // synchronise per call:
 //   k_corner_response<WIDE>  a workgroup of four wavefronts owns a tile of CRN_TX x CRN_TY pixels of one image and stages the tile and
-//                            its 5-pixel halo as bytes in LDS (zeros outside the image).  WIDE (the width is a multiple of 16, so every
-//                            row starts on a 16-byte boundary): 16-byte loads of the aligned vectors that cover the tile; otherwise
-//                            single bytes.  Both stay inside [0, n_images W H).  A lane owns 4 adjacent pixels of a row: it reads the
-//                            dwords of the 9 ring rows that cover columns -8 .. +11 around its first pixel once and cuts every ring
-//                            sample out of them with constant shifts.  The ring samples of a pixel are packed four to a dword: DR is two
-//                            v_sad_u8, S16 four more against zero.  The response leaves as int16 (one 8-byte store per lane when the
-//                            width is a multiple of 4), 0 in the border.
+//                            its 5-pixel halo as bytes in LDS (stage_tile of image_tile.hpp; the byte path stages only the columns
+//                            read below).  A lane owns 4 adjacent pixels of a row: it reads the dwords of the 9 ring rows that cover
+//                            columns -8 .. +11 around its first pixel once and cuts every ring sample out of them with constant
+//                            shifts.  The ring samples of a pixel are packed four to a dword: DR is two v_sad_u8, S16 four more
+//                            against zero.  The response leaves as int16 (store4), 0 in the border.
 //   k_peak_walk, k_peak_prefix  the row-major peak list of peak_walk.hpp (shared with blob_detect.hip), instantiated for int16
 //                            responses, strips of CRN_SH rows and the border CORNER_BORDER.
 //   k_corner_refine          one lane per slot (image, corner), grid-stride: response, COG, GRADIENT, the angle sums
@@ -20,6 +18,7 @@
 
 #include "pipelines.hpp"
 #include "corner_math.hpp"
+#include "image_tile.hpp"
 #include "peak_walk.hpp"
 
 namespace cba {
@@ -76,31 +75,10 @@ template <bool WIDE>
 __global__ __launch_bounds__(CRN_BLOCK) void k_corner_response(CornerRespArgs a) {
     __shared__ __align__(16) uint8_t tile[CRN_ROWS * CRN_PITCH];
     const int W = a.W, H = a.H;
-    int b = blockIdx.x;
-    const int tx = b % a.tiles_x;
-    b /= a.tiles_x;
-    const int ty = b % a.tiles_y, im = b / a.tiles_y;
-    const int x0 = tx * CRN_TX, y0 = ty * CRN_TY;
-    const int64_t fbase = static_cast<int64_t>(im) * W * H;
+    const auto [x0, y0, im, fbase] = tile_decode<CRN_TX, CRN_TY>(a.tiles_x, a.tiles_y, W, H);
     const int tid = static_cast<int>(threadIdx.x);
-    if constexpr (WIDE) {
-        constexpr int VPR = CRN_PITCH / 16;
-        for (int i = tid; i < CRN_ROWS * VPR; i += CRN_BLOCK) {
-            const int row = i / VPR, v = i - row * VPR;
-            const int y = y0 - CORNER_BORDER + row, x = x0 - CRN_LEFT + 16 * v;  // x and W are multiples of 16: all in or all out
-            uint4 q = make_uint4(0u, 0u, 0u, 0u);
-            if (y >= 0 && y < H && x >= 0 && x < W) q = *reinterpret_cast<const uint4*>(a.img + fbase + static_cast<int64_t>(y) * W + x);
-            *reinterpret_cast<uint4*>(tile + row * CRN_PITCH + 16 * v) = q;
-        }
-    } else {
-        constexpr int COLS = CRN_TX + 16, C0 = CRN_LEFT - 8;  // the columns the dword reads below touch: x0 - 8 .. x0 + 71
-        for (int i = tid; i < CRN_ROWS * COLS; i += CRN_BLOCK) {
-            const int row = i / COLS, c = i - row * COLS;
-            const int y = y0 - CORNER_BORDER + row, x = x0 - 8 + c;
-            const bool in = y >= 0 && y < H && x >= 0 && x < W;
-            tile[row * CRN_PITCH + C0 + c] = in ? a.img[fbase + static_cast<int64_t>(y) * W + x] : uint8_t(0);
-        }
-    }
+    // the byte path stages only the columns the dword reads below touch: x0 - 8 .. x0 + 71
+    stage_tile<CRN_TX, CRN_TY, CORNER_BORDER, CRN_LEFT, CRN_PITCH, CRN_BLOCK, WIDE, CRN_LEFT - 8, CRN_TX + 16>(tile, a.img, fbase, x0, y0, W, H, tid);
     __syncthreads();
     const int ry = tid >> 4, l4 = tid & 15;
     const int x = x0 + 4 * l4, y = y0 + ry;
@@ -115,18 +93,7 @@ __global__ __launch_bounds__(CRN_BLOCK) void k_corner_response(CornerRespArgs a)
     }
     const int o0 = crn_pixel<0>(w, x, y, W, H), o1 = crn_pixel<1>(w, x, y, W, H), o2 = crn_pixel<2>(w, x, y, W, H),
               o3 = crn_pixel<3>(w, x, y, W, H);
-    int16_t* dst = a.resp + fbase + static_cast<int64_t>(y) * W + x;
-    if ((W & 3) == 0) {  // x + 3 < W, and the address is a multiple of 8 bytes
-        uint2 q;
-        q.x = (static_cast<uint32_t>(o0) & 0xffffu) | static_cast<uint32_t>(o1) << 16;
-        q.y = (static_cast<uint32_t>(o2) & 0xffffu) | static_cast<uint32_t>(o3) << 16;
-        *reinterpret_cast<uint2*>(dst) = q;
-    } else {
-        dst[0] = static_cast<int16_t>(o0);
-        if (x + 1 < W) dst[1] = static_cast<int16_t>(o1);
-        if (x + 2 < W) dst[2] = static_cast<int16_t>(o2);
-        if (x + 3 < W) dst[3] = static_cast<int16_t>(o3);
-    }
+    store4(x, W, Px4<int16_t, int>{a.resp + fbase + static_cast<int64_t>(y) * W + x, {o0, o1, o2, o3}});
 }
 
 struct CornerRefineArgs {
@@ -145,15 +112,13 @@ struct CornerRefineArgs {
 
 __global__ __launch_bounds__(CRN_BLOCK) void k_corner_refine(CornerRefineArgs a) {
     for (int i = blockIdx.x * CRN_BLOCK + threadIdx.x; i < a.n_slots; i += gridDim.x * CRN_BLOCK) {
-        const int im = i / a.max_corners, slot = i - im * a.max_corners;
+        const SlotAt s = slot_at(i, a.max_corners, a.count, a.peak_px, a.W, a.H);
         double xy[2] = {NAN, NAN}, sums[2] = {NAN, NAN};
         int flags = 0, response = 0;
-        if (slot < min(a.count[im], a.max_corners)) {
-            const int p = a.peak_px[i], py = p / a.W, px = p - py * a.W;
-            const int64_t fbase = static_cast<int64_t>(im) * a.W * a.H;
-            corner_refine_one(a.img + fbase, a.resp + fbase, a.W, a.H, px, py, a.cog_radius, a.refine, a.w, a.iters, a.wt, a.trig, xy, sums,
-                              &flags);
-            response = a.resp[fbase + p];
+        if (s.kept) {
+            corner_refine_one(a.img + s.fbase, a.resp + s.fbase, a.W, a.H, s.px, s.py, a.cog_radius, a.refine, a.w, a.iters, a.wt, a.trig, xy,
+                              sums, &flags);
+            response = a.resp[s.fbase + s.p];
         }
         a.xy[2 * i] = xy[0];
         a.xy[2 * i + 1] = xy[1];
@@ -167,41 +132,23 @@ __global__ __launch_bounds__(CRN_BLOCK) void k_corner_refine(CornerRefineArgs a)
 // ---- host glue ---------------------------------------------------------------------------------------------------------------------
 // The detector: options fixed at create, every buffer (the host staging of the angle sums included) sized for max_images there.  Every
 // call ends with its stream synchronised.
-struct CornerDetector : DeviceHandle {
-    using DeviceHandle::DeviceHandle;
+struct CornerDetector : DetectorFrame {
+    using DetectorFrame::DetectorFrame;
     cba_corner_options opts;
-    int W = 0, H = 0, max_images = 0, max_corners = 0;
-    int tiles_x = 0, tiles_y = 0, strips = 0;
-    DevBuf<uint8_t> img;
     DevBuf<int16_t> resp;
-    DevBuf<int32_t> strip_count, strip_off, count, status, peak_px, response, flags;
-    DevBuf<double> wt, trig, xy, sums;
+    DevBuf<double> wt, trig, sums;
     std::vector<double> h_sums;
-    std::vector<int32_t> h_count;
 };
 static_assert(!std::is_copy_constructible_v<CornerDetector> && !std::is_copy_assignable_v<CornerDetector>, "a handle owns its stream and buffers");
 
 CornerDetector* corner_detector_create(int W, int H, int max_images, int max_corners, const cba_corner_options& o, int device) {
     auto h = std::make_unique<CornerDetector>(device);
     h->opts = o;
-    h->W = W; h->H = H; h->max_images = max_images; h->max_corners = max_corners;
-    h->tiles_x = (W + CRN_TX - 1) / CRN_TX;
-    h->tiles_y = (H + CRN_TY - 1) / CRN_TY;
-    h->strips = (H + CRN_SH - 1) / CRN_SH;
-    const size_t px = static_cast<size_t>(max_images) * W * H, slots = static_cast<size_t>(max_images) * max_corners;
-    h->img.alloc(px);
-    h->resp.alloc(px);
-    h->strip_count.alloc(static_cast<size_t>(max_images) * h->strips);
-    h->strip_off.alloc(static_cast<size_t>(max_images) * h->strips);
-    h->count.alloc(max_images);
-    h->status.alloc(max_images);
-    h->peak_px.alloc(slots);
-    h->response.alloc(slots);
-    h->flags.alloc(slots);
-    h->xy.alloc(2 * slots);
+    h->alloc(W, H, max_images, max_corners, CRN_TX, CRN_TY, CRN_SH);
+    const size_t slots = static_cast<size_t>(max_images) * max_corners;
+    h->resp.alloc(static_cast<size_t>(max_images) * W * H);
     h->sums.alloc(2 * slots);
     h->h_sums.resize(2 * slots);
-    h->h_count.resize(max_images);
     const int w = o.refine_half_window, side = 2 * w + 1;
     std::vector<double> wt(static_cast<size_t>(side) * side), trig(16);
     corner_weight_table(w, wt.data());
@@ -219,46 +166,30 @@ int corner_detector_max_images(const CornerDetector* h) { return h->max_images; 
 void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
                              double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms) {
     const hipStream_t s = h->begin();
-    const size_t px = static_cast<size_t>(n_images) * h->W * h->H, slots = static_cast<size_t>(n_images) * h->max_corners;
+    const size_t slots = static_cast<size_t>(n_images) * h->max_items;
     StageTimer<6> tm(s, stage_ms != nullptr);
-    tm.mark(0);
-    h->img.upload(images, px, s);
-    tm.mark(1);
-    CornerRespArgs ra{h->img.p, h->resp.p, h->W, h->H, h->tiles_x, h->tiles_y};
-    const dim3 rgrid(static_cast<unsigned>(n_images * h->tiles_x * h->tiles_y));
-    if (h->W % 16 == 0) hipLaunchKernelGGL(k_corner_response<true>, rgrid, dim3(CRN_BLOCK), 0, s, ra);
-    else hipLaunchKernelGGL(k_corner_response<false>, rgrid, dim3(CRN_BLOCK), 0, s, ra);
-    CBA_HIP(hipGetLastError());
-    tm.mark(2);
-    PeakArgs<int16_t> pa{h->resp.p, h->W, h->H, h->strips, CORNER_BORDER, h->opts.min_response, h->opts.nms_radius, h->max_corners,
-                         h->strip_count.p, h->strip_off.p, h->peak_px.p};
-    peak_walk_launch<int16_t, CRN_SH>(s, n_images, pa, h->count.p, h->status.p);
-    tm.mark(3);
-    CornerRefineArgs fa{h->img.p, h->resp.p, h->W, h->H, static_cast<int>(slots), h->max_corners, h->opts.cog_radius, h->opts.refine,
+    const CornerRespArgs ra{h->img.p, h->resp.p, h->W, h->H, h->tiles_x, h->tiles_y};
+    const PeakArgs<int16_t> pa{h->resp.p, h->W, h->H, h->strips, CORNER_BORDER, h->opts.min_response, h->opts.nms_radius, h->max_items,
+                               h->strip_count.p, h->strip_off.p, h->peak_px.p};
+    h->find_peaks<CRN_SH>(tm, s, n_images, images, k_corner_response<true>, k_corner_response<false>, CRN_BLOCK, ra, pa);
+    CornerRefineArgs fa{h->img.p, h->resp.p, h->W, h->H, static_cast<int>(slots), h->max_items, h->opts.cog_radius, h->opts.refine,
                         h->opts.refine_half_window, h->opts.refine_iterations, h->count.p, h->peak_px.p, h->wt.p, h->trig.p, h->xy.p,
                         h->sums.p, h->response.p, h->flags.p};
-    const int fgrid = launch_grid(static_cast<int64_t>(slots), CRN_BLOCK, CRN_GRID);
-    hipLaunchKernelGGL(k_corner_refine, dim3(fgrid), dim3(CRN_BLOCK), 0, s, fa);
+    hipLaunchKernelGGL(k_corner_refine, dim3(launch_grid(static_cast<int64_t>(slots), CRN_BLOCK, CRN_GRID)), dim3(CRN_BLOCK), 0, s, fa);
     CBA_HIP(hipGetLastError());
-    tm.mark(4);
-    h->count.download(h->h_count.data(), n_images, s);
-    if (out_status) h->status.download(out_status, n_images, s);
+    h->fetch_counts(tm, s, n_images, out_status);
     if (out_xy) h->xy.download(out_xy, 2 * slots, s);
     if (out_angle) h->sums.download(h->h_sums.data(), 2 * slots, s);
     if (out_response) h->response.download(out_response, slots, s);
     if (out_flags) h->flags.download(out_flags, slots, s);
-    tm.mark(5);
-    CBA_HIP(hipStreamSynchronize(s));
-    for (int im = 0; im < n_images; ++im) {
-        if (out_count) out_count[im] = h->h_count[im];
-        if (!out_angle) continue;
-        const int kept = std::min(h->h_count[im], h->max_corners);
-        for (int c = 0; c < h->max_corners; ++c) {
-            const size_t i = static_cast<size_t>(im) * h->max_corners + c;
+    h->finish(tm, s, n_images, out_count, stage_ms);
+    for (int im = 0; out_angle && im < n_images; ++im) {
+        const int kept = std::min(h->h_count[im], h->max_items);
+        for (int c = 0; c < h->max_items; ++c) {
+            const size_t i = static_cast<size_t>(im) * h->max_items + c;
             out_angle[i] = c < kept ? corner_angle(&h->h_sums[2 * i]) : static_cast<double>(NAN);
         }
     }
-    tm.report(stage_ms);
 }
 
 void corner_detector_destroy(CornerDetector* h) noexcept { destroy_handle(h); }

@@ -6,10 +6,17 @@
 //                           wavefront totals from LDS.  PLACE = false leaves the strip's count; k_peak_prefix turns the counts of an
 //                           image into exclusive offsets, the true count and the status; PLACE = true repeats the walk and writes
 //                           each peak's pixel index at offset + rank.  No atomic: the order is row-major by construction.
+//   DetectorFrame           the host frame of the two detector handles: what they hold in common and the shared parts of a call.
 #pragma once
 #include <cstdint>
 
 #include "camera_math.hpp"
+#if defined(__HIPCC__)
+#include <algorithm>
+#include <vector>
+
+#include "hip_glue.hpp"
+#endif
 
 namespace cba {
 
@@ -113,6 +120,63 @@ inline void peak_walk_launch(hipStream_t s, int n_images, const PeakArgs<RT>& pa
     hipLaunchKernelGGL((k_peak_walk<RT, SH, true>), pgrid, dim3(PEAK_BLOCK), 0, s, pa);
     CBA_HIP(hipGetLastError());
 }
+
+// The frame of a detector handle (corner_detect.hip, blob_detect.hip): the sizes, the buffers of the image, the peak list and the
+// outputs every detector has, and the parts of a call round the detector's own two launches, its downloads and its host pass:
+//   find_peaks  upload, the response kernel (wide when W % 16 == 0), the peak list; timer marks 0 .. 3
+//   fetch_counts  after the refine launch: mark 4, count -> h_count and status queued
+//   finish  mark 5, the call's one synchronise, out_count, the stage times
+struct __attribute__((visibility("hidden"))) DetectorFrame : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
+    int W = 0, H = 0, max_images = 0, max_items = 0;
+    int tiles_x = 0, tiles_y = 0, strips = 0;
+    DevBuf<uint8_t> img;
+    DevBuf<int32_t> strip_count, strip_off, count, status, peak_px, response, flags;
+    DevBuf<double> xy;
+    std::vector<int32_t> h_count;
+
+    // tiles of tw x th pixels, strips of sh rows; returns the pixels and the slots of max_images_ images
+    void alloc(int W_, int H_, int max_images_, int max_items_, int tw, int th, int sh) {
+        W = W_; H = H_; max_images = max_images_; max_items = max_items_;
+        tiles_x = (W + tw - 1) / tw;
+        tiles_y = (H + th - 1) / th;
+        strips = (H + sh - 1) / sh;
+        const size_t slots = static_cast<size_t>(max_images) * max_items;
+        img.alloc(static_cast<size_t>(max_images) * W * H);
+        strip_count.alloc(static_cast<size_t>(max_images) * strips);
+        strip_off.alloc(static_cast<size_t>(max_images) * strips);
+        count.alloc(max_images);
+        status.alloc(max_images);
+        peak_px.alloc(slots);
+        response.alloc(slots);
+        flags.alloc(slots);
+        xy.alloc(2 * slots);
+        h_count.resize(max_images);
+    }
+    template <int SH, typename RT, typename RA>
+    void find_peaks(StageTimer<6>& tm, hipStream_t s, int n_images, const uint8_t* images, void (*wide)(RA), void (*narrow)(RA), int block,
+                    const RA& ra, const PeakArgs<RT>& pa) {
+        tm.mark(0);
+        img.upload(images, static_cast<size_t>(n_images) * W * H, s);
+        tm.mark(1);
+        hipLaunchKernelGGL(W % 16 == 0 ? wide : narrow, dim3(static_cast<unsigned>(n_images * tiles_x * tiles_y)), dim3(block), 0, s, ra);
+        CBA_HIP(hipGetLastError());
+        tm.mark(2);
+        peak_walk_launch<RT, SH>(s, n_images, pa, count.p, status.p);
+        tm.mark(3);
+    }
+    void fetch_counts(StageTimer<6>& tm, hipStream_t s, int n_images, int32_t* out_status) {
+        tm.mark(4);
+        count.download(h_count.data(), n_images, s);
+        if (out_status) status.download(out_status, n_images, s);
+    }
+    void finish(StageTimer<6>& tm, hipStream_t s, int n_images, int32_t* out_count, double* stage_ms) {
+        tm.mark(5);
+        CBA_HIP(hipStreamSynchronize(s));
+        if (out_count) std::copy(h_count.begin(), h_count.begin() + n_images, out_count);
+        tm.report(stage_ms);
+    }
+};
 #endif
 
 }  // namespace cba

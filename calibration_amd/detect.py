@@ -60,61 +60,50 @@ class BoardDetection:
         return np.concatenate([self.object_xy, self.image_uv], axis=1)
 
 
-class CornerDetector:
+class _Detector(capi.Handle):
+    """What the two detector handles share: the create call, the image batch, the outputs every detector has and the process call.
+    A subclass names its functions (``_FN``) and states its options struct (``_options``), its own outputs as (trailing shape, ...)
+    in the order of the C call between xy and response (``_EXTRA``) and its result type (``_RESULT``: count, status, xy, the extra
+    outputs, response, flags)."""
+
+    def __init__(self, width: int, height: int, max_images: int, max_items: int, opts, device: int):
+        self._DESTROY = self._FN + "_destroy"
+        out = self._out()
+        co = self._options(opts)
+        self.width, self.height, self.max_images, self._max_items = int(width), int(height), int(max_images), int(max_items)
+        capi.check(self._lib, getattr(self._lib, self._FN + "_create")(self.width, self.height, self.max_images, self._max_items,
+                                                                       C.byref(co), int(device), out))
+
+    def process(self, images):
+        """images: [n][height][width] uint8 (or one [height][width] image)."""
+        h = self._require_open("the detector is closed")
+        img = capi.u8_batch(images, "images", self.height, self.width, "n", self.max_images,
+                            "{} images given, the detector was created for " + str(self.max_images))
+        n, m = img.shape[0], self._max_items
+        count, status, xy = np.zeros(n, np.int32), np.zeros(n, np.int32), np.full((n, m, 2), np.nan)
+        extra = [np.full((n, m) + tail, np.nan) for tail in self._EXTRA]
+        response, flags = np.zeros((n, m), np.int32), np.zeros((n, m), np.int32)
+        capi.check(self._lib, getattr(self._lib, self._FN + "_process")(h, n, u8ptr(img), i32ptr(count), i32ptr(status), dptr(xy),
+                                                                        *[dptr(e) for e in extra], i32ptr(response), i32ptr(flags)))
+        return self._RESULT(count, status, xy, *extra, response, flags)
+
+
+class CornerDetector(_Detector):
     """``cba_corner_detector``: uint8 images of one size in, corners out.  The device buffers are sized for max_images and
     max_corners at construction.  Use as a context manager or call ``close()``."""
 
+    _FN, _EXTRA, _RESULT = "cba_corner_detector", ((),), CornerResult  # angle [n][max_corners]
+
     def __init__(self, width: int, height: int, max_images: int = 1, max_corners: int = 1024, opts: Optional[CornerOptions] = None,
                  device: int = 0):
-        self._h = None
-        self._lib = capi.load_library()
-        o = opts or CornerOptions()
-        co = CbaCornerOptions(int(o.min_response), int(o.nms_radius), int(o.cog_radius), int(o.refine), int(o.refine_half_window),
-                              int(o.refine_iterations))
-        self.width, self.height, self.max_images, self.max_corners = int(width), int(height), int(max_images), int(max_corners)
-        h = C.c_void_p()
-        capi.check(self._lib, self._lib.cba_corner_detector_create(self.width, self.height, self.max_images, self.max_corners, C.byref(co),
-                                                                   int(device), C.byref(h)))
-        self._h = h
+        super().__init__(width, height, max_images, max_corners, opts, device)
+        self.max_corners = self._max_items
 
-    def process(self, images) -> CornerResult:
-        """images: [n][height][width] uint8 (or one [height][width] image)."""
-        if self._h is None:
-            raise ValueError("the detector is closed")
-        img = np.asarray(images)
-        if img.dtype != np.uint8:
-            raise ValueError(f"images must be uint8, got {img.dtype}")
-        if img.ndim == 2:
-            img = img[None]
-        if img.ndim != 3 or img.shape[1:] != (self.height, self.width):
-            raise ValueError(f"images must have shape [n][{self.height}][{self.width}], got {img.shape}")
-        img = np.ascontiguousarray(img)
-        n, m = img.shape[0], self.max_corners
-        if n > self.max_images:
-            raise ValueError(f"{n} images given, the detector was created for {self.max_images}")
-        count, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        xy, angle = np.full((n, m, 2), np.nan), np.full((n, m), np.nan)
-        response, flags = np.zeros((n, m), np.int32), np.zeros((n, m), np.int32)
-        capi.check(self._lib, self._lib.cba_corner_detector_process(self._h, n, u8ptr(img), i32ptr(count), i32ptr(status), dptr(xy),
-                                                                    dptr(angle), i32ptr(response), i32ptr(flags)))
-        return CornerResult(count, status, xy, angle, response, flags)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cba_corner_detector_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @staticmethod
+    def _options(o):
+        o = o or CornerOptions()
+        return CbaCornerOptions(int(o.min_response), int(o.nms_radius), int(o.cog_radius), int(o.refine), int(o.refine_half_window),
+                                int(o.refine_iterations))
 
 
 def order_chessboard(xy, angle, rows: int, cols: int) -> Optional[np.ndarray]:
@@ -208,61 +197,22 @@ class BlobResult:
         return 0.5 * np.arctan2(2.0 * self.shape[..., 1], self.shape[..., 0] - self.shape[..., 2])
 
 
-class BlobDetector:
+class BlobDetector(_Detector):
     """``cba_blob_detector``: uint8 images of one size in, blobs out.  The device buffers are sized for max_images and max_blobs at
     construction.  Use as a context manager or call ``close()``."""
 
+    _FN, _EXTRA, _RESULT = "cba_blob_detector", ((3,), ()), BlobResult  # shape [n][max_blobs][3], fit_error [n][max_blobs]
+
     def __init__(self, width: int, height: int, max_images: int = 1, max_blobs: int = 1024, opts: Optional[BlobOptions] = None,
                  device: int = 0):
-        self._h = None
-        self._lib = capi.load_library()
-        o = opts or BlobOptions()
-        bo = capi.CbaBlobOptions(int(o.polarity), int(o.inner_half), int(o.outer_half), int(o.min_contrast), int(o.nms_radius),
-                                 int(o.max_radius), int(o.rounds), 0, float(o.max_fit_error), float(o.max_axis_ratio), float(o.min_radius))
-        self.width, self.height, self.max_images, self.max_blobs = int(width), int(height), int(max_images), int(max_blobs)
-        h = C.c_void_p()
-        capi.check(self._lib, self._lib.cba_blob_detector_create(self.width, self.height, self.max_images, self.max_blobs, C.byref(bo),
-                                                                 int(device), C.byref(h)))
-        self._h = h
+        super().__init__(width, height, max_images, max_blobs, opts, device)
+        self.max_blobs = self._max_items
 
-    def process(self, images) -> BlobResult:
-        """images: [n][height][width] uint8 (or one [height][width] image)."""
-        if self._h is None:
-            raise ValueError("the detector is closed")
-        img = np.asarray(images)
-        if img.dtype != np.uint8:
-            raise ValueError(f"images must be uint8, got {img.dtype}")
-        if img.ndim == 2:
-            img = img[None]
-        if img.ndim != 3 or img.shape[1:] != (self.height, self.width):
-            raise ValueError(f"images must have shape [n][{self.height}][{self.width}], got {img.shape}")
-        img = np.ascontiguousarray(img)
-        n, m = img.shape[0], self.max_blobs
-        if n > self.max_images:
-            raise ValueError(f"{n} images given, the detector was created for {self.max_images}")
-        count, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        xy, shape, fit = np.full((n, m, 2), np.nan), np.full((n, m, 3), np.nan), np.full((n, m), np.nan)
-        response, flags = np.zeros((n, m), np.int32), np.zeros((n, m), np.int32)
-        capi.check(self._lib, self._lib.cba_blob_detector_process(self._h, n, u8ptr(img), i32ptr(count), i32ptr(status), dptr(xy),
-                                                                  dptr(shape), dptr(fit), i32ptr(response), i32ptr(flags)))
-        return BlobResult(count, status, xy, shape, fit, response, flags)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cba_blob_detector_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @staticmethod
+    def _options(o):
+        o = o or BlobOptions()
+        return capi.CbaBlobOptions(int(o.polarity), int(o.inner_half), int(o.outer_half), int(o.min_contrast), int(o.nms_radius),
+                                   int(o.max_radius), int(o.rounds), 0, float(o.max_fit_error), float(o.max_axis_ratio), float(o.min_radius))
 
 
 def circle_grid_points(rows: int, cols: int, spacing: float = 1.0, pattern: int = CIRCLES_ASYMMETRIC) -> np.ndarray:

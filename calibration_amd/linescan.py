@@ -288,31 +288,28 @@ def laser_points(uv, camera, plane, frame_offset=None, frame_poses=None, inverse
     return (xyz, pxy) if want_plane_xy else xyz
 
 
-class LaserScanner:
+class LaserScanner(capi.Handle):
     """``cba_laser_scanner``: frames of one size in, laser profiles out, one kernel launch per ``process``.  The device buffers are
     sized for max_frames at construction.  Use as a context manager or call ``close()``."""
 
+    _DESTROY = "cba_laser_scanner_destroy"
+
     def __init__(self, camera, plane, width: int, height: int, max_frames: int = 1, opts: Optional[LaserScanOptions] = None,
                  inverse_coeffs=None, device: int = 0):
-        self._h = None
-        self._lib = capi.load_library()
+        out = self._out()
         model, intr, inv = _camera(camera, inverse_coeffs)
         pl = _plane(plane)
         o = opts or LaserScanOptions()
         co = CbaLaserScanOptions(int(o.axis), int(o.roi_begin), int(o.roi_end), int(o.half_window), float(o.floor_level), float(o.min_peak))
         self.width, self.height, self.max_frames, self.axis = int(width), int(height), int(max_frames), int(o.axis)
         self.n_lines = self.width if self.axis == 0 else self.height
-        h = C.c_void_p()
         capi.check(self._lib, self._lib.cba_laser_scanner_create(model, dptr(intr), 0 if inv is None else int(inv.size), dptr(inv), dptr(pl),
-                                                                 self.width, self.height, self.max_frames, C.byref(co), int(device),
-                                                                 C.byref(h)))
-        self._h = h
+                                                                 self.width, self.height, self.max_frames, C.byref(co), int(device), out))
 
     def process(self, images, frame_poses=None) -> LaserProfiles:
         """images: [n_frames][height][width] (or one [height][width] frame), uint8 or float32; C-contiguous arrays of those types are
         used as they are.  frame_poses: one pose per frame (pose7 rows or 4x4 matrices)."""
-        if self._h is None:
-            raise ValueError("the scanner is closed")
+        h = self._require_open("the scanner is closed")
         img = np.asarray(images)
         if img.dtype not in (np.uint8, np.float32):
             raise ValueError(f"images must be uint8 or float32, got {img.dtype}")
@@ -326,23 +323,6 @@ class LaserScanner:
         shape = (n_frames, self.n_lines)
         centre, amplitude, width_px, xyz = np.empty(shape), np.empty(shape), np.empty(shape), np.empty(shape + (3,))
         dtype = capi.DTYPE_U8 if img.dtype == np.uint8 else capi.DTYPE_F32
-        capi.check(self._lib, self._lib.cba_laser_scanner_process(self._h, n_frames, dtype, img.ctypes.data_as(C.c_void_p), dptr(poses),
+        capi.check(self._lib, self._lib.cba_laser_scanner_process(h, n_frames, dtype, img.ctypes.data_as(C.c_void_p), dptr(poses),
                                                                   dptr(centre), dptr(amplitude), dptr(width_px), dptr(xyz)))
         return LaserProfiles(centre, amplitude, width_px, xyz)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.cba_laser_scanner_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

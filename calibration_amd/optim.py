@@ -280,20 +280,23 @@ def flatten_bundle(observations: Sequence[BundleObservation], cameras, init_g_se
 
 
 # ---- handle wrapper ------------------------------------------------------------------------------
-class ReprojHandle:
+class ReprojHandle(capi.Handle):
     """RAII wrapper of ``cba_reproj``: observations + parameters resident in HBM."""
+
+    _DESTROY = "cba_reproj_destroy"
+    lib = property(lambda self: self._lib)
+    h = property(lambda self: self._h)
 
     def __init__(self, flat: FlatProblem, device: int = 0, lib=None, records: Optional[Sequence[np.ndarray]] = None):
         """``records`` (optional): one C-contiguous float64 array of shape (n_b, 4) per residual block holding its
         observations as {object_x, object_y, image_u, image_v} rows — the layout of the reference's
         ``std::vector<PlanarObservation>`` — handed to ``cba_reproj_create_aos`` and read in place (the flat X, Y, u, v
         arrays are then not used)."""
-        self.lib = lib or capi.load_library()
+        h = self._out(lib)
         self.flat = flat
         self._desc = flat.struct()
-        h = C.c_void_p()
         if records is None:
-            capi.check(self.lib, self.lib.cba_reproj_create(C.byref(self._desc), int(device), C.byref(h)))
+            capi.check(self.lib, self.lib.cba_reproj_create(C.byref(self._desc), int(device), h))
         else:
             if len(records) != flat.n_blocks:
                 raise ValueError("one record array per residual block")
@@ -303,26 +306,8 @@ class ReprojHandle:
                     raise ValueError("record count differs from blk_offset")
             ptrs = (capi.c_double_p * max(1, len(recs)))(*[capi.dptr(r) for r in recs])
             self._desc.X = self._desc.Y = self._desc.u = self._desc.v = None
-            capi.check(self.lib, self.lib.cba_reproj_create_aos(C.byref(self._desc), ptrs, int(device), C.byref(h)))
-        self.h = h
+            capi.check(self.lib, self.lib.cba_reproj_create_aos(C.byref(self._desc), ptrs, int(device), h))
         self._cb = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.cba_reproj_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @property
     def n_obs(self) -> int:

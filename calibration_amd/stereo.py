@@ -134,7 +134,7 @@ def rectify_maps(cameras, rectification: StereoRectification, width: int, height
     return UndistortMap(cameras, width, height, R=rectification.R, new_K=rectification.new_K, device=device)
 
 
-class StereoMatcher:
+class StereoMatcher(capi.Handle):
     """``cba_stereo_matcher``: rectified uint8 pairs of one size in, disparity, cost and (with a geometry) points out.  The device
     buffers are sized for max_pairs at construction.  geometry: a StereoGeometry, a StereoRectification or [focal, cx, cy, baseline];
     pose: pose7 or 4x4 applied to the points (r_T_rect, say).  Use as a context manager or call ``close()``."""
@@ -148,8 +148,8 @@ class StereoMatcher:
                                      int(o.lr_max_diff), int(bool(o.subpixel)))
 
     def __init__(self, width: int, height: int, max_pairs: int = 1, opts=None, geometry=None, pose=None, device: int = 0):
-        self._h = None
-        self._lib = capi.load_library()
+        self._DESTROY = self._FN + "_destroy"
+        out = self._out()
         co = self._options(opts)
         if pose is not None and geometry is None:
             raise ValueError("a pose needs a geometry")
@@ -157,28 +157,16 @@ class StereoMatcher:
         p = _pose7(pose)
         self.width, self.height, self.max_pairs = int(width), int(height), int(max_pairs)
         self.has_geometry = g is not None
-        h = C.c_void_p()
         create = getattr(self._lib, self._FN + "_create")
         capi.check(self._lib, create(self.width, self.height, self.max_pairs, C.byref(co), None if g is None else C.byref(g), dptr(p),
-                                     int(device), C.byref(h)))
-        self._h = h
-
-    def _images(self, a, name):
-        img = np.asarray(a)
-        if img.dtype != np.uint8:
-            raise ValueError(f"{name} must be uint8, got {img.dtype}")
-        if img.ndim == 2:
-            img = img[None]
-        if img.ndim != 3 or img.shape[1:] != (self.height, self.width):
-            raise ValueError(f"{name} must have shape [n_pairs][{self.height}][{self.width}], got {img.shape}")
-        return np.ascontiguousarray(img)
+                                     int(device), out))
 
     def process(self, left, right, want_xyz: Optional[bool] = None) -> StereoResult:
         """left, right: [n_pairs][height][width] uint8 (or one [height][width] pair), rectified.  want_xyz: default = a geometry was
         given."""
-        if self._h is None:
-            raise ValueError("the matcher is closed")
-        L, R = self._images(left, "left"), self._images(right, "right")
+        h = self._require_open("the matcher is closed")
+        L = capi.u8_batch(left, "left", self.height, self.width, "n_pairs")
+        R = capi.u8_batch(right, "right", self.height, self.width, "n_pairs")
         if L.shape != R.shape:
             raise ValueError(f"left and right differ in shape: {L.shape} and {R.shape}")
         n = L.shape[0]
@@ -192,26 +180,9 @@ class StereoMatcher:
         xyz = np.empty(shape + (3,), np.float32) if want_xyz else None
         fp = C.POINTER(C.c_float)
         process = getattr(self._lib, self._FN + "_process")
-        capi.check(self._lib, process(self._h, n, u8ptr(L), u8ptr(R), disp.ctypes.data_as(fp), i32ptr(cost),
+        capi.check(self._lib, process(h, n, u8ptr(L), u8ptr(R), disp.ctypes.data_as(fp), i32ptr(cost),
                                       None if xyz is None else xyz.ctypes.data_as(fp)))
         return StereoResult(disp, cost, xyz)
-
-    def close(self):
-        if self._h is not None:
-            getattr(self._lib, self._FN + "_destroy")(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SgmMatcher(StereoMatcher):

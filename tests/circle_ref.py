@@ -528,8 +528,9 @@ TILE_W, TILE_H, STRIP_H = 64, 16, 16
 # sizes of both tiers, (H, W, n_images), with the small boxes a = 1, b = 2, nms = 1 (smallest legal side 7).  Heights: 11; one row
 # less and one more than a strip (= a tile) and than two (15, 17, 31, 33) next to whole ones (16, 32); 45 and 40 end in part strips.
 # Widths: 64 k - 1, 64 k, 64 k + 1 for k = 1, 2; 23 and 70 are multiples of neither 4 nor 16 (byte staging, single stores), 96 a
-# multiple of 16 with a part tile (16-byte staging, vector stores)
-SIZES = [(11, 11, 1), (17, 23, 2), (15, 63, 1), (17, 64, 3), (33, 65, 2), (16, 127, 1), (31, 128, 2), (32, 129, 1), (45, 70, 3), (40, 96, 2)]
+# multiple of 16 with a part tile (16-byte staging, vector stores), 68 a multiple of 4 and not of 16 (byte staging, vector stores)
+SIZES = [(11, 11, 1), (17, 23, 2), (15, 63, 1), (17, 64, 3), (33, 65, 2), (16, 127, 1), (31, 128, 2), (32, 129, 1), (45, 70, 3), (40, 96, 2),
+         (19, 68, 2)]
 
 
 def border_images(o, H=60, W=72):

@@ -457,8 +457,10 @@ TILE_W, TILE_H, STRIP_H = 64, 16, 16
 # sizes of the GPU tier, (H, W, n_images).  Heights: the smallest legal 11; one row less and one more than a strip and than two strips
 # (15, 17, 31, 33) next to whole strips (16, 32); 40 and 45 end in a part strip of 8 and 13 rows.  The tile is as high as a strip, so the
 # same heights are its edges.  Widths: 64 k - 1, 64 k, 64 k + 1 for k = 1, 2; 23 and 70 are multiples of neither 4 nor 16 (byte
-# staging, single int16 stores), 96 a multiple of 16 with a part tile (16-byte staging, 8-byte stores)
-SIZES = [(11, 11, 1), (17, 23, 2), (15, 63, 1), (17, 64, 3), (33, 65, 2), (16, 127, 1), (31, 128, 2), (32, 129, 1), (45, 70, 3), (40, 96, 2)]
+# staging, single int16 stores), 96 a multiple of 16 with a part tile (16-byte staging, 8-byte stores), 68 a multiple of 4 and not of
+# 16 (byte staging with 8-byte stores)
+SIZES = [(11, 11, 1), (17, 23, 2), (15, 63, 1), (17, 64, 3), (33, 65, 2), (16, 127, 1), (31, 128, 2), (32, 129, 1), (45, 70, 3), (40, 96, 2),
+         (19, 68, 2)]
 
 
 def xcorner(H, W, cx, cy, lo=40, hi=210):
