@@ -593,3 +593,76 @@ def default_options(lib=None) -> CbaOptions:
     o = CbaOptions()
     (lib or load_library()).cba_options_default(C.byref(o))
     return o
+
+
+# ---- ChArUco boards (cba_charuco_detector, cba_marker_dictionary_generate, cba_chessboard_lattice, cba_charuco_match) -------------
+class CbaCharucoBoard(C.Structure):
+    """``cba_charuco_board`` (calibba.h)."""
+
+    _fields_ = [
+        ("squares_x", C.c_int32),
+        ("squares_y", C.c_int32),
+        ("marker_bits", C.c_int32),
+        ("n_markers", C.c_int32),
+        ("square", C.c_double),
+        ("marker_ratio", C.c_double),
+    ]
+
+
+class CbaCharucoOptions(C.Structure):
+    """``cba_charuco_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("arm_lengths", C.c_double * 2),
+        ("arm_offset", C.c_double),
+        ("arm_fan_deg", C.c_double),
+        ("min_arm_contrast", C.c_double),
+        ("min_marker_contrast", C.c_double),
+        ("min_component", C.c_int32),
+        ("cell_samples", C.c_int32),
+        ("max_border_errors", C.c_int32),
+        ("max_correction", C.c_int32),
+        ("min_markers", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+# ``cba_marker_reading`` as a numpy record
+MARKER_READING = np.dtype([("code", np.uint64), ("level_min", np.float64), ("level_max", np.float64), ("flags", np.int32), ("id", np.int32),
+                           ("rotation", np.int32), ("distance", np.int32), ("second_distance", np.int32), ("border_errors", np.int32)])
+assert MARKER_READING.itemsize == 48
+c_uint64_p = C.POINTER(C.c_uint64)
+
+
+def u64ptr(a: Optional[np.ndarray]):
+    if a is None:
+        return C.cast(None, c_uint64_p)
+    assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(c_uint64_p)
+
+
+def recptr(a: Optional[np.ndarray]):
+    """a MARKER_READING array as ``cba_marker_reading*``"""
+    if a is None:
+        return C.c_void_p(None)
+    assert a.dtype == MARKER_READING and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.c_void_p)
+
+
+PROTOTYPES.update({
+    "cba_charuco_options_default": (None, [C.POINTER(CbaCharucoOptions)]),
+    "cba_charuco_detector_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaCornerOptions), C.POINTER(CbaCharucoOptions),
+                    C.POINTER(CbaCharucoBoard), c_uint64_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_charuco_detector_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                    C.c_void_p]),
+    "cba_charuco_detector_arms": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, c_double_p]),
+    "cba_charuco_detector_read": (C.c_int32, [C.c_void_p, C.c_int32, c_int32_p, c_double_p, C.c_void_p]),
+    "cba_charuco_detector_destroy": (None, [C.c_void_p]),
+    "cba_marker_dictionary_generate": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, c_uint64_p, c_int32_p]),
+    "cba_chessboard_lattice": (C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    "cba_charuco_match": (
+        C.c_int32, [C.POINTER(CbaCharucoBoard), C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_double_p, C.c_int32, c_int32_p, c_int32_p,
+                    c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_int32_p]),
+})

@@ -13,6 +13,7 @@
 #include "circle_grid.hpp"
 #include "hom_ransac_math.hpp"
 #include "linescan_math.hpp"
+#include "marker_board.hpp"
 #include "pipelines.hpp"
 #include "stereo_math.hpp"
 
@@ -1016,23 +1017,28 @@ void cba_corner_options_default(cba_corner_options* o) {
     o->refine_iterations = 5;
 }
 
+// the sizes and options of a corner detector (shared with cba_charuco_detector_create)
+static void check_corner_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, const cba_corner_options* opts) {
+    if (!opts) throw std::invalid_argument("null argument");
+    check_sides(width, height);
+    if (width < 11 || height < 11) throw std::invalid_argument("width and height must be >= 11");
+    check_image_batch(width, height, max_images, "max_images");
+    check_peak_capacity(max_images, max_corners, "max_corners");
+    if (opts->min_response < 1 || opts->min_response > 10200) throw std::invalid_argument("min_response must be in 1..10200");
+    if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
+    if (opts->cog_radius < 1 || opts->cog_radius > 5) throw std::invalid_argument("cog_radius must be in 1..5");
+    if (opts->refine < CBA_CORNER_REFINE_NONE || opts->refine > CBA_CORNER_REFINE_GRADIENT)
+        throw std::invalid_argument("refine must be NONE, COG or GRADIENT");
+    if (opts->refine_half_window < 1 || opts->refine_half_window > 10) throw std::invalid_argument("refine_half_window must be in 1..10");
+    if (opts->refine_iterations < 1 || opts->refine_iterations > 100) throw std::invalid_argument("refine_iterations must be in 1..100");
+}
+
 cba_status cba_corner_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, const cba_corner_options* opts,
                                       int32_t device, cba_corner_detector** out) {
     return guarded([&] {
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
-        if (!opts) throw std::invalid_argument("null argument");
-        check_sides(width, height);
-        if (width < 11 || height < 11) throw std::invalid_argument("width and height must be >= 11");
-        check_image_batch(width, height, max_images, "max_images");
-        check_peak_capacity(max_images, max_corners, "max_corners");
-        if (opts->min_response < 1 || opts->min_response > 10200) throw std::invalid_argument("min_response must be in 1..10200");
-        if (opts->nms_radius < 1 || opts->nms_radius > 10) throw std::invalid_argument("nms_radius must be in 1..10");
-        if (opts->cog_radius < 1 || opts->cog_radius > 5) throw std::invalid_argument("cog_radius must be in 1..5");
-        if (opts->refine < CBA_CORNER_REFINE_NONE || opts->refine > CBA_CORNER_REFINE_GRADIENT)
-            throw std::invalid_argument("refine must be NONE, COG or GRADIENT");
-        if (opts->refine_half_window < 1 || opts->refine_half_window > 10) throw std::invalid_argument("refine_half_window must be in 1..10");
-        if (opts->refine_iterations < 1 || opts->refine_iterations > 100) throw std::invalid_argument("refine_iterations must be in 1..100");
+        check_corner_create(width, height, max_images, max_corners, opts);
         require_device(device);
         *out = reinterpret_cast<cba_corner_detector*>(corner_detector_create(width, height, max_images, max_corners, *opts, device));
     });
@@ -1179,5 +1185,174 @@ __attribute__((visibility("default"))) cba_status cba_blob_detector_process_time
                                                                    out_response, out_flags, stage_ms); });
 }
 #endif
+
+// ---- ChArUco boards (marker_read.hip, marker_math.hpp, marker_board.hpp) -----------------------------------------------------------
+void cba_charuco_options_default(cba_charuco_options* o) {
+    if (!o) return;
+    o->arm_lengths[0] = 7.0;
+    o->arm_lengths[1] = 10.0;
+    o->arm_offset = 2.0;
+    o->arm_fan_deg = 14.0;
+    o->min_arm_contrast = 112.0;
+    o->min_marker_contrast = 40.0;
+    o->min_component = 4;
+    o->cell_samples = 3;
+    o->max_border_errors = 1;
+    o->max_correction = 1;
+    o->min_markers = 2;
+    o->reserved = 0;
+}
+
+static void check_charuco_board(const cba_charuco_board* b) {
+    if (!b) throw std::invalid_argument("null argument");
+    if (b->squares_x < 3 || b->squares_y < 3 || b->squares_x > 256 || b->squares_y > 256) throw std::invalid_argument("squares_x and squares_y must be in 3..256");
+    if (b->marker_bits < 3 || b->marker_bits > MARKER_MAX_BITS) throw std::invalid_argument("marker_bits must be in 3..7");
+    if (b->n_markers < 1 || b->n_markers > MARKER_MAX_CODES) throw std::invalid_argument("n_markers must be in 1..16384");
+    if (!(b->square > 0.0) || !std::isfinite(b->square)) throw std::invalid_argument("square must be > 0");
+    if (!(b->marker_ratio >= 0.4 && b->marker_ratio <= 0.8)) throw std::invalid_argument("marker_ratio must be in [0.4, 0.8]");
+}
+
+cba_status cba_charuco_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, int32_t max_cells,
+                                       const cba_corner_options* corner_opts, const cba_charuco_options* o, const cba_charuco_board* board,
+                                       const uint64_t* codes, int32_t device, cba_charuco_detector** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!o || !codes) throw std::invalid_argument("null argument");
+        check_corner_create(width, height, max_images, max_corners, corner_opts);
+        if (max_cells < 1 || max_cells > (1 << 24)) throw std::invalid_argument("max_cells must be in 1..2^24");
+        check_charuco_board(board);
+        for (int k = 0; k < 2; ++k)
+            if (!(o->arm_lengths[k] > 0.0 && o->arm_lengths[k] <= 64.0)) throw std::invalid_argument("arm_lengths must be in (0, 64]");
+        if (!(o->arm_offset > 0.0 && o->arm_offset <= 16.0)) throw std::invalid_argument("arm_offset must be in (0, 16]");
+        if (!(o->arm_fan_deg >= 0.0 && o->arm_fan_deg <= 30.0)) throw std::invalid_argument("arm_fan_deg must be in [0, 30]");
+        if (!(o->min_arm_contrast >= 0.0) || !(o->min_marker_contrast >= 0.0) || !std::isfinite(o->min_arm_contrast) || !std::isfinite(o->min_marker_contrast))
+            throw std::invalid_argument("min_arm_contrast and min_marker_contrast must be finite and >= 0");
+        if (o->min_component < 1) throw std::invalid_argument("min_component must be >= 1");
+        if (o->cell_samples < 1 || o->cell_samples > 5) throw std::invalid_argument("cell_samples must be in 1..5");
+        if (o->max_border_errors < 0 || o->max_correction < 0) throw std::invalid_argument("max_border_errors and max_correction must be >= 0");
+        if (o->min_markers < 1) throw std::invalid_argument("min_markers must be >= 1");
+        const int nbits = board->marker_bits * board->marker_bits;
+        for (int32_t i = 0; i < board->n_markers; ++i)
+            if (codes[i] >> nbits) throw std::invalid_argument("a code has bits above marker_bits^2");
+        require_device(device);
+        *out = reinterpret_cast<cba_charuco_detector*>(
+            charuco_detector_create(width, height, max_images, max_corners, max_cells, *corner_opts, *o, *board, codes, device));
+    });
+}
+
+static cba_status charuco_detector_process_impl(cba_charuco_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
+                                                int32_t* out_status, int32_t* out_ids, double* out_xy, int32_t* out_n_markers,
+                                                int32_t* out_n_corners, int32_t* out_n_cells, int32_t* out_cells,
+                                                cba_marker_reading* out_readings, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        CharucoDetector* d = reinterpret_cast<CharucoDetector*>(h);
+        if (out_n_cells) *out_n_cells = 0;
+        if (!check_batch_call(n_images, charuco_detector_max_images(d), "images", nullptr, images != nullptr)) return;
+        charuco_detector_process(d, n_images, images, out_count, out_status, out_ids, out_xy, out_n_markers, out_n_corners, out_n_cells,
+                                 out_cells, out_readings, stage_ms);
+    });
+}
+
+cba_status cba_charuco_detector_process(cba_charuco_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count,
+                                        int32_t* out_status, int32_t* out_ids, double* out_xy, int32_t* out_n_markers, int32_t* out_n_corners,
+                                        int32_t* out_n_cells, int32_t* out_cells, cba_marker_reading* out_readings) {
+    return charuco_detector_process_impl(h, n_images, images, out_count, out_status, out_ids, out_xy, out_n_markers, out_n_corners, out_n_cells,
+                                         out_cells, out_readings, nullptr);
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_charuco.py): cba_charuco_detector_process timing its stages (stage_ms [9] = upload, response,
+// peaks, refine, arms, host lattice, read, host match, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_charuco_detector_process_timed(cba_charuco_detector* h, int32_t n_images,
+                                                                                     const uint8_t* images, int32_t* out_count,
+                                                                                     int32_t* out_n_markers, int32_t* out_n_cells,
+                                                                                     double* stage_ms) {
+    return timed(stage_ms, [&] { return charuco_detector_process_impl(h, n_images, images, out_count, nullptr, nullptr, nullptr, out_n_markers,
+                                                                      nullptr, out_n_cells, nullptr, nullptr, stage_ms); });
+}
+#endif
+
+cba_status cba_charuco_detector_arms(cba_charuco_detector* h, int32_t n_images, const double* dirs, double* out_score) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        CharucoDetector* d = reinterpret_cast<CharucoDetector*>(h);
+        const char* other = n_images != charuco_detector_last_images(d) ? "n_images must be that of the last process" : nullptr;
+        if (!check_batch_call(n_images, charuco_detector_max_images(d), "images", other, dirs != nullptr && out_score != nullptr)) return;
+        charuco_detector_arms(d, n_images, dirs, out_score);
+    });
+}
+
+cba_status cba_charuco_detector_read(cba_charuco_detector* h, int32_t n_cells, const int32_t* cell_image, const double* quads,
+                                     cba_marker_reading* out_readings) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        CharucoDetector* d = reinterpret_cast<CharucoDetector*>(h);
+        if (!check_batch_call(n_cells, charuco_detector_max_cells(d), "cells", nullptr, cell_image && quads && out_readings)) return;
+        for (int32_t i = 0; i < n_cells; ++i)
+            if (cell_image[i] < 0 || cell_image[i] >= charuco_detector_last_images(d))
+                throw std::invalid_argument("a cell's image index lies outside the last process");
+        charuco_detector_read(d, n_cells, cell_image, quads, out_readings);
+    });
+}
+
+void cba_charuco_detector_destroy(cba_charuco_detector* h) { charuco_detector_destroy(reinterpret_cast<CharucoDetector*>(h)); }
+
+cba_status cba_marker_dictionary_generate(int32_t bits, int32_t count, int32_t min_distance, uint64_t seed, uint64_t* codes,
+                                          int32_t* out_found) {
+    return guarded([&] {
+        if (!codes || !out_found) throw std::invalid_argument("null argument");
+        *out_found = 0;
+        if (bits < 3 || bits > MARKER_MAX_BITS) throw std::invalid_argument("bits must be in 3..7");
+        if (count < 1 || count > MARKER_MAX_CODES) throw std::invalid_argument("count must be in 1..16384");
+        if (min_distance < 0 || min_distance > bits * bits) throw std::invalid_argument("min_distance must be in 0..bits^2");
+        *out_found = marker_dictionary_generate(bits, count, min_distance, seed, codes);
+    });
+}
+
+static void check_corner_list(int32_t n, const double* xy, const double* angle) {
+    if (n < 0 || n > 65536) throw std::invalid_argument("n must be in 0..65536");
+    if (n > 0 && !xy) throw std::invalid_argument("null argument");
+    for (int32_t i = 0; i < n; ++i)
+        if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1]) || (angle && !std::isfinite(angle[i])))
+            throw std::invalid_argument("corners must be finite");
+}
+
+cba_status cba_chessboard_lattice(int32_t n, const double* xy, const double* angle, int32_t min_component, int32_t* out_component,
+                                  int32_t* out_ij, int32_t* out_n_components) {
+    return guarded([&] {
+        if (out_n_components) *out_n_components = 0;
+        if (n > 0 && (!angle || !out_component || !out_ij)) throw std::invalid_argument("null argument");
+        check_corner_list(n, xy, angle);
+        if (min_component < 1) throw std::invalid_argument("min_component must be >= 1");
+        const int k = chessboard_lattice(n, xy, angle, min_component, out_component, out_ij);
+        if (out_n_components) *out_n_components = k;
+    });
+}
+
+cba_status cba_charuco_match(const cba_charuco_board* board, int32_t min_markers, int32_t n, const int32_t* component, const int32_t* ij,
+                             const double* xy, int32_t n_cells, const int32_t* cells, const int32_t* flags, const int32_t* id,
+                             const int32_t* rotation, int32_t* out_count, int32_t* out_ids, double* out_xy, int32_t* out_n_markers) {
+    return guarded([&] {
+        if (!out_count || !out_ids || !out_xy) throw std::invalid_argument("null argument");
+        *out_count = 0;
+        check_charuco_board(board);
+        if (min_markers < 1) throw std::invalid_argument("min_markers must be >= 1");
+        if (n < 0 || n > 65536 || n_cells < 0 || n_cells > 65536) throw std::invalid_argument("n and n_cells must be in 0..65536");
+        if ((n > 0 && (!component || !ij || !xy)) || (n_cells > 0 && (!cells || !flags || !id || !rotation))) throw std::invalid_argument("null argument");
+        for (int32_t c = 0; c < n; ++c) {
+            if (component[c] < -1 || component[c] > 65536 || ij[2 * c] < -65536 || ij[2 * c] > 65536 || ij[2 * c + 1] < -65536 || ij[2 * c + 1] > 65536)
+                throw std::invalid_argument("a corner's component or label is out of range");
+            if (component[c] >= 0 && (!std::isfinite(xy[2 * c]) || !std::isfinite(xy[2 * c + 1]))) throw std::invalid_argument("corners must be finite");
+        }
+        for (int32_t t = 0; t < 3 * n_cells; ++t)
+            if (cells[t] < -65536 || cells[t] > 65536) throw std::invalid_argument("a cell's component or label is out of range");
+        int32_t nm = 0;
+        *out_count = charuco_match(CharucoBoard{board->squares_x, board->squares_y}, min_markers, n, component, ij, xy, n_cells, cells, flags, id,
+                                   rotation, out_ids, out_xy, &nm);
+        if (out_n_markers) *out_n_markers = nm;
+    });
+}
 
 }  // extern "C"

@@ -161,6 +161,7 @@ CornerDetector* corner_detector_create(int W, int H, int max_images, int max_cor
 }
 
 int corner_detector_max_images(const CornerDetector* h) { return h->max_images; }
+CornerDeviceView corner_detector_view(const CornerDetector* h) { return {h->img.p, h->xy.p, h->count.p, h->peak_px.p}; }
 
 // stage_ms [5] (experiment builds): upload, response, peaks, refine, download
 void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,

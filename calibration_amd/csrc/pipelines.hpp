@@ -129,6 +129,14 @@ int corner_detector_max_images(const CornerDetector* h);
 void corner_detector_process(CornerDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status, double* out_xy,
                              double* out_angle, int32_t* out_response, int32_t* out_flags, double* stage_ms);
 void corner_detector_destroy(CornerDetector* h) noexcept;
+// what marker_read.hip reaches of a corner detector: its resident images and the peak list, positions and counts of its last process
+struct CornerDeviceView {
+    const uint8_t* img;
+    const double* xy;
+    const int32_t* count;
+    const int32_t* peak_px;
+};
+CornerDeviceView corner_detector_view(const CornerDetector* h);
 // blob_detect.hip: the cba_blob_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload, response,
 // peaks, refine, download
 struct BlobDetector;
@@ -146,5 +154,23 @@ void handeye_solve(int n_poses, const double* bTg, const double* cTt, double* po
                    void* rccl_comm = nullptr);
 void* rccl_comm_create(const uint8_t* id, int n_ranks, int rank);  // collectives.cpp: ncclCommInitRank on the current device
 void rccl_comm_destroy(void* comm, bool abort);
+
+// marker_read.hip: the cba_charuco_detector handle (checked by the caller).  Every output optional.  arms and read act on the images
+// of the last process.  stage_ms [9] optional: upload, response, peaks, refine, arms, host lattice, read, host match, download; ms [1]
+// optional: the device time of the stage.
+struct CharucoDetector;
+CharucoDetector* charuco_detector_create(int W, int H, int max_images, int max_corners, int max_cells, const cba_corner_options& co,
+                                         const cba_charuco_options& o, const cba_charuco_board& b, const uint64_t* codes, int device);
+int charuco_detector_max_images(const CharucoDetector* h);
+int charuco_detector_max_corners(const CharucoDetector* h);
+int charuco_detector_max_cells(const CharucoDetector* h);
+int charuco_detector_last_images(const CharucoDetector* h);
+void charuco_detector_process(CharucoDetector* h, int n_images, const uint8_t* images, int32_t* out_count, int32_t* out_status,
+                              int32_t* out_ids, double* out_xy, int32_t* out_n_markers, int32_t* out_n_corners, int32_t* out_n_cells,
+                              int32_t* out_cells, cba_marker_reading* out_readings, double* stage_ms);
+void charuco_detector_arms(CharucoDetector* h, int n_images, const double* dirs, double* out_score, double* ms = nullptr);
+void charuco_detector_read(CharucoDetector* h, int n_cells, const int32_t* cell_image, const double* quad, cba_marker_reading* out,
+                           double* ms = nullptr);
+void charuco_detector_destroy(CharucoDetector* h) noexcept;
 
 }  // namespace cba

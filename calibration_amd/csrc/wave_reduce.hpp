@@ -39,6 +39,43 @@ __device__ __forceinline__ double wave_max63(double v) {
     return v;
 }
 
+// DPP move in which a lane that receives nothing (masked off by ROW_MASK, or its source lane out of range) keeps its own value: the
+// identity of a minimum or maximum over any values.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_keep_i32(int v) {
+    return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xF, false);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_keep_f64(double v) {
+    return __hiloint2double(dpp_keep_i32<CTRL, ROW_MASK>(__double2hiint(v)), dpp_keep_i32<CTRL, ROW_MASK>(__double2loint(v)));
+}
+
+// Wave-wide minimum of any values, the steps of wave_sum63; exact in any order, NaN entries are ignored (v_min_f64).  The minimum
+// lands in LANE 63.
+__device__ __forceinline__ double wave_min63(double v) {
+    v = fmin(v, dpp_keep_f64<0xB1, 0xF>(v));
+    v = fmin(v, dpp_keep_f64<0x4E, 0xF>(v));
+    v = fmin(v, dpp_keep_f64<0x141, 0xF>(v));
+    v = fmin(v, dpp_keep_f64<0x140, 0xF>(v));
+    v = fmin(v, dpp_keep_f64<0x142, 0xA>(v));
+    v = fmin(v, dpp_keep_f64<0x143, 0xC>(v));
+    return v;
+}
+__device__ __forceinline__ int wave_min63(int v) {
+    v = min(v, dpp_keep_i32<0xB1, 0xF>(v));
+    v = min(v, dpp_keep_i32<0x4E, 0xF>(v));
+    v = min(v, dpp_keep_i32<0x141, 0xF>(v));
+    v = min(v, dpp_keep_i32<0x140, 0xF>(v));
+    v = min(v, dpp_keep_i32<0x142, 0xA>(v));
+    v = min(v, dpp_keep_i32<0x143, 0xC>(v));
+    return v;
+}
+// lane 63's value in every lane
+__device__ __forceinline__ int wave_from63(int v) { return __builtin_amdgcn_readlane(v, 63); }
+__device__ __forceinline__ double wave_from63(double v) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
 // Transposed wave reduction: every lane enters with N partial sums w[0..N) (N a multiple of 16) and leaves with the
 // WAVE TOTALS of TransposeSum<N>::CNT of them in w[0..CNT): entry j of an OWNING lane's result is element (return value + j).
 // Each butterfly step halves the working set — a lane keeps the lower or upper half (by one bit of its lane id), hands the

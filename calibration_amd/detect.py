@@ -319,3 +319,230 @@ __all__ = ["CornerOptions", "CornerResult", "BoardDetection", "CornerDetector", 
            "BlobDetector", "order_circle_grid", "detect_circle_grid", "circle_centre_bias", "circle_grid_points", "BLOB_DARK", "BLOB_BRIGHT",
            "CIRCLES_SYMMETRIC", "CIRCLES_ASYMMETRIC", "BLOB_FLAG_WINDOW", "BLOB_FLAG_NO_EDGE", "BLOB_FLAG_DEGENERATE", "BLOB_FLAG_SHAPE",
            "BLOB_FLAG_RATIO", "BLOB_FLAG_SIZE", "BLOB_FLAG_DUPLICATE"]
+
+
+# ---- ChArUco boards (cba_charuco_detector, cba_marker_dictionary_generate, cba_chessboard_lattice, cba_charuco_match) -------------
+CHARUCO_STATUS_CORNER_OVERFLOW, CHARUCO_STATUS_CELL_OVERFLOW = 1, 2
+MARKER_FLAG_DEGENERATE, MARKER_FLAG_WINDOW, MARKER_FLAG_LOW_CONTRAST, MARKER_FLAG_BORDER, MARKER_FLAG_NO_MATCH = 1, 2, 4, 8, 16
+
+
+def marker_dictionary(bits: int, count: int, min_distance: int, seed: int = 0) -> np.ndarray:
+    """``cba_marker_dictionary_generate``: up to ``count`` codes of bits x bits cells, each ``min_distance`` from its own rotations
+    and from every rotation of the others.  The result is shorter than ``count`` when the candidate budget ran out."""
+    lib = capi.load_library()
+    codes, found = np.zeros(max(int(count), 1), np.uint64), np.zeros(1, np.int32)
+    capi.check(lib, lib.cba_marker_dictionary_generate(int(bits), int(count), int(min_distance), int(seed) & (2 ** 64 - 1),
+                                                       capi.u64ptr(codes), i32ptr(found)))
+    return codes[:int(found[0])].copy()
+
+
+@dataclass
+class CharucoBoard:
+    """``cba_charuco_board`` with its dictionary: squares_x x squares_y squares of side ``square``, square (0, 0) dark, a marker of
+    marker_bits^2 bits in every bright square, ids ascending row-major."""
+    squares_x: int
+    squares_y: int
+    square: float
+    codes: np.ndarray
+    marker_bits: int = 4
+    marker_ratio: float = 0.6
+
+    @property
+    def n_corners(self) -> int:
+        return (self.squares_x - 1) * (self.squares_y - 1)
+
+    @property
+    def object_points(self) -> np.ndarray:
+        """[n_corners][2]: inner corner (i, j), index j (squares_x - 1) + i, lies at ((i + 1) square, (j + 1) square)"""
+        jj, ii = np.divmod(np.arange(self.n_corners), self.squares_x - 1)
+        return np.stack([(ii + 1) * float(self.square), (jj + 1) * float(self.square)], axis=1)
+
+    @property
+    def marker_squares(self) -> np.ndarray:
+        """[n][2]: the square (sx, sy) of marker id 0, 1, ..."""
+        return np.array([(x, y) for y in range(self.squares_y) for x in range(self.squares_x) if (x + y) % 2 == 1], np.int32).reshape(-1, 2)
+
+    def _c(self):
+        codes = np.ascontiguousarray(np.asarray(self.codes, dtype=np.uint64).reshape(-1))
+        return capi.CbaCharucoBoard(int(self.squares_x), int(self.squares_y), int(self.marker_bits), int(codes.shape[0]), float(self.square),
+                                    float(self.marker_ratio)), codes
+
+
+@dataclass
+class CharucoOptions:
+    """``cba_charuco_options``: the arm test (lengths, offset, fan, lowest score), the smallest lattice component, the marker read
+    (sub-samples per cell, lowest contrast, border errors, corrected bits) and the readings a labelling needs."""
+    arm_lengths: tuple = (7.0, 10.0)
+    arm_offset: float = 2.0
+    arm_fan_deg: float = 14.0
+    min_arm_contrast: float = 112.0
+    min_marker_contrast: float = 40.0
+    min_component: int = 4
+    cell_samples: int = 3
+    max_border_errors: int = 1
+    max_correction: int = 1
+    min_markers: int = 2
+
+    def _c(self):
+        return capi.CbaCharucoOptions((C.c_double * 2)(float(self.arm_lengths[0]), float(self.arm_lengths[1])), float(self.arm_offset),
+                                      float(self.arm_fan_deg), float(self.min_arm_contrast), float(self.min_marker_contrast),
+                                      int(self.min_component), int(self.cell_samples), int(self.max_border_errors), int(self.max_correction),
+                                      int(self.min_markers), 0)
+
+
+@dataclass
+class CharucoResult:
+    count: np.ndarray      # [n] int32: the corners that got a board index
+    status: np.ndarray     # [n] int32: CHARUCO_STATUS_*
+    ids: np.ndarray        # [n][n_corners] int32 ascending, -1 past count
+    xy: np.ndarray         # [n][n_corners][2] float64, NaN past count
+    n_markers: np.ndarray  # [n] int32: the readings behind the labellings used
+    n_corners: np.ndarray  # [n] int32: the peaks of the corner stage
+    n_cells: int           # lattice cells of the call (true number)
+    cells: np.ndarray      # [min(n_cells, max_cells)][4] int32: image, component, i, j
+    readings: np.ndarray   # [min(n_cells, max_cells)] capi.MARKER_READING
+
+
+class CharucoDetector(_Detector):
+    """``cba_charuco_detector``: uint8 images of one size in, the visible inner corners of a ChArUco board with their board indices out.
+    Use as a context manager or call ``close()``.  ``arms`` and ``read`` run the two device stages alone on the images of the last
+    ``process``."""
+
+    _FN = "cba_charuco_detector"
+
+    def __init__(self, width: int, height: int, board: CharucoBoard, max_images: int = 1, max_corners: int = 1024, max_cells: int = 4096,
+                 corner_opts: Optional[CornerOptions] = None, opts: Optional[CharucoOptions] = None, device: int = 0):
+        self._DESTROY = self._FN + "_destroy"
+        out = self._out()
+        cb, codes = board._c()
+        co, ch = CornerDetector._options(corner_opts), (opts or CharucoOptions())._c()
+        self.width, self.height, self.max_images, self.max_corners, self.max_cells = int(width), int(height), int(max_images), int(max_corners), int(max_cells)
+        self.board = board
+        capi.check(self._lib, self._lib.cba_charuco_detector_create(self.width, self.height, self.max_images, self.max_corners, self.max_cells,
+                                                                    C.byref(co), C.byref(ch), C.byref(cb), capi.u64ptr(codes), int(device), out))
+
+    def process(self, images) -> CharucoResult:
+        h = self._require_open("the detector is closed")
+        img = capi.u8_batch(images, "images", self.height, self.width, "n", self.max_images,
+                            "{} images given, the detector was created for " + str(self.max_images))
+        n, nb = img.shape[0], self.board.n_corners
+        count, status, nm, nc = (np.zeros(n, np.int32) for _ in range(4))
+        ids, xy = np.full((n, nb), -1, np.int32), np.full((n, nb, 2), np.nan)
+        n_cells, cells = np.zeros(1, np.int32), np.zeros((self.max_cells, 4), np.int32)
+        readings = np.zeros(self.max_cells, capi.MARKER_READING)
+        capi.check(self._lib, self._lib.cba_charuco_detector_process(h, n, u8ptr(img), i32ptr(count), i32ptr(status), i32ptr(ids), dptr(xy),
+                                                                     i32ptr(nm), i32ptr(nc), i32ptr(n_cells), i32ptr(cells),
+                                                                     capi.recptr(readings)))
+        k = min(int(n_cells[0]), self.max_cells)
+        return CharucoResult(count, status, ids, xy, nm, nc, int(n_cells[0]), cells[:k].copy(), readings[:k].copy())
+
+    def arms(self, dirs) -> np.ndarray:
+        """dirs [n][max_corners][12][2] -> scores [n][max_corners] (NaN past the kept corners); n: the images of the last process"""
+        h = self._require_open("the detector is closed")
+        d = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64))
+        if d.ndim != 4 or d.shape[1:] != (self.max_corners, 12, 2):
+            raise ValueError(f"dirs must have shape [n][{self.max_corners}][12][2], got {d.shape}")
+        score = np.full(d.shape[:2], np.nan)
+        capi.check(self._lib, self._lib.cba_charuco_detector_arms(h, d.shape[0], dptr(d), dptr(score)))
+        return score
+
+    def read(self, cell_image, quads) -> np.ndarray:
+        """cell_image [m], quads [m][4][2] -> readings [m] (capi.MARKER_READING), on the images of the last process"""
+        h = self._require_open("the detector is closed")
+        ci = np.ascontiguousarray(np.asarray(cell_image, dtype=np.int32).reshape(-1))
+        q = np.ascontiguousarray(np.asarray(quads, dtype=np.float64))
+        if q.shape != (ci.shape[0], 4, 2):
+            raise ValueError(f"quads must have shape [{ci.shape[0]}][4][2], got {q.shape}")
+        out = np.zeros(ci.shape[0], capi.MARKER_READING)
+        capi.check(self._lib, self._lib.cba_charuco_detector_read(h, ci.shape[0], i32ptr(ci), dptr(q), capi.recptr(out)))
+        return out
+
+
+def arm_directions(angle, fan_deg: float = 14.0) -> np.ndarray:
+    """angle [...] -> the unit vectors [...][12][2] of the arm test: direction 3 k + f at angle + pi/4 + k pi/2 + (f - 1) fan"""
+    import math
+
+    a = np.asarray(angle, dtype=np.float64)
+    out = np.zeros(a.shape + (12, 2))
+    fan = float(fan_deg) * (math.pi / 180.0)
+    for idx in np.ndindex(a.shape):
+        if not np.isfinite(a[idx]):
+            continue
+        for k in range(4):
+            for f in range(3):
+                phi = float(a[idx]) + math.pi / 4 + k * (math.pi / 2) + (f - 1) * fan
+                out[idx + (3 * k + f,)] = (math.cos(phi), math.sin(phi))
+    return out
+
+
+def chessboard_lattice(xy, angle, min_component: int = 4):
+    """``cba_chessboard_lattice``: one image's corners -> (component [n] (-1: none), ij [n][2], number of components)"""
+    lib = capi.load_library()
+    p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+    a = np.ascontiguousarray(np.asarray(angle, dtype=np.float64).reshape(-1))
+    if p.shape[0] != a.shape[0]:
+        raise ValueError(f"xy must have shape [n][2] and angle [n], got {p.shape} and {a.shape}")
+    comp, ij, k = np.full(max(len(a), 1), -1, np.int32), np.zeros((max(len(a), 1), 2), np.int32), np.zeros(1, np.int32)
+    capi.check(lib, lib.cba_chessboard_lattice(len(a), dptr(p), dptr(a), int(min_component), i32ptr(comp), i32ptr(ij), i32ptr(k)))
+    return comp[:len(a)], ij[:len(a)], int(k[0])
+
+
+def charuco_match(board: CharucoBoard, component, ij, xy, cells, flags, ids, rotations, min_markers: int = 2):
+    """``cba_charuco_match``: one image's labelled corners and readings (cells [m][3] = component, i, j) -> (ids ascending, xy,
+    n_markers)"""
+    lib = capi.load_library()
+    cb, _ = board._c()
+    comp = np.ascontiguousarray(np.asarray(component, dtype=np.int32).reshape(-1))
+    lab = np.ascontiguousarray(np.asarray(ij, dtype=np.int32).reshape(-1, 2))
+    p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+    ce = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 3))
+    fl, mid, rot = (np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1)) for v in (flags, ids, rotations))
+    if not (len(comp) == len(lab) == len(p)) or not (len(ce) == len(fl) == len(mid) == len(rot)):
+        raise ValueError("component, ij and xy need one row per corner; cells, flags, ids and rotations one per reading")
+    nb = board.n_corners
+    count, nm, out_ids, out_xy = np.zeros(1, np.int32), np.zeros(1, np.int32), np.full(nb, -1, np.int32), np.full((nb, 2), np.nan)
+    capi.check(lib, lib.cba_charuco_match(C.byref(cb), int(min_markers), len(comp), i32ptr(comp), i32ptr(lab), dptr(p), len(ce), i32ptr(ce),
+                                          i32ptr(fl), i32ptr(mid), i32ptr(rot), i32ptr(count), i32ptr(out_ids), dptr(out_xy), i32ptr(nm)))
+    k = int(count[0])
+    return out_ids[:k].copy(), out_xy[:k].copy(), int(nm[0])
+
+
+@dataclass
+class CharucoDetection:
+    found: bool
+    ids: np.ndarray         # [k] board indices, ascending
+    object_xy: np.ndarray   # [k][2]
+    image_uv: np.ndarray    # [k][2]
+    n_markers: int = 0
+
+    @property
+    def view(self) -> np.ndarray:
+        """[k][4] rows (X, Y, u, v) of the found corners: one view of the intrinsic and rig entry points."""
+        return np.concatenate([self.object_xy, self.image_uv], axis=1)
+
+
+def detect_charuco(images, board: CharucoBoard, opts: Optional[CharucoOptions] = None, corner_opts: Optional[CornerOptions] = None,
+                   min_corners: int = 6, max_corners: int = 1024, max_cells: int = 4096, device: int = 0) -> List[CharucoDetection]:
+    """The visible inner corners of a ChArUco board in every image, with their board indices.  images: [n][H][W] uint8.  ``found``:
+    at least ``min_corners`` corners got an index."""
+    img = np.asarray(images)
+    if img.ndim == 2:
+        img = img[None]
+    if img.ndim != 3:
+        raise ValueError(f"images must have shape [n][H][W], got {img.shape}")
+    out = []
+    if img.shape[0] == 0:
+        return out
+    with CharucoDetector(img.shape[2], img.shape[1], board, img.shape[0], max_corners, max_cells, corner_opts, opts, device) as det:
+        res = det.process(img)
+    obj = board.object_points
+    for i in range(img.shape[0]):
+        k = int(res.count[i])
+        ids = res.ids[i, :k].copy()
+        out.append(CharucoDetection(k >= min_corners, ids, obj[ids], res.xy[i, :k].copy(), int(res.n_markers[i])))
+    return out
+
+
+__all__ += ["marker_dictionary", "CharucoBoard", "CharucoOptions", "CharucoResult", "CharucoDetector", "CharucoDetection", "arm_directions",
+            "chessboard_lattice", "charuco_match", "detect_charuco", "CHARUCO_STATUS_CORNER_OVERFLOW", "CHARUCO_STATUS_CELL_OVERFLOW",
+            "MARKER_FLAG_DEGENERATE", "MARKER_FLAG_WINDOW", "MARKER_FLAG_LOW_CONTRAST", "MARKER_FLAG_BORDER", "MARKER_FLAG_NO_MATCH"]

@@ -1284,6 +1284,164 @@ void cba_blob_detector_destroy(cba_blob_detector* h);
 cba_status cba_circle_grid_order(int32_t n, const double* xy /*[n][2]*/, const double* shape /*[n][3] or NULL*/, int32_t pattern,
                                  int32_t rows, int32_t cols, int32_t* out_index /*[rows cols]*/, int32_t* out_unique /*or NULL*/);
 
+/* ---- ChArUco boards: corner arms, marker reads, partial views (no counterpart in the reference, which reads corners from files) ----
+ *
+ * Pictures of a ChArUco board, which may hang over the image's edge -> per image the visible inner corners with their BOARD INDEX and
+ * sub-pixel position.  Corners come from cba_corner_detector's rule unchanged; an arm test removes the X-junctions inside the
+ * markers; the host labels the partial lattices; the markers of the complete lattice cells are read on the resident images; the host
+ * assigns board indices by the markers' votes.
+ *
+ * Board (cba_charuco_board): squares_x x squares_y squares (each >= 3) of side `square`; square (sx, sy) is dark when sx + sy is
+ * even, so square (0, 0) is dark.  Every bright square carries, centred, a marker of marker_bits^2 bits (3..7) inside a dark border
+ * one cell wide: (marker_bits + 2)^2 cells on a side of marker_ratio x square, marker_ratio in [0.4, 0.8].  Marker ids ascend
+ * row-major (sy, then sx) over the bright squares, the layout of OpenCV's CharucoBoard.  Inner corner (i, j), 0 <= i < squares_x - 1,
+ * 0 <= j < squares_y - 1, has board index j (squares_x - 1) + i and object point ((i + 1) square, (j + 1) square): the origin is the
+ * outer corner of square (0, 0).  n_markers codes are given (1..16384); a board with more bright squares than codes is legal, its
+ * squares past the dictionary are never read as theirs.
+ *
+ * Dictionary: codes [n_markers] uint64, the marker_bits^2 inner cells row-major (y down, then x right), the first cell the most
+ * significant of the marker_bits^2 low bits, bright = 1.  A quarter-turn clockwise, rot(c), has cell (y, x) = c's cell
+ * (marker_bits - 1 - x, y).  cba_marker_dictionary_generate (host) draws candidates from splitmix64 with state s = seed: s +=
+ * 0x9E3779B97F4A7C15; z = s; z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) 0x94D049BB133111EB; z ^= z >> 31 (mod
+ * 2^64); the candidate is z >> (64 - bits^2).  A candidate is kept when its Hamming distance to each of its own three rotations and to
+ * all four rotations of every kept code is >= min_distance.  At most 200000 candidates are drawn; *out_found is the number of codes
+ * found, which may be less than count.
+ *
+ * Options (cba_charuco_options):
+ *   arm_lengths [2]      (0, 64]       the two distances L along an edge (defaults 7, 10)
+ *   arm_offset           (0, 16]       the distance of the two samples from the edge (default 2)
+ *   arm_fan_deg          [0, 30]       the fan's half opening in degrees (default 14)
+ *   min_arm_contrast     >= 0          lowest arm score of a corner, grey levels (default 112)
+ *   min_component        >= 1          smallest lattice component (default 4)
+ *   cell_samples         1..5          S: sub-samples per marker cell and axis (default 3)
+ *   min_marker_contrast  >= 0          lowest max - min of a reading's cell means, grey levels (default 40)
+ *   max_border_errors    >= 0          bright border cells allowed (default 1)
+ *   max_correction       >= 0          wrong bits allowed; keep it at most (the dictionary's min_distance - 1) / 2 (default 1)
+ *   min_markers          >= 1          readings a component's winning vote needs (default 2)
+ *
+ * 1. Arm test, one fp64 score per kept corner at its position (x, y) (cba_corner_detector's out_xy) and angle.  Direction 3 k + f, arm
+ *    k = 0..3, fan f = 0..2, has phi = angle + pi/4 + k pi/2 + (f - 1) arm_fan_deg pi / 180 and the unit vector (c, s) = (cos phi,
+ *    sin phi), made on the host.  On the device only + - x / and floor, in the order written, nothing contracted.  For a length L:
+ *    px = x + L c, py = y + L s; a = (px - off s, py + off c), b = (px + off s, py - off c), off = arm_offset; d = B(a) - B(b) with
+ *    B(x, y) the bilinear sample: x0 = floor(x), fx = x - x0 (y alike), top = p00 + fx (p01 - p00), bot = p10 + fx (p11 - p10),
+ *    B = top + fy (bot - top).  A sample is legal when 1 <= x <= W - 2 and 1 <= y <= H - 2.  An arm with an illegal sample in any of its
+ *    three directions is not counted at that length.  For a counted arm, P_k = max_f (-1)^k d and M_k = max_f -(-1)^k d; the score at
+ *    L is max(min_k P_k, min_k M_k) over the counted arms, and 0 when fewer than two arms are counted.  The corner's score is the
+ *    smaller of the scores at arm_lengths[0] and arm_lengths[1].  A corner passes with score >= min_arm_contrast.
+ * 2. Lattice of a partial view (host, fp64; cba_chessboard_lattice).  Input: the corners that passed and carry no refine flag, in the
+ *    order of the corner list.  Links: the neighbour rule of cba_chessboard_order (polarity, reach 1.7, 35 degree cone, mutual
+ *    links).  Labels: corners are visited in index order; an unlabelled corner starts a component at (0, 0) with quarter-turn count
+ *    o = 0 and the component grows breadth-first, slots k = 0..3 in order: slot k of a corner with count o steps by t = (k + o) mod 4,
+ *    (1,0) (0,1) (-1,0) (0,-1), and the neighbour, whose slot `back` points back, gets count (k + o + 2 - back) mod 4.  A link to a
+ *    corner that already has a different label or count is dropped (both directions) and nothing else changes.  After the pass, if
+ *    any label (component, i, j) is claimed by more than one corner, all its claimants lose all their links and leave, and the labels
+ *    are made once more from the remaining links; claimants of a label claimed twice in that second pass leave without another pass.
+ *    Then every labelled corner that has fewer than two links left leaves (all judged before any leaves).  Components with fewer than
+ *    min_component corners are discarded.  Handedness: with the mean i-step the mean of xy(i+1, j) - xy(i, j) over the labelled pairs,
+ *    the mean j-step alike, a component whose cross(mean i-step, mean j-step) is negative gets i negated; one with no i-pair, no
+ *    j-pair or a zero cross product is discarded.  Labels are shifted so that each component's smallest i and j are 0.  Components are
+ *    numbered by size, the largest first, ties by the lowest corner index.  Output per corner: component (-1: none) and (i, j).
+ *    After this only a quarter-turn and a shift of each component are unknown.
+ * 3. Marker read, one reading per lattice cell (component, i, j) whose corners (i, j) (i+1, j) (i+1, j+1) (i, j+1) are all labelled;
+ *    the cells of an image are listed by component, then j, then i.  The quad (x0, y0) .. (x3, y3), in that order, is the image of the
+ *    unit square (0,0) (1,0) (1,1) (0,1) under x = (a u + b v + c) / (g u + h v + 1), y = (d u + e v + f) / (g u + h v + 1)
+ *    (Heckbert): sx = x0 - x1 + x2 - x3, dx1 = x1 - x2, dx2 = x3 - x2 (y alike), den = dx1 dy2 - dy1 dx2, g = (sx dy2 - sy dx2) / den,
+ *    h = (dx1 sy - dy1 sx) / den, a = x1 - x0 + g x1, b = x3 - x0 + h x3, c = x0, d = y1 - y0 + g y1, e = y3 - y0 + h y3, f = y0.
+ *    The quad is DEGENERATE when |den|, or the like cross product of the two sides at any other corner (at corner k: (P_{k+1} - P_k) x
+ *    (P_{k-1} - P_k), indices modulo 4; den is the one at corner 2), is not greater than 1e-12 x the square of the longest side: two
+ *    equal points and three collinear points are both caught.  Marker cell (cx, cy), 0 <= cx, cy
+ *    < marker_bits + 2, sub-sample (kx, ky): u = m0 + ms (cx + (0.25 + 0.5 (kx + 0.5) / S)), v alike with cy and ky, m0 = 0.5 (1 -
+ *    marker_ratio), ms = marker_ratio / (marker_bits + 2); w = g u + h v + 1, x = (a u + b v + c) / w, y = (d u + e v + f) / w,
+ *    products summed left to right.  The cell's mean is the sum of B(x, y) over ky, then kx (row-major), divided once by S^2.  If any
+ *    sample of any cell is illegal (rule 1) the reading is WINDOW and nothing is read.  t = (min + max) / 2 over the cell means; a
+ *    cell is bright when mean > t.  LOW_CONTRAST: max - min < min_marker_contrast.  BORDER: more than max_border_errors bright border
+ *    cells.  The inner cells, row-major, the first the most significant, form the code.  Match: over the table entry 4 id + r =
+ *    rot^r(codes[id]) the smallest key = distance 2^16 + 4 id + r wins (distance: Hamming distance to the code), so ties go to the
+ *    lowest id, then the lowest rotation; NO_MATCH when the winner's distance > max_correction.  second_distance is the smallest
+ *    distance over the entries of every other id (-1 when there is none).  The flags are independent; a reading is accepted when it
+ *    has none.  A DEGENERATE or WINDOW reading has id -1, distances -1 and zeros elsewhere.
+ * 4. Board index (host; cba_charuco_match).  With T(a, b) = (b, -a), an accepted reading of cell (i, j) with marker id in square
+ *    (qx, qy) and rotation r votes for (r, shift) with 2 shift = (2 qx - 1, 2 qy - 1) - T^r(2 i + 1, 2 j + 1): the labelling
+ *    board (i, j) = T^r(lattice (i, j)) + shift.  Readings whose id the board does not carry do not vote.  Per component the vote with
+ *    the most readings wins when it has at least min_markers and strictly more than every other vote.  Components are then taken by
+ *    their winning votes, most first (ties: lower component number): its corners get board indices, corners outside the board are
+ *    dropped, and a component one of whose indices is already taken is dropped whole.  Output per image: out_count, out_ids ascending
+ *    with out_xy (entries past the count -1 and NaN), out_n_markers (the votes of the winning labellings that were used).
+ *
+ * cba_charuco_detector: the handle owns a cba_corner_detector's state for max_images images of width x height with up to max_corners
+ * corners each, and room for max_cells lattice cells per call; process allocates no device memory.  out_ids [n][nb], out_xy
+ * [n][nb][2] with nb = (squares_x - 1)(squares_y - 1).  out_status: CBA_CHARUCO_STATUS_CORNER_OVERFLOW as the corner detector's, and
+ * CBA_CHARUCO_STATUS_CELL_OVERFLOW on the images whose cells did not all fit: the first max_cells cells of the call are kept and
+ * *out_n_cells stays the true number.  For diagnosis: out_n_corners [n] (peaks), out_cells [max_cells][4] (image, component, i, j)
+ * and out_readings [max_cells], the first min(*out_n_cells, max_cells) filled.  Every output may be NULL.  An image's result does not
+ * depend on the other images of the call unless cells overflow.  Two mid-level calls act on the images, positions and counts of the
+ * last process: cba_charuco_detector_arms (dirs [n][max_corners][12][2] -> scores [n][max_corners], NaN past the kept corners; n must
+ * be the last process's) and cba_charuco_detector_read (n_cells <= max_cells cells: the image index and the quad of each ->
+ * readings).
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, checked before any device work): NULL pointers where one is needed; the size limits of
+ * cba_corner_detector_create; max_cells < 1 or > 2^24; a board or option value outside the ranges above; a code with bits above
+ * marker_bits^2; n_images or n outside its range; an image index outside the last process's; for the host calls n < 0 or > 65536, a
+ * non-finite corner, a component or cell label outside [-1, 65536].  No device -> CBA_ERR_NO_DEVICE (the three host calls need none).
+ * Not built: the markers of the rim squares (two inner corners only), plain ArUco boards, occlusion inside a square. */
+#define CBA_CHARUCO_STATUS_CORNER_OVERFLOW 1
+#define CBA_CHARUCO_STATUS_CELL_OVERFLOW 2
+#define CBA_MARKER_FLAG_DEGENERATE 1
+#define CBA_MARKER_FLAG_WINDOW 2
+#define CBA_MARKER_FLAG_LOW_CONTRAST 4
+#define CBA_MARKER_FLAG_BORDER 8
+#define CBA_MARKER_FLAG_NO_MATCH 16
+typedef struct cba_charuco_board {
+    int32_t squares_x, squares_y; /* >= 3 */
+    int32_t marker_bits;          /* 3..7 */
+    int32_t n_markers;            /* codes given */
+    double square;                /* side of a square, > 0 */
+    double marker_ratio;          /* marker side / square side, [0.4, 0.8] */
+} cba_charuco_board;
+typedef struct cba_charuco_options {
+    double arm_lengths[2];
+    double arm_offset;
+    double arm_fan_deg;
+    double min_arm_contrast;
+    double min_marker_contrast;
+    int32_t min_component;
+    int32_t cell_samples;
+    int32_t max_border_errors;
+    int32_t max_correction;
+    int32_t min_markers;
+    int32_t reserved; /* 0 */
+} cba_charuco_options;
+typedef struct cba_marker_reading {
+    uint64_t code;
+    double level_min, level_max; /* smallest and largest cell mean */
+    int32_t flags;               /* CBA_MARKER_FLAG_* */
+    int32_t id, rotation, distance, second_distance, border_errors;
+} cba_marker_reading;
+void cba_charuco_options_default(cba_charuco_options* o);
+typedef struct cba_charuco_detector cba_charuco_detector; /* opaque */
+cba_status cba_charuco_detector_create(int32_t width, int32_t height, int32_t max_images, int32_t max_corners, int32_t max_cells,
+                                       const cba_corner_options* corner_opts, const cba_charuco_options* charuco_opts,
+                                       const cba_charuco_board* board, const uint64_t* codes /*[n_markers]*/, int32_t device,
+                                       cba_charuco_detector** out);
+cba_status cba_charuco_detector_process(cba_charuco_detector* h, int32_t n_images, const uint8_t* images, int32_t* out_count /*[n]*/,
+                                        int32_t* out_status /*[n]*/, int32_t* out_ids /*[n][nb]*/, double* out_xy /*[n][nb][2]*/,
+                                        int32_t* out_n_markers /*[n]*/, int32_t* out_n_corners /*[n]*/, int32_t* out_n_cells /*[1]*/,
+                                        int32_t* out_cells /*[max_cells][4]*/, cba_marker_reading* out_readings /*[max_cells]*/);
+cba_status cba_charuco_detector_arms(cba_charuco_detector* h, int32_t n_images, const double* dirs /*[n][max_corners][12][2]*/,
+                                     double* out_score /*[n][max_corners]*/);
+cba_status cba_charuco_detector_read(cba_charuco_detector* h, int32_t n_cells, const int32_t* cell_image /*[n_cells]*/,
+                                     const double* quads /*[n_cells][4][2]*/, cba_marker_reading* out_readings /*[n_cells]*/);
+void cba_charuco_detector_destroy(cba_charuco_detector* h);
+cba_status cba_marker_dictionary_generate(int32_t bits, int32_t count, int32_t min_distance, uint64_t seed, uint64_t* codes /*[count]*/,
+                                          int32_t* out_found);
+cba_status cba_chessboard_lattice(int32_t n, const double* xy /*[n][2]*/, const double* angle /*[n]*/, int32_t min_component,
+                                  int32_t* out_component /*[n]*/, int32_t* out_ij /*[n][2]*/, int32_t* out_n_components /*[1] or NULL*/);
+cba_status cba_charuco_match(const cba_charuco_board* board, int32_t min_markers, int32_t n, const int32_t* component /*[n]*/,
+                             const int32_t* ij /*[n][2]*/, const double* xy /*[n][2]*/, int32_t n_cells,
+                             const int32_t* cells /*[n_cells][3]: component, i, j*/, const int32_t* flags /*[n_cells]*/,
+                             const int32_t* id /*[n_cells]*/, const int32_t* rotation /*[n_cells]*/, int32_t* out_count /*[1]*/,
+                             int32_t* out_ids /*[nb]*/, double* out_xy /*[nb][2]*/, int32_t* out_n_markers /*[1] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
