@@ -94,6 +94,8 @@ from .camera import (  # noqa: F401
     unproject,
 )
 from .stereo import (  # noqa: F401
+    DisparityFilter,
+    DisparityFilterOptions,
     SgmMatcher,
     SgmOptions,
     StereoGeometry,

@@ -199,6 +199,12 @@ class CbaSgmOptions(C.Structure):
     ]
 
 
+class CbaDisparityFilterOptions(C.Structure):
+    """``cba_disparity_filter_options`` (calibba.h)."""
+
+    _fields_ = [("median_half", C.c_int32), ("speckle_max_size", C.c_int32), ("speckle_max_diff", C.c_double)]
+
+
 class CbaStereoGeometry(C.Structure):
     """``cba_stereo_geometry`` (calibba.h)."""
 
@@ -475,6 +481,13 @@ PROTOTYPES = {
     "cba_sgm_matcher_process": (
         C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, C.POINTER(C.c_float)]),
     "cba_sgm_matcher_destroy": (None, [C.c_void_p]),
+    "cba_disparity_filter_options_default": (None, [C.POINTER(CbaDisparityFilterOptions)]),
+    "cba_disparity_filter_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaDisparityFilterOptions), C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_disparity_filter_process": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), c_int64_p]),
+    "cba_disparity_filter_destroy": (None, [C.c_void_p]),
+    "cba_stereo_matcher_set_filter": (C.c_int32, [C.c_void_p, C.POINTER(CbaDisparityFilterOptions)]),
+    "cba_sgm_matcher_set_filter": (C.c_int32, [C.c_void_p, C.POINTER(CbaDisparityFilterOptions)]),
     "cba_corner_options_default": (None, [C.POINTER(CbaCornerOptions)]),
     "cba_corner_detector_create": (
         C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CbaCornerOptions), C.c_int32, C.POINTER(C.c_void_p)]),

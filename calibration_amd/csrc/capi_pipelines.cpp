@@ -1006,6 +1006,74 @@ __attribute__((visibility("default"))) cba_status cba_sgm_matcher_process_timed(
 }
 #endif
 
+// ---- disparity filters (disparity_filter.hip, disparity_filter_math.hpp) -----------------------------------------------------------
+void cba_disparity_filter_options_default(cba_disparity_filter_options* o) {
+    if (!o) return;
+    o->median_half = 1;
+    o->speckle_max_size = 100;
+    o->speckle_max_diff = 1.0;
+}
+
+static void check_disparity_filter_options(const cba_disparity_filter_options* o) {
+    if (o->median_half < 0 || o->median_half > 2) throw std::invalid_argument("median_half must be in 0..2");
+    if (o->speckle_max_size < 0) throw std::invalid_argument("speckle_max_size must be >= 0");
+    if (!std::isfinite(o->speckle_max_diff) || !(o->speckle_max_diff >= 0.0)) throw std::invalid_argument("speckle_max_diff must be finite and >= 0");
+}
+
+cba_status cba_disparity_filter_create(int32_t width, int32_t height, int32_t max_images, const cba_disparity_filter_options* opts,
+                                       int32_t device, cba_disparity_filter** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!opts) throw std::invalid_argument("null argument");
+        check_image_batch(width, height, max_images, "max_images");
+        check_disparity_filter_options(opts);
+        require_device(device);
+        *out = reinterpret_cast<cba_disparity_filter*>(disparity_filter_create(width, height, max_images, *opts, device));
+    });
+}
+
+static cba_status disparity_filter_process_impl(cba_disparity_filter* h, int32_t n, const float* in, float* out, int64_t* stats,
+                                                double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        DisparityFilter* f = reinterpret_cast<DisparityFilter*>(h);
+        if (!check_batch_call(n, disparity_filter_max_images(f), "images", nullptr, in && out)) return;
+        disparity_filter_process(f, n, in, out, stats, stage_ms);
+    });
+}
+
+cba_status cba_disparity_filter_process(cba_disparity_filter* h, int32_t n, const float* in, float* out, int64_t* stats) {
+    return disparity_filter_process_impl(h, n, in, out, stats, nullptr);
+}
+
+void cba_disparity_filter_destroy(cba_disparity_filter* h) { disparity_filter_destroy(reinterpret_cast<DisparityFilter*>(h)); }
+
+cba_status cba_stereo_matcher_set_filter(cba_stereo_matcher* h, const cba_disparity_filter_options* opts) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        if (opts) check_disparity_filter_options(opts);
+        stereo_matcher_set_filter(reinterpret_cast<StereoMatcher*>(h), opts);
+    });
+}
+
+cba_status cba_sgm_matcher_set_filter(cba_sgm_matcher* h, const cba_disparity_filter_options* opts) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        if (opts) check_disparity_filter_options(opts);
+        sgm_matcher_set_filter(reinterpret_cast<SgmMatcher*>(h), opts);
+    });
+}
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_disparity_filter.py): cba_disparity_filter_process timing its kernels on the device (stage_ms [6] =
+// median, local labels, merge, flatten, sizes, apply).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_disparity_filter_process_timed(cba_disparity_filter* h, int32_t n, const float* in,
+                                                                                     float* out, int64_t* stats, double* stage_ms) {
+    return timed(stage_ms, [&] { return disparity_filter_process_impl(h, n, in, out, stats, stage_ms); });
+}
+#endif
+
 // ---- chessboard detection (corner_detect.hip, corner_math.hpp, corner_grid.hpp) ---------------------------------------------------
 void cba_corner_options_default(cba_corner_options* o) {
     if (!o) return;

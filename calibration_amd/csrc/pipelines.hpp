@@ -1,6 +1,8 @@
 // pipelines.hpp — the entry points of the one-shot solvers and the batched pipelines, as capi.cpp and capi_pipelines.cpp call them.
 // Each is defined in the .hip file its comment names.
 #pragma once
+#include <memory>
+
 #include "../../include/calibba.h"
 #include "hip_glue.hpp"
 
@@ -110,6 +112,43 @@ void stereo_matcher_destroy(StereoMatcher* h) noexcept;
 struct StereoGeom;
 void stereo_finish_launch(hipStream_t s, int64_t n_px, int W, int H, int lr_max_diff, const int16_t* dl, const int16_t* dr, float* disparity,
                           float* xyz, const StereoGeom& g);
+// disparity_filter.hip: the median and speckle filters.  DispFilter is the device-side object behind the cba_disparity_filter handle
+// and behind a matcher with a filter set: options and every buffer fixed by disp_filter_init (on the current device), the one launch
+// sequence queued on the caller's stream by disp_filter_run (in, out: device maps [n][H][W], in == out allowed; stats stays in
+// f.stats, [n][3]).  stage_ms [DISP_FILTER_STAGES] optional: median, local labels, merge, flatten, sizes, apply
+constexpr int DISP_FILTER_STAGES = 6;
+struct __attribute__((visibility("hidden"))) DispFilter {
+    cba_disparity_filter_options opts;
+    int W = 0, H = 0, max_images = 0;
+    DevBuf<float> med;             // the maps after the median step
+    DevBuf<int32_t> label, size;   // per pixel; only with speckle_max_size > 0
+    DevBuf<int64_t> stats;
+};
+void disp_filter_init(DispFilter& f, int W, int H, int max_images, const cba_disparity_filter_options& o);
+void disp_filter_run(DispFilter& f, hipStream_t s, int n, const float* in, float* out, double* stage_ms);
+struct DisparityFilter;
+DisparityFilter* disparity_filter_create(int W, int H, int max_images, const cba_disparity_filter_options& o, int device);
+int disparity_filter_max_images(const DisparityFilter* h);
+void disparity_filter_process(DisparityFilter* h, int n, const float* in, float* out, int64_t* stats, double* stage_ms);
+void disparity_filter_destroy(DisparityFilter* h) noexcept;
+// a matcher's filter: o == nullptr removes it; the workspace is allocated here.  Both matchers keep it as std::unique_ptr<DispFilter>
+// filter beside W, H and max_pairs, and with it set they run their finish step without xyz, then matcher_filter_finish.
+void stereo_matcher_set_filter(StereoMatcher* h, const cba_disparity_filter_options* o);
+template <class Matcher>
+__attribute__((visibility("hidden"))) void matcher_set_filter(Matcher* h, const cba_disparity_filter_options* o) {
+    h->begin();
+    h->filter.reset();  // every call has ended with its stream synchronised
+    if (!o) return;
+    auto f = std::make_unique<DispFilter>();
+    disp_filter_init(*f, h->W, h->H, h->max_pairs, *o);
+    h->filter = std::move(f);
+}
+// the resident disparity filtered in place, then the points from the filtered map (the finish step with the left-right check off)
+__attribute__((visibility("hidden"))) inline void matcher_filter_finish(DispFilter& f, hipStream_t s, int n_pairs, float* disparity, float* xyz,
+                                                                        const StereoGeom& g) {
+    disp_filter_run(f, s, n_pairs, disparity, disparity, nullptr);
+    if (xyz) stereo_finish_launch(s, static_cast<int64_t>(n_pairs) * f.W * f.H, f.W, f.H, -1, nullptr, nullptr, disparity, xyz, g);
+}
 // stereo_sgm.hip: the cba_sgm_matcher handle (checked by the caller).  geom and pose7 optional at create; disparity, cost, xyz optional;
 // stage_ms [SGM_STAGES] optional: upload, census, cost, the 8 path launches, selection, download
 constexpr int SGM_STAGES = 13;
@@ -120,6 +159,7 @@ int sgm_matcher_max_pairs(const SgmMatcher* h);
 bool sgm_matcher_has_geometry(const SgmMatcher* h);
 void sgm_matcher_process(SgmMatcher* h, int n_pairs, const uint8_t* left, const uint8_t* right, float* disparity, int32_t* cost, float* xyz,
                          double* stage_ms);
+void sgm_matcher_set_filter(SgmMatcher* h, const cba_disparity_filter_options* o);
 void sgm_matcher_destroy(SgmMatcher* h) noexcept;
 // corner_detect.hip: the cba_corner_detector handle (checked by the caller).  Every output optional; stage_ms [5] optional: upload,
 // response, peaks, refine, download

@@ -215,6 +215,7 @@ struct StereoMatcher : DeviceHandle {
     DevBuf<float> disparity, xyz;
     DevBuf<int32_t> cost;
     DevBuf<int16_t> dl, dr;
+    std::unique_ptr<DispFilter> filter;  // set_filter; null: none
 };
 static_assert(!std::is_copy_constructible_v<StereoMatcher> && !std::is_copy_assignable_v<StereoMatcher>, "a handle owns its stream and buffers");
 
@@ -282,7 +283,10 @@ void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, 
         hipLaunchKernelGGL(k_stereo_match<true>, grid, dim3(STM_BLOCK), h->lds, s, a);
         CBA_HIP(hipGetLastError());
     }
-    if (lr || xyz) {
+    if (h->filter) {
+        if (lr) stereo_finish_launch(s, static_cast<int64_t>(px), h->W, h->H, h->opts.lr_max_diff, h->dl.p, h->dr.p, h->disparity.p, nullptr, h->geom);
+        matcher_filter_finish(*h->filter, s, n_pairs, h->disparity.p, xyz ? h->xyz.p : nullptr, h->geom);
+    } else if (lr || xyz) {
         stereo_finish_launch(s, static_cast<int64_t>(px), h->W, h->H, h->opts.lr_max_diff, h->dl.p, h->dr.p, h->disparity.p, xyz ? h->xyz.p : nullptr,
                              h->geom);
     }
@@ -294,6 +298,8 @@ void stereo_matcher_process(StereoMatcher* h, int n_pairs, const uint8_t* left, 
     CBA_HIP(hipStreamSynchronize(s));
     tm.report(stage_ms);
 }
+
+void stereo_matcher_set_filter(StereoMatcher* h, const cba_disparity_filter_options* o) { matcher_set_filter(h, o); }
 
 void stereo_matcher_destroy(StereoMatcher* h) noexcept { destroy_handle(h); }
 

@@ -315,6 +315,7 @@ struct SgmMatcher : DeviceHandle {
     DevBuf<float> disparity, xyz;
     DevBuf<int32_t> cost;
     DevBuf<int16_t> dl, dr;
+    std::unique_ptr<DispFilter> filter;  // set_filter; null: none
 };
 static_assert(!std::is_copy_constructible_v<SgmMatcher> && !std::is_copy_assignable_v<SgmMatcher>, "a handle owns its stream and buffers");
 
@@ -421,15 +422,17 @@ void sgm_matcher_process(SgmMatcher* h, int n_pairs, const uint8_t* left, const 
             hipLaunchKernelGGL((k_sgm_select<true, 32>), grid, dim3(SGM_SEL_T), 0, s, a);
             CBA_HIP(hipGetLastError());
         }
-        if (lr || xyz)  // a pixel's check stays inside its own row, so the finish step can run group by group
+        float* const gxyz = xyz && !h->filter ? h->xyz.p + 3 * first : nullptr;  // with a filter the points come from the filtered map
+        if (lr || gxyz)  // a pixel's check stays inside its own row, so the finish step can run group by group
             stereo_finish_launch(s, gpx, W, H, h->opts.lr_max_diff, h->dl.p + first, lr ? h->dr.p + first : nullptr, h->disparity.p + first,
-                                 xyz ? h->xyz.p + 3 * first : nullptr, h->geom);
+                                 gxyz, h->geom);
         tm.mark(11);
         if (timed) {
             CBA_HIP(hipStreamSynchronize(s));
             for (int k = 0; k < 11; ++k) stage_ms[1 + k] += tm.ms(k, k + 1);
         }
     }
+    if (h->filter) matcher_filter_finish(*h->filter, s, n_pairs, h->disparity.p, xyz ? h->xyz.p : nullptr, h->geom);
     down.mark(0);
     if (disparity) h->disparity.download(disparity, px, s);
     if (cost) h->cost.download(cost, px, s);
@@ -441,6 +444,8 @@ void sgm_matcher_process(SgmMatcher* h, int n_pairs, const uint8_t* left, const 
         stage_ms[SGM_STAGES - 1] = down.ms(0, 1);
     }
 }
+
+void sgm_matcher_set_filter(SgmMatcher* h, const cba_disparity_filter_options* o) { matcher_set_filter(h, o); }
 
 void sgm_matcher_destroy(SgmMatcher* h) noexcept { destroy_handle(h); }
 

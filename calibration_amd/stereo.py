@@ -1,11 +1,11 @@
-"""Stereo depth on top of the C ABI (``cba_stereo_rectify``, ``cba_stereo_matcher``, ``cba_stereo_points``; no counterpart in the
+"""Stereo depth on top of the C ABI (``cba_stereo_rectify``, ``cba_stereo_matcher``, ``cba_stereo_points``, ``cba_disparity_filter``; no counterpart in the
 reference): calibrated pair -> rectified pair -> dense disparity -> 3D points.
 
 ``rectify`` takes the two cameras and their ``c_T_r`` rows as the rig entry points return them and gives the rectifying rotations, the
 common camera matrix, the baseline and ``r_T_rect``; ``rectify_maps`` builds the ``UndistortMap`` of ``camera.py`` from them;
 ``StereoMatcher`` (block matching) and ``SgmMatcher`` (semi-global matching, ``cba_sgm_matcher``) turn rectified uint8 pairs into
-disparity, cost and points; ``stereo_points`` does the last step for caller
-(u, v, disparity) triples.  The rules are stated in calibba.h.  Arguments are validated here before the library sees them.
+disparity, cost and points, with ``filter=`` through the median and speckle filters that ``DisparityFilter`` applies to caller maps;
+``stereo_points`` does the last step for caller (u, v, disparity) triples.  The rules are stated in calibba.h.  Arguments are validated here before the library sees them.
 """
 from __future__ import annotations
 
@@ -17,7 +17,7 @@ import numpy as np
 
 from . import capi
 from .camera import UndistortMap
-from .capi import CbaSgmOptions, CbaStereoGeometry, CbaStereoMatchOptions, CbaStereoRectifyOptions, dptr, i32ptr, u8ptr
+from .capi import CbaDisparityFilterOptions, CbaSgmOptions, CbaStereoGeometry, CbaStereoMatchOptions, CbaStereoRectifyOptions, dptr, i32ptr, u8ptr
 from .linescan import _camera
 
 
@@ -68,6 +68,27 @@ class SgmOptions:
     lr_max_diff: int = 1
     subpixel: bool = True
     workspace_mb: int = 0
+
+
+@dataclass
+class DisparityFilterOptions:
+    """``cba_disparity_filter_options``: the median window (2 median_half + 1)^2 (0: no median), the largest component that speckle
+    removal deletes (0: off) and the largest difference between joined 4-neighbours."""
+    median_half: int = 1
+    speckle_max_size: int = 100
+    speckle_max_diff: float = 1.0
+
+
+def _filter_options(o) -> CbaDisparityFilterOptions:
+    o = o or DisparityFilterOptions()
+    m, size, diff = int(o.median_half), int(o.speckle_max_size), float(o.speckle_max_diff)
+    if not 0 <= m <= 2:
+        raise ValueError(f"median_half must be in 0..2, got {o.median_half}")
+    if not 0 <= size <= 2**31 - 1:
+        raise ValueError(f"speckle_max_size must be in 0..2^31 - 1, got {o.speckle_max_size}")
+    if not (np.isfinite(diff) and diff >= 0.0):
+        raise ValueError(f"speckle_max_diff must be finite and >= 0, got {o.speckle_max_diff}")
+    return CbaDisparityFilterOptions(m, size, diff)
 
 
 @dataclass
@@ -147,10 +168,11 @@ class StereoMatcher(capi.Handle):
         return CbaStereoMatchOptions(int(o.min_disparity), int(o.num_disparities), int(o.half_window), int(o.uniqueness_percent),
                                      int(o.lr_max_diff), int(bool(o.subpixel)))
 
-    def __init__(self, width: int, height: int, max_pairs: int = 1, opts=None, geometry=None, pose=None, device: int = 0):
+    def __init__(self, width: int, height: int, max_pairs: int = 1, opts=None, geometry=None, pose=None, device: int = 0, filter=None):
         self._DESTROY = self._FN + "_destroy"
         out = self._out()
         co = self._options(opts)
+        fo = None if filter is None else _filter_options(filter)
         if pose is not None and geometry is None:
             raise ValueError("a pose needs a geometry")
         g = None if geometry is None else _geometry(geometry)
@@ -160,6 +182,14 @@ class StereoMatcher(capi.Handle):
         create = getattr(self._lib, self._FN + "_create")
         capi.check(self._lib, create(self.width, self.height, self.max_pairs, C.byref(co), None if g is None else C.byref(g), dptr(p),
                                      int(device), out))
+        if fo is not None:  # None: the calls made without this keyword and nothing else
+            capi.check(self._lib, getattr(self._lib, self._FN + "_set_filter")(self._h, C.byref(fo)))
+
+    def set_filter(self, filter=None):
+        """``..._set_filter``: a ``DisparityFilterOptions`` (the disparity is filtered on the device, xyz follows it), or None for none."""
+        h = self._require_open("the matcher is closed")
+        fo = None if filter is None else _filter_options(filter)
+        capi.check(self._lib, getattr(self._lib, self._FN + "_set_filter")(h, None if fo is None else C.byref(fo)))
 
     def process(self, left, right, want_xyz: Optional[bool] = None) -> StereoResult:
         """left, right: [n_pairs][height][width] uint8 (or one [height][width] pair), rectified.  want_xyz: default = a geometry was
@@ -202,6 +232,40 @@ class SgmMatcher(StereoMatcher):
                              int(o.lr_max_diff), int(bool(o.subpixel)), int(o.workspace_mb))
 
 
+class DisparityFilter(capi.Handle):
+    """``cba_disparity_filter``: float32 disparity maps of one size in, NaN = no disparity; the median and speckle filters of calibba.h
+    out.  The device buffers are sized for max_images at construction.  Use as a context manager or call ``close()``."""
+
+    _DESTROY = "cba_disparity_filter_destroy"
+
+    def __init__(self, width: int, height: int, max_images: int = 1, opts=None, device: int = 0):
+        co = _filter_options(opts)
+        out = self._out()
+        self.width, self.height, self.max_images = int(width), int(height), int(max_images)
+        capi.check(self._lib, self._lib.cba_disparity_filter_create(self.width, self.height, self.max_images, C.byref(co), int(device), out))
+
+    def process(self, disparity, want_stats: bool = False):
+        """disparity: [n][height][width] float32 (or one [height][width] map).  Returns the filtered maps [n][height][width]; with
+        want_stats also int64 [n][3] = valid pixels read, components removed, pixels removed."""
+        h = self._require_open("the filter is closed")
+        d = np.asarray(disparity)
+        if d.dtype != np.float32:
+            raise ValueError(f"disparity must be float32, got {d.dtype}")
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1:] != (self.height, self.width):
+            raise ValueError(f"disparity must have shape [n][{self.height}][{self.width}], got {d.shape}")
+        if d.shape[0] > self.max_images:
+            raise ValueError(f"{d.shape[0]} maps given, the filter was created for {self.max_images}")
+        d = np.ascontiguousarray(d)
+        out = np.empty_like(d)
+        stats = np.zeros((d.shape[0], 3), np.int64) if want_stats else None
+        fp = C.POINTER(C.c_float)
+        capi.check(self._lib, self._lib.cba_disparity_filter_process(h, d.shape[0], d.ctypes.data_as(fp), out.ctypes.data_as(fp),
+                                                                     capi.i64ptr(stats)))
+        return (out, stats) if want_stats else out
+
+
 def stereo_points(uvd, geometry, pose=None) -> np.ndarray:
     """``cba_stereo_points``: triples uvd [n][3] (u, v, disparity) -> points [n][3]; NaN where the disparity is not > 0."""
     lib = capi.load_library()
@@ -217,4 +281,4 @@ def stereo_points(uvd, geometry, pose=None) -> np.ndarray:
 
 
 __all__ = ["StereoGeometry", "StereoRectification", "StereoMatchOptions", "StereoResult", "StereoMatcher", "SgmOptions", "SgmMatcher",
-           "rectify", "rectify_maps", "stereo_points"]
+           "DisparityFilterOptions", "DisparityFilter", "rectify", "rectify_maps", "stereo_points"]

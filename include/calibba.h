@@ -1083,6 +1083,48 @@ cba_status cba_sgm_matcher_process(cba_sgm_matcher* h, int32_t n_pairs, const ui
                                    float* xyz /*[n][H][W][3] or NULL*/);
 void cba_sgm_matcher_destroy(cba_sgm_matcher* h);
 
+/* ---- disparity filters: median and speckle removal by connected components (no counterpart in the reference) ----------------------
+ *
+ * cba_disparity_filter: what follows a dense matcher.  Uniqueness and the left-right check remove single pixels; what survives them in
+ * occluded and low-texture regions is small islands of wrong disparity.  The handle owns the options, one stream and every device
+ * buffer, sized at create for max_images maps of width x height; cba_disparity_filter_process allocates nothing and ends with its
+ * stream synchronised.  Input and output are float32 [n][height][width], rows and maps contiguous, NaN = "no disparity"; out == in is
+ * allowed.  Every map is filtered on its own.  Options:
+ *   median_half         0..2          m: the window is (2m+1) x (2m+1); 0 skips step 1
+ *   speckle_max_size    >= 0          S: a component of at most S pixels is removed; 0 skips step 2
+ *   speckle_max_diff    finite, >= 0  two neighbours are joined when their disparities differ by at most this
+ * Rule:
+ * 0. Reading.  A non-finite input is invalid (NaN); -0.0 is read as +0.0, so every output is a bit pattern this rule defines.
+ * 1. Median (m > 0).  An invalid pixel stays NaN: holes are not filled.  For a valid pixel take the valid values of the window clipped
+ *    to the image, k >= 1 of them (the centre counts), sorted ascending: the output is the element of index (k - 1) / 2 (integer
+ *    division), the lower median.  The step selects and never averages: the output is one of the inputs.
+ * 2. Speckle removal (S > 0), on the result of step 1.  The nodes are the valid pixels of one map.  Pixels p and q are joined when they
+ *    are 4-neighbours in the same map and |double(d_p) - double(d_q)| <= speckle_max_diff: one fp64 subtraction, one comparison.
+ *    Diagonal neighbours are never joined, nor are the last pixel of a row and the first of the next row, nor the last row of map i and
+ *    the first row of map i + 1.  A connected component of at most S pixels becomes NaN as a whole.  The relation is symmetric, so the
+ *    components, and with them the result, depend on no traversal, tiling or arrival order.
+ * 3. Stats, optional: int64 [n][3] = {valid pixels after step 0, components removed, pixels removed}.
+ * cba_stereo_matcher_set_filter / cba_sgm_matcher_set_filter attach such a filter to a matcher (NULL: none, the default).  Its
+ * workspace is allocated in that call.  With a filter set, process computes the disparity as before, filters it, and writes xyz from
+ * the filtered map: xyz is NaN exactly where the filtered disparity is.  cost stays as the matcher's rule leaves it.
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all checked before any device work): NULL required pointers, sizes outside
+ * [1, CBA_IMAGE_MAX_SIDE], max_images < 1 or max_images width height > 2^31 - 1, an option outside its range, n < 0 or n > max_images.
+ * n == 0 is no work; otherwise no device -> CBA_ERR_NO_DEVICE. */
+typedef struct cba_disparity_filter_options {
+    int32_t median_half;      /* 0..2 (default 1) */
+    int32_t speckle_max_size; /* >= 0 (default 100) */
+    double speckle_max_diff;  /* finite, >= 0 (default 1.0) */
+} cba_disparity_filter_options;
+void cba_disparity_filter_options_default(cba_disparity_filter_options* o);
+typedef struct cba_disparity_filter cba_disparity_filter; /* opaque: options, device buffers sized at create, one stream */
+cba_status cba_disparity_filter_create(int32_t width, int32_t height, int32_t max_images, const cba_disparity_filter_options* opts,
+                                       int32_t device, cba_disparity_filter** out);
+cba_status cba_disparity_filter_process(cba_disparity_filter* h, int32_t n, const float* in /*[n][H][W]*/, float* out /*[n][H][W]*/,
+                                        int64_t* stats /*[n][3] or NULL*/);
+void cba_disparity_filter_destroy(cba_disparity_filter* h);
+cba_status cba_stereo_matcher_set_filter(cba_stereo_matcher* h, const cba_disparity_filter_options* opts /*or NULL: no filter*/);
+cba_status cba_sgm_matcher_set_filter(cba_sgm_matcher* h, const cba_disparity_filter_options* opts /*or NULL: no filter*/);
+
 /* ---- chessboard detection: corners, sub-pixel fit, grid order (no counterpart in the reference, which reads corners from files) ---
  *
  * Pictures of a plain chessboard -> the (object_xy, image_uv) lists every other entry point starts from.
