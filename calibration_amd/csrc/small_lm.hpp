@@ -182,6 +182,13 @@ CBA_HD bool small_covariance(const double* H, long long n_res, double variance_f
     double cmax = 0.0, dmin = 1e300;
     for (int i = 0; i < NP; ++i) { cmax = fmax(cmax, sqrt(H[i * NP + i])); dmin = fmin(dmin, L[i * NP + i]); }
     if (dmin <= 20.0 * static_cast<double>(n_res + NP) * 2.220446049250313e-16 * cmax) return false;
+    // From the Gram matrix R_jj^2 is the Cholesky pivot H_jj - sum_k L_jk^2, a difference that carries the rounding of the n_res
+    // products summed into H_jj (~ sqrt(n_res) eps H_jj): an exactly dependent column (collinear target points) leaves +- that
+    // rounding there, its sign alone decides whether chol_n fails, and the test above cannot see it (it resolves R_jj / |J_j|
+    // only down to sqrt(eps)).  A pivot within 20 times that rounding of zero is a dependent column.
+    const double tol2 = 20.0 * sqrt(static_cast<double>(n_res + NP)) * 2.220446049250313e-16;
+    for (int i = 0; i < NP; ++i)
+        if (L[i * NP + i] * L[i * NP + i] <= tol2 * H[i * NP + i]) return false;
     for (int c = 0; c < NP; ++c) {
         double e[NP];
         for (int r = 0; r < NP; ++r) e[r] = 0.0;

@@ -363,6 +363,12 @@ class Problem {
             scatter(x);
         };
         if (n == 0) { finish(TERM_CONVERGENCE, "no free parameters"); return; }
+        {   // Ceres checks every residual and Jacobian block it evaluates (IsArrayValid): a NaN / Inf observation fails the evaluation
+            // at x0 and the solve ends as FAILURE.  (A NaN gradient would otherwise pass `gmax <= epsilon`: std::max drops NaNs.)
+            bool finite = std::isfinite(cost);
+            for (int i = 0; i < n; ++i) finite = finite && std::isfinite(g[i]);
+            if (!finite) { finish(TERM_FAILURE, "Residual and Jacobian evaluation failed."); return; }
+        }
         if (gmax <= o.epsilon) { finish(TERM_CONVERGENCE, "Gradient tolerance reached."); return; }
 
         std::vector<double> A;
@@ -484,6 +490,11 @@ class Problem {
         double cost;
         evaluate(x, o, true, &cost, &H, &g);
         const int n = ntan;
+        {   // ceres::Covariance::Compute evaluates the problem first, and an evaluation with a NaN / Inf residual fails
+            bool finite = std::isfinite(cost);
+            for (int i = 0; i < n; ++i) finite = finite && std::isfinite(g[i]);
+            if (!finite) return false;
+        }
         std::vector<double> L = H;
         if (n > 0 && !cholesky_inplace(L, n)) return false;
         // ceres::Covariance defaults to SPARSE_QR; SuiteSparseQR declares a column dependent when its
@@ -497,6 +508,15 @@ class Problem {
                 dmin = std::min(dmin, L[static_cast<size_t>(i) * n + i]);
             }
             if (n > 0 && dmin <= 20.0 * static_cast<double>(m + n) * 2.220446049250313e-16 * cmax) return false;
+            // R_jj^2 is formed here from the Gram matrix: the Cholesky pivot H_jj - sum_k L_jk^2 carries the rounding of the m products
+            // summed into H_jj (~ sqrt(m) eps H_jj).  An exactly dependent column - what the QR of J shows as R_jj ~ eps |J_j| -
+            // leaves +- that rounding in the pivot, and its sign alone would decide whether the factorisation above fails: a pivot
+            // within 20 times that rounding of zero is a dependent column.
+            const double tol2 = 20.0 * std::sqrt(static_cast<double>(m + n)) * 2.220446049250313e-16;
+            for (int i = 0; i < n; ++i) {
+                const double d = L[static_cast<size_t>(i) * n + i];
+                if (d * d <= tol2 * H[static_cast<size_t>(i) * n + i]) return false;
+            }
         }
         std::vector<double> Sig(static_cast<size_t>(n) * n, 0.0), e(n);
         for (int c = 0; c < n; ++c) {

@@ -266,9 +266,10 @@ struct PlanarPoseVPBlock final : ResidualBlock {
 // planar_observables_to_observables (observationutils.h:78-95: point = c_se3_t * (X, Y, 0), xn = x/z, yn = y/z with the
 // rotation from quat_array_to_rotmat, no normalisation), then ONE fit_distortion_full over all observations
 // (distortion.h:229-295) and residual = A alpha - b.  Least squares by SVD on Jets (lstsq_svd), as the reference does.
-// Jets are NJ = 5 + 7 * VMAX wide: the oracle handles up to VMAX views (enough for the tests).
+// Jets are NJ = 5 + 7 * VMAX wide: the oracle handles up to VMAX views (enough for the tests: the ragged 9-view batch that leaves
+// one live wave in the last block of the per-view kernels is the largest).
 struct CalibVPBlock final : ResidualBlock {
-    static constexpr int VMAX = 6, NJ = 5 + 7 * VMAX;
+    static constexpr int VMAX = 9, NJ = 5 + 7 * VMAX;
     std::vector<ViewData> views;
     int num_radial, total = 0;
     CalibVPBlock(const std::vector<ViewData>& v, int nr) : views(v), num_radial(nr) {

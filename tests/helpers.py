@@ -91,6 +91,7 @@ def load_hostmath():
     h.hm_semidlt_solve_sharded.argtypes = SEMIDLT_SOLVE_ARGS[:6] + [C.c_int, C.c_int] + SEMIDLT_SOLVE_ARGS[6:] + [capi.ALLREDUCE_FN, C.c_void_p]
     h.hm_planar_seed.argtypes = [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     h.hm_planar_seed.restype = None
+    h.hm_dlt_homography.argtypes = [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     h.hm_quat_to_angle_axis.argtypes = [c_double_p, c_double_p]
     h.hm_angle_axis_to_quat.argtypes = [c_double_p, c_double_p]
     h.hm_handeye_last_error.restype = C.c_char_p
