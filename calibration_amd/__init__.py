@@ -126,6 +126,14 @@ from .triangulate import (  # noqa: F401
     TriangulationResult,
     triangulate,
 )
+from .structured_light import (  # noqa: F401
+    Decoded,
+    StructuredLightDecoder,
+    StructuredLightOptions,
+    image_count,
+    patterns,
+    projector_corners,
+)
 from .diagnostics import (  # noqa: F401
     ResidualStats,
     RobustOptions,

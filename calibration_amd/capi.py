@@ -164,6 +164,22 @@ class CbaLaserScanOptions(C.Structure):
     ]
 
 
+class CbaSlOptions(C.Structure):
+    """``cba_sl_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("proj_width", C.c_int32),
+        ("proj_height", C.c_int32),
+        ("axes", C.c_int32),
+        ("gray_skip_bits", C.c_int32),
+        ("phase_steps", C.c_int32),
+        ("phase_period", C.c_int32),
+        ("min_contrast", C.c_int32),
+        ("min_bit_diff", C.c_int32),
+        ("min_modulation", C.c_double),
+    ]
+
+
 class CbaStereoRectifyOptions(C.Structure):
     """``cba_stereo_rectify_options`` (calibba.h)."""
 
@@ -463,6 +479,15 @@ PROTOTYPES = {
     "cba_laser_scanner_process": (
         C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "cba_laser_scanner_destroy": (None, [C.c_void_p]),
+    "cba_sl_options_default": (None, [C.POINTER(CbaSlOptions)]),
+    "cba_sl_image_count": (C.c_int32, [C.POINTER(CbaSlOptions), c_int32_p]),
+    "cba_sl_patterns": (C.c_int32, [C.POINTER(CbaSlOptions), c_uint8_p]),
+    "cba_sl_decoder_create": (C.c_int32, [C.POINTER(CbaSlOptions), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_sl_decoder_set_rig": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.POINTER(CbaTriangulateOptions)]),
+    "cba_sl_decoder_process": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_double_p, c_double_p, c_uint8_p, c_double_p, c_double_p, c_int32_p]),
+    "cba_sl_decoder_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (
         C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(CbaStereoRectifyOptions), c_double_p, c_double_p,

@@ -1,6 +1,7 @@
 // capi_pipelines.cpp — the extern "C" entry points of the batched pipelines (include/calibba.h): laser-plane calibration, the linear
-// seeds, the distortion fits, the camera models, triangulation, laser scanning, stereo depth (block and semi-global matching) and
-// chessboard detection.  Host-side duties only, as in capi.cpp: validate the arguments, find the device, call the pipeline (pipelines.hpp).
+// seeds, the distortion fits, the camera models, triangulation, laser scanning, structured-light decoding, stereo depth (block and
+// semi-global matching) and chessboard detection.  Host-side duties only, as in capi.cpp: validate the arguments, find the device, call
+// the pipeline (pipelines.hpp).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -16,6 +17,7 @@
 #include "marker_board.hpp"
 #include "pipelines.hpp"
 #include "stereo_math.hpp"
+#include "structured_light_math.hpp"
 
 using namespace cba;
 
@@ -697,22 +699,31 @@ void cba_triangulate_options_default(cba_triangulate_options* o) {
     o->max_reproj_px = std::numeric_limits<double>::infinity();
 }
 
+// the cameras and the options of a triangulation (shared with cba_sl_decoder_set_rig), in the order cba_triangulate checks them
+static void check_tri_cameras(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs, const double* inverse_coeffs,
+                              const double* c_T_r, const cba_triangulate_options* opts) {
+    check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
+    if (n_cams < 2 || n_cams > CBA_TRI_MAX_CAMS) throw std::invalid_argument("n_cams must be in [2, 16]");
+    if (!c_T_r || !opts) throw std::invalid_argument("null argument");
+    const int ni = cam_intr_size(camera_model);
+    for (int c = 0; c < n_cams; ++c)
+        if (intr[static_cast<size_t>(c) * ni] == 0.0 || intr[static_cast<size_t>(c) * ni + 1] == 0.0)
+            throw std::invalid_argument("fx and fy must not be 0");
+}
+static void check_tri_options(const cba_triangulate_options* opts) {
+    if (opts->max_iterations < 0) throw std::invalid_argument("max_iterations must be >= 0");
+    if (!(opts->step_tolerance >= 0.0)) throw std::invalid_argument("step_tolerance must be >= 0");
+    if (!(opts->max_reproj_px > 0.0)) throw std::invalid_argument("max_reproj_px must be > 0");
+}
+
 static cba_status triangulate_impl(int32_t camera_model, int32_t n_cams, const double* intr, int32_t n_inverse_coeffs,
                                    const double* inverse_coeffs, const double* c_T_r, int64_t n, const double* uv,
                                    const cba_triangulate_options* opts, double* xyz, double* rms_px, uint32_t* used_mask, int32_t* status,
                                    double* cov6, int32_t* linearisations, double* stage_ms) {
     return guarded([&] {
-        check_camera(camera_model, intr, n_inverse_coeffs, inverse_coeffs);
-        if (n_cams < 2 || n_cams > CBA_TRI_MAX_CAMS) throw std::invalid_argument("n_cams must be in [2, 16]");
-        if (!c_T_r || !opts) throw std::invalid_argument("null argument");
-        const int ni = cam_intr_size(camera_model);
-        for (int c = 0; c < n_cams; ++c)
-            if (intr[static_cast<size_t>(c) * ni] == 0.0 || intr[static_cast<size_t>(c) * ni + 1] == 0.0)
-                throw std::invalid_argument("fx and fy must not be 0");
+        check_tri_cameras(camera_model, n_cams, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, opts);
         if (n < 0) throw std::invalid_argument("n must be >= 0");
-        if (opts->max_iterations < 0) throw std::invalid_argument("max_iterations must be >= 0");
-        if (!(opts->step_tolerance >= 0.0)) throw std::invalid_argument("step_tolerance must be >= 0");
-        if (!(opts->max_reproj_px > 0.0)) throw std::invalid_argument("max_reproj_px must be > 0");
+        check_tri_options(opts);
         if (n == 0) return;
         if (!uv || !xyz || !status) throw std::invalid_argument("null argument");
         require_device();
@@ -834,6 +845,107 @@ __attribute__((visibility("default"))) cba_status cba_laser_scanner_process_time
                                                                                   double* centre, double* amplitude, double* width_px,
                                                                                   double* xyz, double* stage_ms) {
     return timed(stage_ms, [&] { return laser_scanner_process_impl(h, n_frames, dtype, images, frame_pose7, centre, amplitude, width_px, xyz, stage_ms); });
+}
+#endif
+
+// ---- structured-light scanning (structured_light.hip, structured_light_math.hpp) ------------------------------------------------
+void cba_sl_options_default(cba_sl_options* o) {
+    if (!o) return;
+    o->proj_width = 0;
+    o->proj_height = 0;
+    o->axes = 3;
+    o->gray_skip_bits = 0;
+    o->phase_steps = 0;
+    o->phase_period = 16;
+    o->min_contrast = 10;
+    o->min_bit_diff = 4;
+    o->min_modulation = 5.0;
+}
+
+static void check_sl_options(const cba_sl_options* o) {
+    if (!o) throw std::invalid_argument("null argument");
+    if (std::min(o->proj_width, o->proj_height) < 2 || std::max(o->proj_width, o->proj_height) > CBA_IMAGE_MAX_SIDE)
+        throw std::invalid_argument("proj_width and proj_height must be in [2, 32768]");
+    if (o->axes < 1 || o->axes > 3) throw std::invalid_argument("axes must be 1, 2 or 3");
+    if (o->gray_skip_bits < 0) throw std::invalid_argument("gray_skip_bits must be >= 0");
+    if (o->phase_steps != 0 && (o->phase_steps < 3 || o->phase_steps > SL_MAX_STEPS)) throw std::invalid_argument("phase_steps must be 0 or in 3..8");
+    if (o->min_contrast < 0 || o->min_contrast > 255 || o->min_bit_diff < 0 || o->min_bit_diff > 255)
+        throw std::invalid_argument("min_contrast and min_bit_diff must be in 0..255");
+    if (!std::isfinite(o->min_modulation) || !(o->min_modulation >= 0.0)) throw std::invalid_argument("min_modulation must be finite and >= 0");
+    for (int a = 0; a < 2; ++a)
+        if ((o->axes >> a & 1) && (o->gray_skip_bits > 15 || sl_nbits(a == 0 ? o->proj_width : o->proj_height, o->gray_skip_bits) < 1))
+            throw std::invalid_argument("gray_skip_bits leaves no Gray plane");
+    if (o->phase_steps > 0 && (o->phase_period < 1 || o->phase_period > CBA_IMAGE_MAX_SIDE || o->phase_period < (2 << o->gray_skip_bits)))
+        throw std::invalid_argument("phase_period must be in [2^(gray_skip_bits + 1), 32768]");
+}
+
+cba_status cba_sl_image_count(const cba_sl_options* opts, int32_t* n_images) {
+    return guarded([&] {
+        check_sl_options(opts);
+        if (!n_images) throw std::invalid_argument("null argument");
+        *n_images = sl_options_image_count(*opts);
+    });
+}
+
+cba_status cba_sl_patterns(const cba_sl_options* opts, uint8_t* out) {
+    return guarded([&] {
+        check_sl_options(opts);
+        if (!out) throw std::invalid_argument("null argument");
+        sl_patterns_host(*opts, out);
+    });
+}
+
+cba_status cba_sl_decoder_create(const cba_sl_options* opts, int32_t width, int32_t height, int32_t max_sequences, int32_t device,
+                                 cba_sl_decoder** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        check_sl_options(opts);
+        check_image_batch(width, height, max_sequences, "max_sequences");
+        if (static_cast<double>(max_sequences) * sl_options_image_count(*opts) * width * height > 2147483647.0)
+            throw std::invalid_argument("max_sequences n_images width height must be <= 2^31 - 1");
+        require_device(device);
+        *out = reinterpret_cast<cba_sl_decoder*>(sl_decoder_create(*opts, width, height, max_sequences, device));
+    });
+}
+
+cba_status cba_sl_decoder_set_rig(cba_sl_decoder* h, int32_t camera_model, const double* intr, int32_t n_inverse_coeffs,
+                                  const double* inverse_coeffs, const double* c_T_r, const cba_triangulate_options* tri_opts) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        check_tri_cameras(camera_model, 2, intr, n_inverse_coeffs, inverse_coeffs, c_T_r, tri_opts);
+        check_tri_options(tri_opts);
+        sl_decoder_set_rig(reinterpret_cast<SlDecoder*>(h), camera_model, intr, inverse_coeffs ? n_inverse_coeffs : 0, inverse_coeffs, c_T_r,
+                           *tri_opts);
+    });
+}
+
+static cba_status sl_decoder_process_impl(cba_sl_decoder* h, int32_t n_sequences, const uint8_t* images, double* coord, double* modulation,
+                                          uint8_t* status, double* xyz, double* rms_px, int32_t* tri_status, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        SlDecoder* d = reinterpret_cast<SlDecoder*>(h);
+        const char* no_points = (xyz || rms_px || tri_status) && !sl_decoder_can_point(d) ? "points need a rig and both axes" : nullptr;
+        if (!check_batch_call(n_sequences, sl_decoder_max_sequences(d), "sequences", no_points, images != nullptr)) return;
+        sl_decoder_process(d, n_sequences, images, coord, modulation, status, xyz, rms_px, tri_status, stage_ms);
+    });
+}
+
+cba_status cba_sl_decoder_process(cba_sl_decoder* h, int32_t n_sequences, const uint8_t* images, double* coord, double* modulation,
+                                  uint8_t* status, double* xyz, double* rms_px, int32_t* tri_status) {
+    return sl_decoder_process_impl(h, n_sequences, images, coord, modulation, status, xyz, rms_px, tri_status, nullptr);
+}
+
+void cba_sl_decoder_destroy(cba_sl_decoder* h) { sl_decoder_destroy(reinterpret_cast<SlDecoder*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_structured_light.py): cba_sl_decoder_process timing its stages on the device (stage_ms [4] =
+// upload, decode, points, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_sl_decoder_process_timed(cba_sl_decoder* h, int32_t n_sequences, const uint8_t* images,
+                                                                               double* coord, double* modulation, uint8_t* status,
+                                                                               double* xyz, double* rms_px, int32_t* tri_status,
+                                                                               double* stage_ms) {
+    return timed(stage_ms, [&] { return sl_decoder_process_impl(h, n_sequences, images, coord, modulation, status, xyz, rms_px, tri_status, stage_ms); });
 }
 #endif
 

@@ -96,6 +96,19 @@ int laser_scanner_max_frames(const LaserScanner* h);
 void laser_scanner_process(LaserScanner* h, int n_frames, int dtype, const void* images, const double* frame_pose7, double* centre,
                            double* amplitude, double* width_px, double* xyz, double* stage_ms);
 void laser_scanner_destroy(LaserScanner* h) noexcept;
+// structured_light.hip: the host pattern generator and the cba_sl_decoder handle (checked by the caller).  set_rig: two cameras of
+// one model, the camera then the projector; every output of process optional; stage_ms [4] optional: upload, decode, points, download
+void sl_patterns_host(const cba_sl_options& o, uint8_t* out);
+int sl_options_image_count(const cba_sl_options& o);
+struct SlDecoder;
+SlDecoder* sl_decoder_create(const cba_sl_options& o, int W, int H, int max_sequences, int device);
+int sl_decoder_max_sequences(const SlDecoder* h);
+bool sl_decoder_can_point(const SlDecoder* h);  // a rig is set and both axes are decoded
+void sl_decoder_set_rig(SlDecoder* h, int model, const double* intr, int n_inv, const double* inv, const double* c_T_r,
+                        const cba_triangulate_options& o);
+void sl_decoder_process(SlDecoder* h, int n_seq, const uint8_t* images, double* coord, double* modulation, uint8_t* status, double* xyz,
+                        double* rms_px, int32_t* tri_status, double* stage_ms);
+void sl_decoder_destroy(SlDecoder* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download
 void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device);

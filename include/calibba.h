@@ -931,6 +931,96 @@ cba_status cba_laser_scanner_process(cba_laser_scanner* h, int32_t n_frames, int
                                      double* xyz /*[n_frames][n_lines][3] or NULL*/);
 void cba_laser_scanner_destroy(cba_laser_scanner* h);
 
+/* ---- structured-light scanning: Gray-code and phase decode, points (no counterpart in the reference) --------------------------
+ *
+ * The third 3D front end: a projector and a camera.  A sequence of pattern images, taken by the camera while the projector shows
+ * cba_sl_patterns, becomes a projector coordinate for every camera pixel (cba_sl_decoder_process), and with a rig set a point map.
+ * A projector is calibrated as an inverse camera through the entry points that exist: decode a board's views, take the projector
+ * position of every detected corner (the Python layer's projector_corners: a local homography per corner, fitted to the valid
+ * pixels of the square window |du|, |dv| <= radius around rint(corner), by cba_estimate_homography_ransac_batch with opts == NULL,
+ * which is the all-points DLT of cba_estimate_homography_batch), and pass them with the board coordinates to the intrinsic and rig
+ * solvers.
+ *
+ * Options.  proj_width, proj_height in [2, CBA_IMAGE_MAX_SIDE]; axes: bit 0 = columns (decodes the projector x), bit 1 = rows (y), at
+ * least one; gray_skip_bits s >= 0: the s lowest Gray bits are not projected, a stripe is 2^s projector pixels wide; phase_steps N: 0
+ * = no phase patterns, else 3..8; phase_period T in integer projector pixels (used when N > 0, 1 <= T <= CBA_IMAGE_MAX_SIDE and
+ * T >= 2^(s+1)); min_contrast and min_bit_diff in 0..255; min_modulation finite and >= 0.  For an axis of P projector pixels
+ * nbits = max(1, ceil(log2 P)) - s, which must be >= 1.
+ *
+ * Sequence.  white, black, then for axis 0 and axis 1 (each only if selected): the nbits Gray planes, MSB first, each followed by
+ * its inverse, then the N phase steps k = 0..N-1.  n_images = 2 + sum over the axes of (2 nbits + N) (cba_sl_image_count).
+ *
+ * Patterns (cba_sl_patterns: host only, no device; out [n_images][proj_height][proj_width] uint8).  Coordinates are pixel indices:
+ * index j is the coordinate j.  White is 255, black 0.  Gray plane b at index j: c = j >> s, g = c ^ (c >> 1); 255 when bit
+ * nbits-1-b of g is set, else 0; the inverse is 255 minus that.  Phase step k at index j: m = (j N - k T) mod (N T) in [0, N T);
+ * c = cos(2 pi m / (N T)) by the C library, and c = 0 exactly when 4 m == N T or 4 m == 3 N T; the pixel is
+ * floor(127.5 (1 + c) + 0.5) clamped to [0, 255].  (127.5 (1 + c) + 0.5 is an integer only for rational c; cos of a rational
+ * multiple of pi is rational only at 0, +-1/2, +-1, and +-1/2 gives 191.25 and 63.75: with the exact zeros no pixel is a tie.)
+ * Column patterns are constant along y, row patterns along x.
+ *
+ * Decode, per camera pixel, from uint8 images [n_images][height][width]; everything up to the phase sums in exact integers.
+ * 1. white - black < min_contrast: status = 1 (bit 0 alone), every coordinate and modulation NaN, nothing else is evaluated.
+ * 2. Per selected axis, Gray bits: for each plane with pattern p and inverse q, |p - q| < min_bit_diff sets the axis's "uncertain"
+ *    bit: coordinate and modulation NaN, nothing else is evaluated for the axis.  Otherwise the bit is p > q; Gray to binary by the
+ *    prefix XOR from the MSB gives c; xg = c 2^s + (2^s - 1) / 2 (exact in fp64).  xg > P - 1 sets the axis's "outside" bit:
+ *    coordinate and modulation NaN.
+ * 3. N == 0: the coordinate is xg, the modulation NaN.
+ * 4. N > 0: ws[k] = sin(2 pi k / N), wc[k] = cos(2 pi k / N), formed once on the host in fp64 by the C library.  S = sum I_k ws[k],
+ *    C = sum I_k wc[k], ascending k from 0.0, each product rounded before it is added (no contraction).
+ *    modulation = (2 / N) sqrt(S S + C C), written whether or not the next test passes; modulation < min_modulation sets the axis's
+ *    "low modulation" bit and the coordinate is NaN.  phi = atan2(S, C), + 2 pi when negative; f = phi T / (2 pi);
+ *    kk = rint((xg - f) / T); coordinate = kk T + f.  No clamp to the projector: with T >= 2^(s+1) a stripe's half width is at most
+ *    T / 4, which leaves T / 4 of phase error before the unwrap slips.
+ * 5. status, one uint8: bit 0 contrast; bits 1..3 axis 0 uncertain, outside, low modulation; bits 4..6 the same for axis 1 (the
+ *    bits belong to the projector axis, whichever axes are selected); 0: every selected axis is valid.  An axis's coordinate is
+ *    finite exactly when its bits and bit 0 are clear.  A pixel's result depends on nothing but its own samples.
+ *
+ * Points.  With a rig set (cba_sl_decoder_set_rig) and both axes decoded: n_cams = 2 cameras {camera, projector} of one
+ * camera_model, intr [2][10 | 12], optional inverse_coeffs [2][n_inverse_coeffs], c_T_r [2][7], all as for cba_triangulate;
+ * uv_0 = (column, row), uv_1 = (x, y) of the decode, NaN where invalid.  xyz, rms_px and tri_status of the pixel are what
+ * cba_triangulate's rule gives for that point (the same code): a pixel with either axis NaN has CBA_TRI_TOO_FEW and NaN.  rms_px is
+ * the epipolar disagreement of the two axes and is the caller's quality gate.
+ *
+ * cba_sl_decoder: a handle that owns the options, one stream and device buffers sized at create for max_sequences sequences of
+ * width x height images (the point buffers when the rig is first set); cba_sl_decoder_process allocates nothing.  Outputs, each
+ * may be NULL: coord and modulation [n_sequences][n_axes][height][width] fp64 (the selected axes in order), status
+ * [n_sequences][height][width] uint8, xyz [n_sequences][height][width][3], rms_px [..][height][width], tri_status int32.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all before any device work): an option outside its range; nbits < 1; T < 2^(s+1) with N > 0;
+ * width or height outside [1, CBA_IMAGE_MAX_SIDE]; max_sequences < 1; max_sequences n_images width height > 2^31 - 1; n_sequences
+ * outside [0, max_sequences]; NULL options, out, handle, images (for n_sequences > 0), intr, c_T_r, tri_opts; point outputs asked
+ * for without a rig or with one axis only; what cba_triangulate rejects in the rig.  n_sequences == 0 is no work; otherwise no
+ * device -> CBA_ERR_NO_DEVICE. */
+typedef struct cba_sl_options {
+    int32_t proj_width, proj_height;
+    int32_t axes;           /* bit 0: columns (x), bit 1: rows (y) (default 3) */
+    int32_t gray_skip_bits; /* s (default 0) */
+    int32_t phase_steps;    /* N: 0 or 3..8 (default 0) */
+    int32_t phase_period;   /* T (default 16) */
+    int32_t min_contrast;   /* default 10 */
+    int32_t min_bit_diff;   /* default 4 */
+    double min_modulation;  /* default 5 */
+} cba_sl_options;
+typedef enum cba_sl_status_bits {
+    CBA_SL_LOW_CONTRAST = 1,
+    CBA_SL_X_UNCERTAIN = 2, CBA_SL_X_OUTSIDE = 4, CBA_SL_X_LOW_MODULATION = 8,
+    CBA_SL_Y_UNCERTAIN = 16, CBA_SL_Y_OUTSIDE = 32, CBA_SL_Y_LOW_MODULATION = 64
+} cba_sl_status_bits;
+void cba_sl_options_default(cba_sl_options* o); /* proj_width and proj_height are left at 0: the caller sets them */
+cba_status cba_sl_image_count(const cba_sl_options* opts, int32_t* n_images);
+cba_status cba_sl_patterns(const cba_sl_options* opts, uint8_t* out /*[n_images][proj_height][proj_width]*/);
+typedef struct cba_sl_decoder cba_sl_decoder; /* opaque: options, device buffers sized at create, one stream */
+cba_status cba_sl_decoder_create(const cba_sl_options* opts, int32_t width, int32_t height, int32_t max_sequences, int32_t device,
+                                 cba_sl_decoder** out);
+cba_status cba_sl_decoder_set_rig(cba_sl_decoder* h, int32_t camera_model, const double* intr /*[2][10 | 12]*/,
+                                  int32_t n_inverse_coeffs, const double* inverse_coeffs /*[2][n_inverse_coeffs] or NULL*/,
+                                  const double* c_T_r /*[2][7]*/, const cba_triangulate_options* tri_opts);
+cba_status cba_sl_decoder_process(cba_sl_decoder* h, int32_t n_sequences, const uint8_t* images /*[n_seq][n_images][H][W]*/,
+                                  double* coord /*[n_seq][n_axes][H][W] or NULL*/, double* modulation /*same shape, or NULL*/,
+                                  uint8_t* status /*[n_seq][H][W] or NULL*/, double* xyz /*[n_seq][H][W][3] or NULL*/,
+                                  double* rms_px /*[n_seq][H][W] or NULL*/, int32_t* tri_status /*[n_seq][H][W] or NULL*/);
+void cba_sl_decoder_destroy(cba_sl_decoder* h);
+
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
  *
  * What a calibrated two-camera rig is used for: calibrated pair -> rectified pair -> dense disparity -> 3D points.
