@@ -126,6 +126,13 @@ from .triangulate import (  # noqa: F401
     TriangulationResult,
     triangulate,
 )
+from .registration import (  # noqa: F401
+    CloudIndex,
+    IcpOptions,
+    IcpResult,
+    point_normals,
+    register,
+)
 from .structured_light import (  # noqa: F401
     Decoded,
     StructuredLightDecoder,

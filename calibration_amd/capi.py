@@ -180,6 +180,36 @@ class CbaSlOptions(C.Structure):
     ]
 
 
+class CbaIcpOptions(C.Structure):
+    """``cba_icp_options`` (calibba.h)."""
+
+    _fields_ = [
+        ("metric", C.c_int32),
+        ("max_distance", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("step_tolerance", C.c_double),
+        ("min_pairs", C.c_int32),
+    ]
+
+
+class CbaIcpResult(C.Structure):
+    """``cba_icp_result`` (calibba.h)."""
+
+    _fields_ = [
+        ("pose7", C.c_double * 7),
+        ("rms", C.c_double),
+        ("H", C.c_double * 36),
+        ("g", C.c_double * 6),
+        ("n_pairs", C.c_int64),
+        ("iterations", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+
+ICP_OK, ICP_NOT_CONVERGED, ICP_TOO_FEW, ICP_DEGENERATE = 0, 1, 2, 3
+CLOUD_MAX_CELLS = 1 << 24
+
+
 class CbaStereoRectifyOptions(C.Structure):
     """``cba_stereo_rectify_options`` (calibba.h)."""
 
@@ -488,6 +518,13 @@ PROTOTYPES = {
     "cba_sl_decoder_process": (
         C.c_int32, [C.c_void_p, C.c_int32, c_uint8_p, c_double_p, c_double_p, c_uint8_p, c_double_p, c_double_p, c_int32_p]),
     "cba_sl_decoder_destroy": (None, [C.c_void_p]),
+    "cba_point_normals": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_double, c_double_p]),
+    "cba_cloud_index_create": (C.c_int32, [C.c_int64, c_double_p, c_double_p, C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_cloud_nearest": (C.c_int32, [C.c_void_p, C.c_int64, c_double_p, C.c_double, c_int64_p, c_double_p]),
+    "cba_icp_options_default": (None, [C.POINTER(CbaIcpOptions)]),
+    "cba_cloud_register": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_int64_p, c_double_p, c_double_p, C.POINTER(CbaIcpOptions), C.POINTER(CbaIcpResult)]),
+    "cba_cloud_index_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (
         C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(CbaStereoRectifyOptions), c_double_p, c_double_p,

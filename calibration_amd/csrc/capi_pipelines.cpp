@@ -1,9 +1,10 @@
 // capi_pipelines.cpp — the extern "C" entry points of the batched pipelines (include/calibba.h): laser-plane calibration, the linear
-// seeds, the distortion fits, the camera models, triangulation, laser scanning, structured-light decoding, stereo depth (block and
+// seeds, the distortion fits, the camera models, triangulation, laser scanning, structured-light decoding, scan registration, stereo depth (block and
 // semi-global matching) and chessboard detection.  Host-side duties only, as in capi.cpp: validate the arguments, find the device, call
 // the pipeline (pipelines.hpp).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <limits>
 #include <vector>
 
@@ -946,6 +947,121 @@ __attribute__((visibility("default"))) cba_status cba_sl_decoder_process_timed(c
                                                                                double* xyz, double* rms_px, int32_t* tri_status,
                                                                                double* stage_ms) {
     return timed(stage_ms, [&] { return sl_decoder_process_impl(h, n_sequences, images, coord, modulation, status, xyz, rms_px, tri_status, stage_ms); });
+}
+#endif
+
+// ---- scan registration (cloud_register.hip, cloud_math.hpp) -------------------------------------------------------------------
+cba_status cba_point_normals(int32_t n_maps, int32_t height, int32_t width, const double* xyz, const double* viewpoint, double max_jump,
+                             double* normals) {
+    return guarded([&] {
+        if (n_maps < 0) throw std::invalid_argument("n_maps must be >= 0");
+        check_sides(width, height);
+        if (static_cast<int64_t>(n_maps) * width * height > 0x7fffffff) throw std::invalid_argument("n_maps width height must be <= 2^31 - 1");
+        if (!(max_jump > 0.0)) throw std::invalid_argument("max_jump must be > 0");
+        if (n_maps == 0) return;
+        if (!xyz || !normals) throw std::invalid_argument("null argument");
+        require_device();
+        point_normals_gpu(n_maps, height, width, xyz, viewpoint, max_jump, normals, default_device());
+    });
+}
+
+cba_status cba_cloud_index_create(int64_t n, const double* xyz, const double* normals, double cell_size, int32_t device, cba_cloud_index** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (n < 1 || n > 0x7fffffff) throw std::invalid_argument("n must be in [1, 2^31 - 1]");
+        if (!xyz) throw std::invalid_argument("null argument");
+        if (!std::isfinite(cell_size) || !(cell_size > 0.0)) throw std::invalid_argument("cell_size must be finite and > 0");
+        double fit = 0.0;
+        const int plan = cloud_plan(n, xyz, cell_size, &fit);
+        if (plan == 1) throw std::invalid_argument("the target has no valid point");
+        if (plan == 2) {
+            char fits[32];
+            std::snprintf(fits, sizeof fits, "%.6g", fit);
+            throw std::invalid_argument(std::string("cell_size gives more than 2^24 cells; a cell_size of ") + fits + " or more fits");
+        }
+        require_device(device);
+        *out = reinterpret_cast<cba_cloud_index*>(cloud_index_create(n, xyz, normals, cell_size, device));
+    });
+}
+
+static void check_cloud_distance(const CloudIndex* h, double max_distance) {
+    if (!std::isfinite(max_distance) || !(max_distance > 0.0) || max_distance > 0.999 * cloud_index_cell_size(h))
+        throw std::invalid_argument("max_distance must be > 0 and <= 0.999 cell_size");
+}
+
+cba_status cba_cloud_nearest(cba_cloud_index* h, int64_t m, const double* query, double max_distance, int64_t* index, double* dist2) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        CloudIndex* c = reinterpret_cast<CloudIndex*>(h);
+        if (m < 0 || m > 0x7fffffff) throw std::invalid_argument("m must be in [0, 2^31 - 1]");
+        check_cloud_distance(c, max_distance);
+        if (m == 0) return;
+        if (!query || !index) throw std::invalid_argument("null argument");
+        cloud_index_nearest(c, m, query, max_distance, index, dist2);
+    });
+}
+
+void cba_icp_options_default(cba_icp_options* o) {
+    if (!o) return;
+    o->metric = 0;
+    o->max_distance = 0.0;
+    o->max_iterations = 30;
+    o->step_tolerance = 1e-9;
+    o->min_pairs = 6;
+}
+
+static cba_status cloud_register_impl(cba_cloud_index* h, int32_t n_sources, const int64_t* source_offset, const double* source_xyz,
+                                      const double* init_pose7, const cba_icp_options* opts, cba_icp_result* results, double* stage_ms) {
+    return guarded([&] {
+        if (!h || !opts) throw std::invalid_argument("null argument");
+        CloudIndex* c = reinterpret_cast<CloudIndex*>(h);
+        if (n_sources < 0) throw std::invalid_argument("n_sources must be >= 0");
+        if (opts->metric != 0 && opts->metric != 1) throw std::invalid_argument("metric must be 0 or 1");
+        if (opts->metric == 0 && !cloud_index_has_normals(c)) throw std::invalid_argument("metric 0 needs an index with normals");
+        check_cloud_distance(c, opts->max_distance);
+        if (opts->max_iterations < 0 || opts->max_iterations > CBA_ICP_MAX_ITERATIONS)
+            throw std::invalid_argument("max_iterations must be in [0, 10000]");
+        if (!std::isfinite(opts->step_tolerance) || opts->step_tolerance < 0.0) throw std::invalid_argument("step_tolerance must be finite and >= 0");
+        if (n_sources == 0) return;
+        if (!source_offset || !results) throw std::invalid_argument("null argument");
+        check_offsets(source_offset, n_sources, "source ", OFF_FROM_ZERO | OFF_INT32_GROUPS);
+        if (source_offset[n_sources] > 0 && !source_xyz) throw std::invalid_argument("null argument");
+        for (int32_t i = 0; i < n_sources; ++i) {
+            cba_icp_result& r = results[i];
+            r = cba_icp_result{};
+            r.pose7[0] = 1.0;
+            if (init_pose7) {
+#pragma clang fp contract(off)
+                double q[4] = {init_pose7[7 * i], init_pose7[7 * i + 1], init_pose7[7 * i + 2], init_pose7[7 * i + 3]};
+                const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+                if (!(nq > 0.0) || !std::isfinite(nq) || !std::isfinite(init_pose7[7 * i + 4]) || !std::isfinite(init_pose7[7 * i + 5]) ||
+                    !std::isfinite(init_pose7[7 * i + 6]))
+                    throw std::invalid_argument("init_pose7 needs a non-zero finite quaternion and a finite translation");
+                for (int k = 0; k < 4; ++k) r.pose7[k] = q[k] / nq;
+                for (int k = 4; k < 7; ++k) r.pose7[k] = init_pose7[7 * i + k];
+            }
+            r.status = CBA_ICP_NOT_CONVERGED;
+        }
+        cloud_index_register(c, n_sources, source_offset, source_xyz, *opts, results, stage_ms);
+    });
+}
+
+cba_status cba_cloud_register(cba_cloud_index* h, int32_t n_sources, const int64_t* source_offset, const double* source_xyz,
+                              const double* init_pose7, const cba_icp_options* opts, cba_icp_result* results) {
+    return cloud_register_impl(h, n_sources, source_offset, source_xyz, init_pose7, opts, results, nullptr);
+}
+
+void cba_cloud_index_destroy(cba_cloud_index* h) { cloud_index_destroy(reinterpret_cast<CloudIndex*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_registration.py): cba_cloud_register timing its stages on the device (stage_ms [3] = upload,
+// rounds, download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_cloud_register_timed(cba_cloud_index* h, int32_t n_sources, const int64_t* source_offset,
+                                                                           const double* source_xyz, const double* init_pose7,
+                                                                           const cba_icp_options* opts, cba_icp_result* results,
+                                                                           double* stage_ms) {
+    return timed(stage_ms, [&] { return cloud_register_impl(h, n_sources, source_offset, source_xyz, init_pose7, opts, results, stage_ms); });
 }
 #endif
 

@@ -109,6 +109,19 @@ void sl_decoder_set_rig(SlDecoder* h, int model, const double* intr, int n_inv, 
 void sl_decoder_process(SlDecoder* h, int n_seq, const uint8_t* images, double* coord, double* modulation, uint8_t* status, double* xyz,
                         double* rms_px, int32_t* tri_status, double* stage_ms);
 void sl_decoder_destroy(SlDecoder* h) noexcept;
+// cloud_register.hip: cba_point_normals and the cba_cloud_index handle (checked by the caller).  cloud_plan: the host's grid plan of a
+// target (0, or 1: no valid point, 2: too many cells, *fit then a cell size that fits).  register: results holds the normalised
+// initial poses on entry (iterations 0, the rest zero); stage_ms [3] optional: upload, rounds, download
+void point_normals_gpu(int n_maps, int H, int W, const double* xyz, const double* viewpoint, double max_jump, double* normals, int device);
+int cloud_plan(int64_t n, const double* xyz, double cell_size, double* fit);
+struct CloudIndex;
+CloudIndex* cloud_index_create(int64_t n, const double* xyz, const double* normals, double cell_size, int device);
+double cloud_index_cell_size(const CloudIndex* h);
+bool cloud_index_has_normals(const CloudIndex* h);
+void cloud_index_nearest(CloudIndex* h, int64_t m, const double* query, double max_distance, int64_t* index, double* dist2);
+void cloud_index_register(CloudIndex* h, int n_sources, const int64_t* source_offset, const double* source_xyz, const cba_icp_options& o,
+                          cba_icp_result* results, double* stage_ms);
+void cloud_index_destroy(CloudIndex* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download
 void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device);

@@ -1021,6 +1021,110 @@ cba_status cba_sl_decoder_process(cba_sl_decoder* h, int32_t n_sequences, const 
                                   double* rms_px /*[n_seq][H][W] or NULL*/, int32_t* tri_status /*[n_seq][H][W] or NULL*/);
 void cba_sl_decoder_destroy(cba_sl_decoder* h);
 
+/* ---- scan registration: grid neighbour search, normals, ICP (no counterpart in the reference) ----------------------------------
+ *
+ * What comes after a 3D front end: the points of one view are brought into the frame of another.  Everything is fp64.  No product
+ * or sum named below is contracted into an FMA (as in cba_laser_points), so a restatement in IEEE operations can be held to the
+ * bit.  An invalid point is one with a non-finite coordinate, which is how every front end here marks one.
+ *
+ * 1. cba_point_normals: normals of organised point maps xyz [n_maps][height][width][3] (what the stereo, SGM and structured-light
+ *    handles write) -> normals of the same shape.  viewpoint [3], NULL = the origin; max_jump > 0, +inf allowed.  Per pixel with a
+ *    valid centre P; a neighbour "qualifies" when it is inside the map, valid and ((ex ex + ey ey) + ez ez) <= max_jump max_jump with
+ *    e = neighbour - P.
+ *    Horizontal difference dx: P(x+1) - P(x-1) when both qualify; else P(x+1) - P when the right one does; else P - P(x-1) when the
+ *    left one does; else there is no normal.  Vertical difference dy: the same with the row below (y+1) in the place of the right
+ *    neighbour and the row above in the place of the left one.
+ *    n = dx x dy, each component a b - c d with both products rounded: (dx_y dy_z - dx_z dy_y, dx_z dy_x - dx_x dy_z,
+ *    dx_x dy_y - dx_y dy_x); len = sqrt((nx nx + ny ny) + nz nz); a len that is zero or non-finite gives no normal; n = n / len
+ *    (three divisions).  Orientation: v = viewpoint - P, s = (nx vx + ny vy) + nz vz; n is negated when s < 0 and left as it is
+ *    when s >= 0.  No normal: NaN in all three coordinates.  A pixel's result depends only on its own 5-point cross.
+ *
+ * 2. cba_cloud_index: a uniform grid over a target cloud xyz [n][3] (1 <= n <= 2^31 - 1, at least one valid point) with optional
+ *    normals [n][3], built once on the device by cba_cloud_index_create; the handle owns one stream and all device buffers.  Invalid
+ *    points are skipped but keep their indices.  lo, hi: the exact minima and maxima of the valid points; cells along axis k:
+ *    n_k = floor((hi_k - lo_k) / cell_size) + 1; n_x n_y n_z may not exceed CBA_CLOUD_MAX_CELLS: beyond that create fails with a
+ *    message that names a cell size that fits (there is no silent coarsening).  The cell of a coordinate is
+ *    c_k = min(n_k - 1, (int)floor((p_k - lo_k) / cell_size)): one subtraction, one division.  Cells are numbered x fastest.  Build:
+ *    a count per cell (integer atomics, independent of arrival order), an exclusive scan over the cells, a scatter of 32-byte records
+ *    {x, y, z, original index} into cell order, the normals into a parallel array.  The order of the points inside a cell may
+ *    depend on arrival; no result does (the tie rule below).  Float atomics are used nowhere.
+ *
+ * 3. cba_cloud_nearest: for each query [m][3] the nearest valid target point within max_distance, 0 < max_distance <=
+ *    0.999 cell_size (the product rounded).  The result is, to the bit, brute force over all valid target points y: d = q - y per
+ *    coordinate, d2 = ((dx dx + dy dy) + dz dz); the smallest d2 with d2 <= max_distance max_distance wins, equal d2 goes to the
+ *    lowest original index; index [m] int64 receives the original index and dist2 [m] (optional) d2.  None, or an invalid query:
+ *    index -1 and dist2 NaN.  A query with lo_k - q_k > max_distance or q_k - hi_k > max_distance on an axis (the differences
+ *    rounded) returns -1 without touching the grid: every d2 is then above the bar, and the test keeps the cell arithmetic of the
+ *    others inside [-1, n_k].  Otherwise the cells c_k - 1 .. c_k + 1 of the query's unclamped c_k, cut to the grid, are searched:
+ *    9 runs of the sorted records.  The 0.1 % covers the rounding of the two quotients (at most about 2^-28 of a cell at the largest
+ *    grid), so this neighbourhood holds every point within the radius.
+ *
+ * 4. cba_cloud_register: ICP of n_sources point sets onto the index.  Source i is source_xyz[source_offset[i] ..
+ *    source_offset[i+1]); init_pose7 [n_sources][7] = [qw qx qy qz tx ty tz] maps source to target, NULL = identities; its quaternion
+ *    is normalised once on entry: |q| = sqrt(((w w + x x) + y y) + z z), four divisions; zero or non-finite is an argument error.
+ *    R of a unit q: xx = x x, ... wz = w z; R00 = 1 - 2 (yy + zz), R01 = 2 (xy - wz), R02 = 2 (xz + wy), R10 = 2 (xy + wz),
+ *    R11 = 1 - 2 (xx + zz), R12 = 2 (yz - wx), R20 = 2 (xz - wy), R21 = 2 (yz + wx), R22 = 1 - 2 (xx + yy).
+ *    The system at a pose (q, t): for every valid source point p, in index order: Q_i = ((R_i0 p_0 + R_i1 p_1) + R_i2 p_2) + t_i;
+ *    j = the neighbour of Q by rule 3 with opts->max_distance; none: no pair; metric 0 and a NaN normal at j: no pair.
+ *    Metric 0 (point to plane): e = Q - y_j, r = (n_0 e_0 + n_1 e_1) + n_2 e_2, J = [Q_1 n_2 - Q_2 n_1, Q_2 n_0 - Q_0 n_2,
+ *    Q_0 n_1 - Q_1 n_0, n_0, n_1, n_2].  Metric 1 (point to point): three rows, r = Q_0 - y_0 with J = [0, Q_2, -Q_1, 1, 0, 0], then
+ *    r = Q_1 - y_1 with [-Q_2, 0, Q_0, 0, 1, 0], then r = Q_2 - y_2 with [Q_1, -Q_0, 0, 0, 0, 1].  H = sum J^T J (21 distinct
+ *    entries, mirrored into H[36], row-major), g = sum J^T r, ss = sum r r, n_pairs counts pairs (not rows).
+ *    Iteration: form the system.  n_pairs < min_pairs ends with CBA_ICP_TOO_FEW (values of min_pairs below 6 for metric 0 or 3 for
+ *    metric 1 mean 6 or 3).  iterations == max_iterations ends with CBA_ICP_NOT_CONVERGED (so max_iterations = 0 gives the statistics
+ *    at the initial pose).  Solve H xi = -g by unpivoted 6 x 6 Cholesky, xi = (omega, v): row k has d = H_kk - sum_j<k L_kj L_kj; the
+ *    solve fails unless d > 1e-12 H_kk (scale-free; a single plane under metric 0 ends here), and a failed solve ends with
+ *    CBA_ICP_DEGENERATE.  Update: th = |omega| = sqrt((w0 w0 + w1 w1) + w2 w2); dq = [cos(th/2), (sin(th/2) / th) omega], the identity
+ *    when th == 0; q <- (dq (x) q) / |dq (x) q| (Hamilton product, each component summed left to right in w, x, y, z order of dq);
+ *    t <- R(dq) t + v by the forms of R and Q above.  iterations counts the updates.  The update with th <= step_tolerance and
+ *    |v| <= step_tolerance extent (extent: the length of the index's box diagonal, ((ex ex + ey ey) + ez ez) under the root) is the
+ *    last one and gives CBA_ICP_OK; otherwise the max_iterations-th update is the last one and gives CBA_ICP_NOT_CONVERGED.  After
+ *    the last update the system is formed once more, for the statistics alone.  In every case rms = sqrt(ss / n_pairs) (NaN when
+ *    n_pairs == 0), n_pairs, H and g are those of the system at the returned pose.
+ *    A source's result depends on nothing but its own points and pose: not on the other sources of the call, not on how the device
+ *    splits the work; two calls give the same bits.  (Sums are added in a fixed order: per lane in index order with a fixed stride,
+ *    a fixed tree inside the wave and the workgroup, then the workgroups of a source in order.)  The sine and cosine of the update
+ *    are the device's.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all before any device work): NULL xyz, normals (the output of cba_point_normals), out, handle,
+ * query, index, source_offset, source_xyz, opts, results where one is needed; n_maps < 0, width or height outside
+ * [1, CBA_IMAGE_MAX_SIDE], n_maps width height > 2^31 - 1; max_jump not > 0; n outside [1, 2^31 - 1]; cell_size not finite and > 0;
+ * no valid target point; too many cells; m < 0; max_distance not finite, not > 0 or above 0.999 cell_size; n_sources < 0; offsets
+ * that decrease, do not start at 0 or give a source more than 2^31 - 1 points; a metric other than 0 or 1; metric 0 on an index
+ * without normals; max_iterations outside [0, CBA_ICP_MAX_ITERATIONS]; step_tolerance not finite or < 0; a bad initial quaternion.
+ * n_maps == 0, m == 0 and n_sources == 0 are no work; otherwise no device -> CBA_ERR_NO_DEVICE. */
+#define CBA_CLOUD_MAX_CELLS (1 << 24)
+#define CBA_ICP_MAX_ITERATIONS 10000
+typedef struct cba_icp_options {
+    int32_t metric;         /* 0: point-to-plane (the index must hold normals), 1: point-to-point (default 0) */
+    double max_distance;    /* correspondence gate, as in cba_cloud_nearest (no default: the caller sets it) */
+    int32_t max_iterations; /* default 30; 0: only the statistics at the initial pose */
+    double step_tolerance;  /* default 1e-9 */
+    int32_t min_pairs;      /* default 6; values below 6 (plane) or 3 (point) mean 6 or 3 */
+} cba_icp_options;
+typedef enum cba_icp_status { CBA_ICP_OK = 0, CBA_ICP_NOT_CONVERGED = 1, CBA_ICP_TOO_FEW = 2, CBA_ICP_DEGENERATE = 3 } cba_icp_status;
+typedef struct cba_icp_result {
+    double pose7[7];
+    double rms;
+    double H[36];
+    double g[6];
+    int64_t n_pairs;
+    int32_t iterations;
+    int32_t status; /* cba_icp_status */
+} cba_icp_result;
+cba_status cba_point_normals(int32_t n_maps, int32_t height, int32_t width, const double* xyz /*[n_maps][height][width][3]*/,
+                             const double* viewpoint /*[3] or NULL*/, double max_jump, double* normals /*[n_maps][height][width][3]*/);
+typedef struct cba_cloud_index cba_cloud_index; /* opaque: the grid, the sorted target, the buffers of its calls, one stream */
+cba_status cba_cloud_index_create(int64_t n, const double* xyz /*[n][3]*/, const double* normals /*[n][3] or NULL*/, double cell_size,
+                                  int32_t device, cba_cloud_index** out);
+cba_status cba_cloud_nearest(cba_cloud_index* h, int64_t m, const double* query /*[m][3]*/, double max_distance, int64_t* index /*[m]*/,
+                             double* dist2 /*[m] or NULL*/);
+void cba_icp_options_default(cba_icp_options* o); /* max_distance is left at 0: the caller sets it */
+cba_status cba_cloud_register(cba_cloud_index* h, int32_t n_sources, const int64_t* source_offset /*[n_sources + 1]*/,
+                              const double* source_xyz /*[m][3]*/, const double* init_pose7 /*[n_sources][7] or NULL*/,
+                              const cba_icp_options* opts, cba_icp_result* results /*[n_sources]*/);
+void cba_cloud_index_destroy(cba_cloud_index* h);
+
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
  *
  * What a calibrated two-camera rig is used for: calibrated pair -> rectified pair -> dense disparity -> 3D points.
