@@ -133,6 +133,12 @@ from .registration import (  # noqa: F401
     point_normals,
     register,
 )
+from .fusion import (  # noqa: F401
+    TsdfOptions,
+    TsdfVolume,
+    depth_from_xyz,
+    fuse,
+)
 from .structured_light import (  # noqa: F401
     Decoded,
     StructuredLightDecoder,

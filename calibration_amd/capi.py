@@ -210,6 +210,15 @@ ICP_OK, ICP_NOT_CONVERGED, ICP_TOO_FEW, ICP_DEGENERATE = 0, 1, 2, 3
 CLOUD_MAX_CELLS = 1 << 24
 
 
+class CbaTsdfOptions(C.Structure):
+    """``cba_tsdf_options`` (calibba.h)."""
+
+    _fields_ = [("voxel_size", C.c_double), ("truncation", C.c_double), ("max_weight", C.c_double), ("max_depth", C.c_double)]
+
+
+TSDF_MAX_VOXELS = 1 << 28
+
+
 class CbaStereoRectifyOptions(C.Structure):
     """``cba_stereo_rectify_options`` (calibba.h)."""
 
@@ -525,6 +534,16 @@ PROTOTYPES = {
     "cba_cloud_register": (
         C.c_int32, [C.c_void_p, C.c_int32, c_int64_p, c_double_p, c_double_p, C.POINTER(CbaIcpOptions), C.POINTER(CbaIcpResult)]),
     "cba_cloud_index_destroy": (None, [C.c_void_p]),
+    "cba_tsdf_options_default": (None, [C.POINTER(CbaTsdfOptions)]),
+    "cba_tsdf_volume_create": (
+        C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.POINTER(CbaTsdfOptions), C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_tsdf_integrate": (C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p]),
+    "cba_tsdf_fetch": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cba_tsdf_upload": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cba_tsdf_reset": (C.c_int32, [C.c_void_p]),
+    "cba_tsdf_extract": (C.c_int32, [C.c_void_p, C.c_double, c_int64_p]),
+    "cba_tsdf_extract_fetch": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
+    "cba_tsdf_volume_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (
         C.c_int32, [C.c_int32, c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(CbaStereoRectifyOptions), c_double_p, c_double_p,

@@ -1,5 +1,5 @@
 // capi_pipelines.cpp — the extern "C" entry points of the batched pipelines (include/calibba.h): laser-plane calibration, the linear
-// seeds, the distortion fits, the camera models, triangulation, laser scanning, structured-light decoding, scan registration, stereo depth (block and
+// seeds, the distortion fits, the camera models, triangulation, laser scanning, structured-light decoding, scan registration, scan fusion, stereo depth (block and
 // semi-global matching) and chessboard detection.  Host-side duties only, as in capi.cpp: validate the arguments, find the device, call
 // the pipeline (pipelines.hpp).
 #include <algorithm>
@@ -1062,6 +1062,117 @@ __attribute__((visibility("default"))) cba_status cba_cloud_register_timed(cba_c
                                                                            const cba_icp_options* opts, cba_icp_result* results,
                                                                            double* stage_ms) {
     return timed(stage_ms, [&] { return cloud_register_impl(h, n_sources, source_offset, source_xyz, init_pose7, opts, results, stage_ms); });
+}
+#endif
+
+// ---- scan fusion (tsdf_fusion.hip, tsdf_math.hpp) ------------------------------------------------------------------------------
+void cba_tsdf_options_default(cba_tsdf_options* o) {
+    if (!o) return;
+    o->voxel_size = 0.0;
+    o->truncation = 0.0;
+    o->max_weight = 64.0;
+    o->max_depth = std::numeric_limits<double>::infinity();
+}
+
+cba_status cba_tsdf_volume_create(int32_t nx, int32_t ny, int32_t nz, const double* origin, const cba_tsdf_options* opts, int32_t device,
+                                  cba_tsdf_volume** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (!origin || !opts) throw std::invalid_argument("null argument");
+        if (std::min({nx, ny, nz}) < 2 || std::max({nx, ny, nz}) > 1024) throw std::invalid_argument("nx, ny and nz must be in [2, 1024]");
+        if (static_cast<int64_t>(nx) * ny * nz > CBA_TSDF_MAX_VOXELS) throw std::invalid_argument("nx ny nz must be <= 2^28");
+        if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) throw std::invalid_argument("origin must be finite");
+        if (!std::isfinite(opts->voxel_size) || !(opts->voxel_size > 0.0)) throw std::invalid_argument("voxel_size must be finite and > 0");
+        if (!std::isfinite(opts->truncation) || !(opts->truncation > 0.0)) throw std::invalid_argument("truncation must be finite and > 0");
+        if (!(opts->max_weight >= 1.0 && opts->max_weight <= 16777216.0) || opts->max_weight != std::floor(opts->max_weight))
+            throw std::invalid_argument("max_weight must be an integer value in [1, 2^24]");
+        if (!(opts->max_depth > 0.0)) throw std::invalid_argument("max_depth must be > 0");
+        require_device(device);
+        *out = reinterpret_cast<cba_tsdf_volume*>(tsdf_volume_create(nx, ny, nz, origin, *opts, device));
+    });
+}
+
+static cba_status tsdf_integrate_impl(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_maps, int32_t height, int32_t width,
+                                      const double* depth, const double* c_T_v, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        check_camera(camera_model, intr, 0, nullptr);
+        if (intr[0] == 0.0 || intr[1] == 0.0) throw std::invalid_argument("fx and fy must not be 0");
+        if (n_maps < 0) throw std::invalid_argument("n_maps must be >= 0");
+        check_sides(width, height);
+        if (n_maps == 0) return;
+        if (!depth || !c_T_v) throw std::invalid_argument("null argument");
+        for (int32_t m = 0; m < n_maps; ++m) {
+#pragma clang fp contract(off)
+            const double* q = c_T_v + 7 * static_cast<size_t>(m);
+            const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+            if (!(nq > 0.0) || !std::isfinite(nq)) throw std::invalid_argument("c_T_v needs a non-zero finite quaternion");
+        }
+        tsdf_volume_integrate(reinterpret_cast<TsdfVolume*>(h), camera_model, intr, n_maps, height, width, depth, c_T_v, stage_ms);
+    });
+}
+
+cba_status cba_tsdf_integrate(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_maps, int32_t height, int32_t width,
+                              const double* depth, const double* c_T_v) {
+    return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, c_T_v, nullptr);
+}
+
+cba_status cba_tsdf_fetch(cba_tsdf_volume* h, float* tsdf, float* weight) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        if (tsdf || weight) tsdf_volume_fetch(reinterpret_cast<TsdfVolume*>(h), tsdf, weight);
+    });
+}
+
+cba_status cba_tsdf_upload(cba_tsdf_volume* h, const float* tsdf, const float* weight) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        if (tsdf || weight) tsdf_volume_upload(reinterpret_cast<TsdfVolume*>(h), tsdf, weight);
+    });
+}
+
+cba_status cba_tsdf_reset(cba_tsdf_volume* h) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        tsdf_volume_reset(reinterpret_cast<TsdfVolume*>(h));
+    });
+}
+
+static cba_status tsdf_extract_impl(cba_tsdf_volume* h, double min_weight, int64_t* n_points, double* stage_ms) {
+    return guarded([&] {
+        if (!h || !n_points) throw std::invalid_argument("null argument");
+        if (!(min_weight >= 1.0)) throw std::invalid_argument("min_weight must be >= 1");
+        tsdf_volume_extract(reinterpret_cast<TsdfVolume*>(h), min_weight, n_points, stage_ms);
+    });
+}
+
+cba_status cba_tsdf_extract(cba_tsdf_volume* h, double min_weight, int64_t* n_points) { return tsdf_extract_impl(h, min_weight, n_points, nullptr); }
+
+cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz, double* normals) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (tsdf_volume_points(v) < 0) throw std::invalid_argument("no extract has run on this volume");
+        if (tsdf_volume_points(v) == 0) return;
+        if (!xyz) throw std::invalid_argument("null argument");
+        tsdf_volume_extract_fetch(v, xyz, normals);
+    });
+}
+
+void cba_tsdf_volume_destroy(cba_tsdf_volume* h) { tsdf_volume_destroy(reinterpret_cast<TsdfVolume*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_fusion.py): integrate and extract timing their stages on the device (stage_ms [2] = upload,
+// kernel; count and scan, place).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_tsdf_integrate_timed(cba_tsdf_volume* h, int32_t camera_model, const double* intr,
+                                                                           int32_t n_maps, int32_t height, int32_t width, const double* depth,
+                                                                           const double* c_T_v, double* stage_ms) {
+    return timed(stage_ms, [&] { return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, c_T_v, stage_ms); });
+}
+__attribute__((visibility("default"))) cba_status cba_tsdf_extract_timed(cba_tsdf_volume* h, double min_weight, int64_t* n_points,
+                                                                         double* stage_ms) {
+    return timed(stage_ms, [&] { return tsdf_extract_impl(h, min_weight, n_points, stage_ms); });
 }
 #endif
 

@@ -3,8 +3,8 @@
 //   k_point_normals     one lane per pixel: the centre and its four neighbours straight from global memory (a row is read by three
 //                       rows of lanes, which the caches serve), cloud_normal.
 //   k_cloud_count       one lane per target point: its cell into cell_of (-1: invalid), integer atomicAdd on the cell's count.
-//   k_scan_tiles / k_scan_add   exclusive scan of the counts in tiles of CLOUD_SCAN_TILE = 1024 cells (256 lanes, 4 cells each, the
-//                       lanes' sums scanned in LDS); the tile sums are scanned by the same kernels, up to three levels at the cap.
+//   k_scan_tiles / k_scan_add   (scan_tiles.hpp) exclusive scan of the counts in tiles of CLOUD_SCAN_TILE = 1024 cells (256 lanes, 4 cells
+//                       each, the lanes' sums scanned in LDS); the tile sums are scanned by the same kernels, up to three levels at the cap.
 //   k_cloud_scatter     one lane per valid point: its place by integer atomicAdd on the cell's start, the 32-byte record and the
 //                       normal into cell order.  The starts live at start + 1 while they are bumped: afterwards start[c + 1] is the
 //                       end of cell c, which is the start of cell c + 1, and start[0] = 0 was never touched.
@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "pipelines.hpp"
+#include "scan_tiles.hpp"
 #include "wave_reduce.hpp"
 #include "cloud_math.hpp"
 
@@ -27,7 +28,7 @@ namespace cba {
 
 constexpr int CLOUD_BLOCK = 256;
 constexpr int CLOUD_GRID = 8192;        // grid-stride cap
-constexpr int CLOUD_SCAN_TILE = 1024;   // cells per workgroup of the scan
+constexpr int CLOUD_SCAN_TILE = SCAN_TILE;  // cells per workgroup of the scan (scan_tiles.hpp)
 constexpr int ICP_BLOCKS = 128;         // workgroups per source: fixed, so a source's sums do not depend on the call
 constexpr int ICP_POLL = 4;             // rounds between two looks at the done count
 
@@ -79,42 +80,6 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_count(int64_t n, const do
         }
         cell_of[i] = c;
     }
-}
-
-// v [n] -> its exclusive scan inside each tile of CLOUD_SCAN_TILE entries; sums [tiles]: each tile's total.  One workgroup per tile.
-__global__ __launch_bounds__(CLOUD_BLOCK) void k_scan_tiles(int64_t n, int32_t* __restrict__ v, int32_t* __restrict__ sums) {
-    __shared__ int32_t part[CLOUD_BLOCK];
-    const int t = threadIdx.x;
-    const int64_t at = static_cast<int64_t>(blockIdx.x) * CLOUD_SCAN_TILE + 4 * t;
-    int32_t a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = at + k < n ? v[at + k] : 0;
-    const int32_t mine = (a[0] + a[1]) + (a[2] + a[3]);
-    part[t] = mine;
-    __syncthreads();
-    // inclusive scan of the 256 lane sums (integers: any order gives the same)
-    for (int d = 1; d < CLOUD_BLOCK; d <<= 1) {
-        const int32_t add = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    int32_t run = part[t] - mine;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (at + k < n) v[at + k] = run;
-        run += a[k];
-    }
-    if (t == CLOUD_BLOCK - 1) sums[blockIdx.x] = part[t];
-}
-
-// v [n] += the scanned total of the tiles before its own
-__global__ __launch_bounds__(CLOUD_BLOCK) void k_scan_add(int64_t n, int32_t* __restrict__ v, const int32_t* __restrict__ sums) {
-    const int64_t at = static_cast<int64_t>(blockIdx.x) * CLOUD_SCAN_TILE + 4 * threadIdx.x;
-    const int32_t add = sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (at + k < n) v[at + k] += add;
 }
 
 __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_scatter(int64_t n, const double* __restrict__ xyz, const double* __restrict__ normals,
@@ -265,16 +230,6 @@ int cloud_plan(int64_t n, const double* xyz, double cell_size, double* fit) {
     return cloud_plan_grid(n, xyz, cell_size, &g, &extent, &n_cells, fit);
 }
 
-// exclusive scan of v [n] in place on s; tmp: room for the tile sums of every level
-static void scan_exclusive(hipStream_t s, int32_t* v, int64_t n, int32_t* tmp) {
-    const int64_t tiles = (n + CLOUD_SCAN_TILE - 1) / CLOUD_SCAN_TILE;
-    hipLaunchKernelGGL(k_scan_tiles, dim3(static_cast<unsigned>(tiles)), dim3(CLOUD_BLOCK), 0, s, n, v, tmp);
-    if (tiles > 1) {
-        scan_exclusive(s, tmp, tiles, tmp + tiles);
-        hipLaunchKernelGGL(k_scan_add, dim3(static_cast<unsigned>(tiles)), dim3(CLOUD_BLOCK), 0, s, n, v, tmp);
-    }
-}
-
 CloudIndex* cloud_index_create(int64_t n, const double* xyz, const double* normals, double cell_size, int device) {
     auto h = std::make_unique<CloudIndex>(device);
     double fit;
@@ -287,12 +242,7 @@ CloudIndex* cloud_index_create(int64_t n, const double* xyz, const double* norma
     pts.assign(xyz, static_cast<size_t>(3 * n), s);
     if (normals) nrm.assign(normals, static_cast<size_t>(3 * n), s);
     cell_of.alloc(static_cast<size_t>(n));
-    size_t tmp_n = 0;
-    for (int64_t t = h->n_cells; t > 1;) {
-        t = (t + CLOUD_SCAN_TILE - 1) / CLOUD_SCAN_TILE;
-        tmp_n += static_cast<size_t>(t);
-    }
-    tmp.alloc(tmp_n + 1);
+    tmp.alloc(scan_tmp_size(h->n_cells));
     h->start.alloc(static_cast<size_t>(h->n_cells) + 1);
     h->start.zero(s);
     h->rec.alloc(static_cast<size_t>(n));

@@ -122,6 +122,19 @@ void cloud_index_nearest(CloudIndex* h, int64_t m, const double* query, double m
 void cloud_index_register(CloudIndex* h, int n_sources, const int64_t* source_offset, const double* source_xyz, const cba_icp_options& o,
                           cba_icp_result* results, double* stage_ms);
 void cloud_index_destroy(CloudIndex* h) noexcept;
+// tsdf_fusion.hip: the cba_tsdf_volume handle (checked by the caller).  integrate: stage_ms [2] optional: upload, kernel; extract:
+// stage_ms [2] optional: count and scan, place.  points: the count of the last extract, -1 before the first
+struct TsdfVolume;
+TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, const cba_tsdf_options& o, int device);
+int64_t tsdf_volume_points(const TsdfVolume* h);
+void tsdf_volume_reset(TsdfVolume* h);
+void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
+                           double* stage_ms);
+void tsdf_volume_fetch(TsdfVolume* h, float* tsdf, float* weight);
+void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight);
+void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms);
+void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals);
+void tsdf_volume_destroy(TsdfVolume* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download
 void stereo_points_gpu(const cba_stereo_geometry& geom, const double* pose7, int64_t n, const double* uvd, double* xyz, int device);

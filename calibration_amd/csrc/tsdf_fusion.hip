@@ -1,0 +1,288 @@
+// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, calibba.h: cba_tsdf_volume, cba_tsdf_integrate, cba_tsdf_extract).
+//   k_tsdf_fill         D = 1, W = 0 in every stored voxel (create, reset).
+//   k_tsdf_integrate    one launch per call.  A lane owns two adjacent x voxels, one aligned 16-byte {D, W, D, W} word that it loads
+//                       once, keeps in registers while it walks the call's maps in order, and stores once: the whole word when both
+//                       voxels were updated, 8 bytes when one was, nothing otherwise.  The camera and the pose of map m are tables
+//                       indexed by wave-uniform values alone (scalar loads, as in k_triangulate).  Per voxel and map: tsdf_update,
+//                       one fp64 projection and one 8-byte gather from the map; neighbouring voxels gather neighbouring pixels.  No
+//                       LDS, no atomics; no lane reads another's voxel.
+//   k_tsdf_planes       the interleaved rows <-> dense [nz][ny][nx] planes of D and of W (fetch, upload).
+//   k_tsdf_extract<0>   one workgroup per tile of TSDF_EXTRACT_TILE voxels of the dense order, in four rounds of 256 voxels: each lane
+//                       tests the three edges of its voxel; ballots and popcounts give the wave's total, LDS the workgroup's.
+//   k_scan_tiles / k_scan_add   (scan_tiles.hpp) the exclusive scan of the tile counts; one extra entry receives the total.
+//   k_tsdf_extract<1>   the same walk again: an edge's place is its tile's start, the rounds and waves before it, and the popcount of
+//                       the ballots below its lane, so the order is the visiting order whatever the arrival order; tsdf_edge_point.
+// The handle owns one stream and every buffer; a call grows a buffer that is too small and allocates nothing else; every call ends
+// with the stream synchronised.  No float atomics, and no integer ones either.
+#include <memory>
+#include <type_traits>
+#include <vector>
+
+#include "pipelines.hpp"
+#include "scan_tiles.hpp"
+#include "tsdf_math.hpp"
+
+namespace cba {
+
+constexpr int TSDF_BLOCK = 256;
+constexpr int TSDF_GRID = 8192;  // grid-stride cap of the fill and plane kernels
+static_assert(TSDF_EXTRACT_TILE == 4 * TSDF_BLOCK, "k_tsdf_extract walks a tile in four rounds");
+
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_fill(int64_t n_stored, float2* __restrict__ vol) {
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x; i < n_stored; i += static_cast<int64_t>(gridDim.x) * TSDF_BLOCK)
+        vol[i] = make_float2(1.0f, 0.0f);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_integrate(TsdfGrid g, const TsdfCam* __restrict__ cam, const TsdfPose* __restrict__ poses,
+                                                               const double* __restrict__ depth, int n_maps, TsdfRule r, float* __restrict__ vol) {
+    const int64_t pair = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x;
+    const int half = g.pitch >> 1;
+    const int64_t row = pair / half;
+    if (row >= static_cast<int64_t>(g.ny) * g.nz) return;
+    const int i = 2 * static_cast<int>(pair - row * half), k = static_cast<int>(row / g.ny), j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+    float4* at = reinterpret_cast<float4*>(vol) + pair;  // rows are pitch / 2 words long: the pair's number is its word's
+    float4 q = *at;
+    const double xa = tsdf_coord(g.o[0], i, g.vs), xb = tsdf_coord(g.o[0], i + 1, g.vs);
+    const double y = tsdf_coord(g.o[1], j, g.vs), z = tsdf_coord(g.o[2], k, g.vs);
+    const bool second = i + 1 < g.nx;
+    const int64_t plane = static_cast<int64_t>(r.W) * r.H;
+    bool ca = false, cb = false;
+#pragma unroll 1
+    for (int m = 0; m < n_maps; ++m) {
+        const double* map = depth + m * plane;
+        ca |= tsdf_update<MODEL>(*cam, poses[m], map, r, xa, y, z, &q.x, &q.y);
+        if (second) cb |= tsdf_update<MODEL>(*cam, poses[m], map, r, xb, y, z, &q.z, &q.w);
+    }
+    if (ca && cb)
+        *at = q;
+    else if (ca)
+        *reinterpret_cast<float2*>(at) = make_float2(q.x, q.y);
+    else if (cb)
+        *(reinterpret_cast<float2*>(at) + 1) = make_float2(q.z, q.w);
+}
+
+// TO_DENSE: tsdf [n], weight [n] <- the volume; else the volume <- the planes.  Either plane may be NULL.
+template <bool TO_DENSE>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_planes(TsdfGrid g, float* __restrict__ vol, float* __restrict__ tsdf, float* __restrict__ weight) {
+    const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
+    for (int64_t l = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x; l < n; l += static_cast<int64_t>(gridDim.x) * TSDF_BLOCK) {
+        const int64_t row = l / g.nx;
+        float* v = vol + 2 * (row * g.pitch + (l - row * g.nx));
+        if (TO_DENSE) {
+            if (tsdf) tsdf[l] = v[0];
+            if (weight) weight[l] = v[1];
+        } else {
+            if (tsdf) v[0] = tsdf[l];
+            if (weight) v[1] = weight[l];
+        }
+    }
+}
+
+// PLACE false: count [tile] <- the tile's qualifying edges.  PLACE true: count holds the scanned starts; xyz, nrm [n_points][3] written.
+template <bool PLACE>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const float* __restrict__ vol, double min_weight, int32_t* __restrict__ count,
+                                                             double* __restrict__ xyz, double* __restrict__ nrm) {
+    __shared__ int32_t wave_total[TSDF_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
+    int32_t base = PLACE ? count[blockIdx.x] : 0;
+#pragma unroll 1
+    for (int round = 0; round < TSDF_EXTRACT_TILE / TSDF_BLOCK; ++round) {
+        const int64_t l = static_cast<int64_t>(blockIdx.x) * TSDF_EXTRACT_TILE + round * TSDF_BLOCK + threadIdx.x;
+        int i = 0, j = 0, k = 0, mask = 0;
+        if (l < n) {
+            const int64_t row = l / g.nx;
+            i = static_cast<int>(l - row * g.nx);
+            k = static_cast<int>(row / g.ny);
+            j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+            mask = tsdf_edge_mask(vol, g, i, j, k, min_weight);
+        }
+        // every lane of the workgroup is here: the ballots and the barriers see all of them
+        const uint64_t b0 = __ballot(mask & 1), b1 = __ballot(mask & 2), b2 = __ballot(mask & 4);
+        const uint64_t below = (1ull << lane) - 1;
+        if (lane == 0) wave_total[wave] = __popcll(b0) + __popcll(b1) + __popcll(b2);
+        __syncthreads();
+        int32_t before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < TSDF_BLOCK / 64; ++w) {
+            const int32_t t = wave_total[w];
+            before += w < wave ? t : 0;
+            all += t;
+        }
+        __syncthreads();  // the next round writes wave_total again
+        if (PLACE && mask) {
+            int64_t at = base + before + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);
+#pragma unroll
+            for (int axis = 0; axis < 3; ++axis) {
+                double Da, Db;
+                if (!tsdf_edge(vol, g, i, j, k, axis, min_weight, &Da, &Db)) continue;
+                double pt[3], nn[3];
+                tsdf_edge_point(vol, g, i, j, k, axis, Da, Db, pt, nn);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    xyz[3 * at + c] = pt[c];
+                    nrm[3 * at + c] = nn[c];
+                }
+                ++at;
+            }
+        }
+        base += all;
+    }
+    if (!PLACE && threadIdx.x == 0) count[blockIdx.x] = base;
+}
+
+struct TsdfVolume : DeviceHandle {
+    using DeviceHandle::DeviceHandle;
+    TsdfGrid g{};
+    cba_tsdf_options o{};
+    int64_t n_voxels = 0, n_stored = 0, n_tiles = 0;
+    int64_t n_points = -1;     // of the last extract; -1: none yet
+    DevBuf<float> vol;         // [nz][ny][pitch][2]
+    DevBuf<float> planes;      // [2][n_voxels]: the staging of fetch and upload
+    DevBuf<TsdfCam> cam;
+    DevBuf<TsdfPose> poses;
+    DevBuf<double> depth;
+    DevBuf<int32_t> count, tmp;  // [n_tiles + 1] and the scan's levels
+    DevBuf<double> xyz, nrm;     // [n_points][3] of the last extract
+    PinnedBuf<int32_t> total_h;
+};
+static_assert(!std::is_copy_constructible_v<TsdfVolume> && !std::is_copy_assignable_v<TsdfVolume>, "a handle owns its stream and buffers");
+
+static void tsdf_fill(TsdfVolume* h, hipStream_t s) {
+    hipLaunchKernelGGL(k_tsdf_fill, dim3(launch_grid(h->n_stored, TSDF_BLOCK, TSDF_GRID)), dim3(TSDF_BLOCK), 0, s, h->n_stored,
+                       reinterpret_cast<float2*>(h->vol.p));
+    CBA_HIP(hipGetLastError());
+}
+
+TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, const cba_tsdf_options& o, int device) {
+    auto h = std::make_unique<TsdfVolume>(device);
+    const hipStream_t s = h->begin();
+    h->g.nx = nx; h->g.ny = ny; h->g.nz = nz; h->g.pitch = (nx + 1) & ~1;
+    for (int c = 0; c < 3; ++c) h->g.o[c] = origin[c];
+    h->g.vs = o.voxel_size;
+    h->o = o;
+    h->n_voxels = static_cast<int64_t>(nx) * ny * nz;
+    h->n_stored = static_cast<int64_t>(h->g.pitch) * ny * nz;
+    h->n_tiles = (h->n_voxels + TSDF_EXTRACT_TILE - 1) / TSDF_EXTRACT_TILE;
+    h->vol.alloc(2 * static_cast<size_t>(h->n_stored));
+    h->cam.alloc(1);
+    h->count.alloc(static_cast<size_t>(h->n_tiles) + 1);
+    h->tmp.alloc(scan_tmp_size(h->n_tiles + 1));
+    h->total_h.reserve(1);
+    tsdf_fill(h.get(), s);
+    CBA_HIP(hipStreamSynchronize(s));
+    return h.release();
+}
+
+void tsdf_volume_reset(TsdfVolume* h) {
+    const hipStream_t s = h->begin();
+    tsdf_fill(h, s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+int64_t tsdf_volume_points(const TsdfVolume* h) { return h->n_points; }
+
+// stage_ms [2] optional: upload, kernel
+void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
+                           double* stage_ms) {
+    const hipStream_t s = h->begin();
+    TsdfCam cam;
+    double intr12[12];
+    ls_fill_intr(model, intr, intr12, cam.sd);
+    for (int k = 0; k < 12; ++k) cam.intr[k] = intr12[k];
+    std::vector<TsdfPose> poses(static_cast<size_t>(n_maps));
+    for (int m = 0; m < n_maps; ++m) {
+        quat_to_rotmat(c_T_v + 7 * static_cast<size_t>(m), poses[m].R);
+        for (int c = 0; c < 3; ++c) poses[m].t[c] = c_T_v[7 * static_cast<size_t>(m) + 4 + c];
+    }
+    const size_t n_px = static_cast<size_t>(n_maps) * H * W;
+    StageTimer<3> tm(s, stage_ms != nullptr);
+    h->poses.ensure(static_cast<size_t>(n_maps));
+    h->depth.ensure(n_px);
+    tm.mark(0);
+    h->cam.upload(&cam, 1, s);
+    h->poses.upload(poses.data(), static_cast<size_t>(n_maps), s);
+    h->depth.upload(depth, n_px, s);
+    tm.mark(1);
+    TsdfRule r;
+    r.trunc = h->o.truncation; r.max_depth = h->o.max_depth; r.max_weight = h->o.max_weight; r.W = W; r.H = H;
+    const dim3 grid(static_cast<unsigned>((h->n_stored / 2 + TSDF_BLOCK - 1) / TSDF_BLOCK));
+    if (model == CAM_SCHEIMPFLUG)
+        hipLaunchKernelGGL(k_tsdf_integrate<CAM_SCHEIMPFLUG>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
+    else
+        hipLaunchKernelGGL(k_tsdf_integrate<CAM_PINHOLE_BC>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
+    CBA_HIP(hipGetLastError());
+    tm.mark(2);
+    CBA_HIP(hipStreamSynchronize(s));  // cam and poses go out of scope
+    tm.report(stage_ms);
+}
+
+static void tsdf_planes(TsdfVolume* h, hipStream_t s, bool to_dense, float* tsdf, float* weight) {
+    const dim3 grid(launch_grid(h->n_voxels, TSDF_BLOCK, TSDF_GRID));
+    if (to_dense)
+        hipLaunchKernelGGL(k_tsdf_planes<true>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, tsdf, weight);
+    else
+        hipLaunchKernelGGL(k_tsdf_planes<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, tsdf, weight);
+    CBA_HIP(hipGetLastError());
+}
+
+void tsdf_volume_fetch(TsdfVolume* h, float* tsdf, float* weight) {
+    const hipStream_t s = h->begin();
+    const size_t n = static_cast<size_t>(h->n_voxels);
+    h->planes.ensure(2 * n);
+    tsdf_planes(h, s, true, tsdf ? h->planes.p : nullptr, weight ? h->planes.p + n : nullptr);
+    if (tsdf) h->planes.download(tsdf, n, s);
+    if (weight) h->planes.download(weight, n, s, n);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight) {
+    const hipStream_t s = h->begin();
+    const size_t n = static_cast<size_t>(h->n_voxels);
+    h->planes.ensure(2 * n);
+    if (tsdf) h->planes.upload(tsdf, n, s);
+    if (weight) h->planes.upload(weight, n, s, n);
+    tsdf_planes(h, s, false, tsdf ? h->planes.p : nullptr, weight ? h->planes.p + n : nullptr);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+// stage_ms [2] optional: count and scan, place
+void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms) {
+    const hipStream_t s = h->begin();
+    StageTimer<3> tm(s, stage_ms != nullptr);
+    const dim3 grid(static_cast<unsigned>(h->n_tiles));
+    tm.mark(0);
+    CBA_HIP(hipMemsetAsync(h->count.p + h->n_tiles, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_tsdf_extract<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr);
+    scan_exclusive(s, h->count.p, h->n_tiles + 1, h->tmp.p);
+    CBA_HIP(hipGetLastError());
+    h->count.download(h->total_h.p, 1, s, static_cast<size_t>(h->n_tiles));
+    CBA_HIP(hipStreamSynchronize(s));
+    const int64_t total = h->total_h.p[0];
+    tm.mark(1);
+    h->n_points = -1;
+    if (total > 0) {
+        h->xyz.ensure(3 * static_cast<size_t>(total));
+        h->nrm.ensure(3 * static_cast<size_t>(total));
+        hipLaunchKernelGGL(k_tsdf_extract<true>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p);
+        CBA_HIP(hipGetLastError());
+    }
+    tm.mark(2);
+    CBA_HIP(hipStreamSynchronize(s));
+    h->n_points = total;
+    *n_points = total;
+    tm.report(stage_ms);
+}
+
+void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals) {
+    const hipStream_t s = h->begin();
+    const size_t n = 3 * static_cast<size_t>(h->n_points);
+    h->xyz.download(xyz, n, s);
+    if (normals) h->nrm.download(normals, n, s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+void tsdf_volume_destroy(TsdfVolume* h) noexcept { destroy_handle(h); }
+
+}  // namespace cba

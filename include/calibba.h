@@ -1125,6 +1125,72 @@ cba_status cba_cloud_register(cba_cloud_index* h, int32_t n_sources, const int64
                               const cba_icp_options* opts, cba_icp_result* results /*[n_sources]*/);
 void cba_cloud_index_destroy(cba_cloud_index* h);
 
+/* ---- scan fusion: a truncated signed distance volume from depth maps, surface points (no counterpart in the reference) ---------
+ *
+ * What comes after registration: the views of one object, each with its pose, are merged into one surface.  Storage is float32;
+ * every decision and every arithmetic step is fp64, rounded once on store; no product or sum named below is contracted into an
+ * FMA, so a restatement in IEEE operations can be held to the bit.
+ *
+ * 1. The volume: nx, ny, nz, each in [2, 1024], nx ny nz <= CBA_TSDF_MAX_VOXELS.  Lattice point (i, j, k) lies at
+ *    X = (ox + i vs, oy + j vs, oz + k vs) with origin o and vs = voxel_size: the product rounded, then the sum.  A voxel holds D
+ *    (float32, starts at 1) and W (float32, starts at 0).  The linear order is x fastest: l = (k ny + j) nx + i.
+ *
+ * 2. cba_tsdf_integrate: one camera (camera_model and intr [10 | 12] as cba_camera_project takes them), n_maps depth maps
+ *    depth [n_maps][height][width], fp64, holding z in the camera frame (a value that is non-finite or <= 0 is invalid), and
+ *    c_T_v [n_maps][7], pose7 rows = [qw qx qy qz tx ty tz] that map the volume frame to the camera; R of a row is built as
+ *    cba_triangulate builds it (the quaternion as it is, no normalisation).  Maps are applied in order m = 0, 1, ...; each voxel goes
+ *    through these steps for each map:
+ *      1. P_r = ((R_r0 X_0 + R_r1 X_1) + R_r2 X_2) + t_r.
+ *      2. Skip unless P_2 > 0 and the model's denominator is > 0 (P_2 for the pinhole, n_sensor . P for Scheimpflug).
+ *      3. (u, v) by cba_camera_project's arithmetic; px = floor(u + 0.5), py = floor(v + 0.5), in fp64.  Skip unless
+ *         0 <= px <= width - 1 and 0 <= py <= height - 1 (comparisons that are false for NaN).
+ *      4. d = depth[m][py][px].  Skip unless d is finite, d > 0 and d <= max_depth.
+ *      5. s = d - P_2.  Skip when s < -truncation.  f = s / truncation, and f = 1 when f > 1.
+ *      6. D <- float32((double(W) double(D) + f) / (double(W) + 1)); W <- float32(min(double(W) + 1, max_weight)).
+ *    A voxel's result depends only on its own position and the maps, taken in order: not on the batch (one call with seven maps
+ *    gives the bits of seven calls with one map each), not on how the device splits the work, not on the other voxels.
+ *
+ * 3. cba_tsdf_extract(h, min_weight, &n_points): the zero crossings on lattice edges.  Voxels are visited in ascending l; at each
+ *    voxel the +x, +y and +z edges in that order; an edge is absent on the grid's last plane along its axis.  With a the voxel and
+ *    b the neighbour at the other end: the edge qualifies when W_a >= min_weight, W_b >= min_weight and (D_a < 0) != (D_b < 0)
+ *    (so -0.0 counts as non-negative).  t = D_a / (D_a - D_b) in fp64; the point is X_a with t vs (the product rounded) added along
+ *    the axis.  The normal: for v in {a, b}, g_c(v) = D(v + e_c) - D(v - e_c) for c = x, y, z, where every neighbour used must be
+ *    inside the grid and have W > 0; n_c = g_c(a) + t (g_c(b) - g_c(a)); len = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2); n / len by three
+ *    divisions.  There is no normal (NaN in all three components, the point is kept) when a neighbour is missing or len is zero or
+ *    non-finite.  D is positive in observed free space, so the normal points from the surface into it: the side cba_point_normals
+ *    orients towards.  The output order is the visiting order.  The points and normals stay on the device until
+ *    cba_tsdf_extract_fetch(h, xyz [n_points][3], normals [n_points][3] or NULL) copies those of the last extract out.
+ *
+ * cba_tsdf_fetch copies the dense [nz][ny][nx] planes of D and W out and cba_tsdf_upload writes them (a saved volume restored; the
+ * values are taken as they are); either pointer may be NULL.  cba_tsdf_reset restores D = 1 and W = 0.  The handle owns one stream
+ * and all of its device buffers; every call ends synchronised.  Float atomics are used nowhere.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all before any device work): NULL origin, opts, out, handle, intr, n_points, depth or c_T_v for
+ * n_maps > 0, xyz for n_points > 0; a side outside [2, 1024] or nx ny nz > CBA_TSDF_MAX_VOXELS; voxel_size, truncation or origin not
+ * finite, voxel_size or truncation not > 0; max_weight outside [1, 2^24] or not an integer value; max_depth not > 0; an unknown
+ * camera model, fx or fy equal to 0; n_maps < 0; width or height outside [1, CBA_IMAGE_MAX_SIDE]; a zero or non-finite quaternion;
+ * min_weight not >= 1; cba_tsdf_extract_fetch before any extract.  n_maps == 0 is no work; create without a device ->
+ * CBA_ERR_NO_DEVICE. */
+#define CBA_TSDF_MAX_VOXELS (1 << 28)
+typedef struct cba_tsdf_options {
+    double voxel_size; /* lattice spacing (no default: the caller sets it) */
+    double truncation; /* the band, in the volume's unit (no default: the caller sets it; a few voxel sizes) */
+    double max_weight; /* an integer value in [1, 2^24] (default 64) */
+    double max_depth;  /* depths beyond it are not used (default +inf) */
+} cba_tsdf_options;
+void cba_tsdf_options_default(cba_tsdf_options* o); /* voxel_size and truncation are left at 0: the caller sets them */
+typedef struct cba_tsdf_volume cba_tsdf_volume; /* opaque: the volume, the buffers of its calls, the last extract's points, one stream */
+cba_status cba_tsdf_volume_create(int32_t nx, int32_t ny, int32_t nz, const double* origin /*[3]*/, const cba_tsdf_options* opts,
+                                  int32_t device, cba_tsdf_volume** out);
+cba_status cba_tsdf_integrate(cba_tsdf_volume* h, int32_t camera_model, const double* intr /*[10 | 12]*/, int32_t n_maps, int32_t height,
+                              int32_t width, const double* depth /*[n_maps][height][width]*/, const double* c_T_v /*[n_maps][7]*/);
+cba_status cba_tsdf_fetch(cba_tsdf_volume* h, float* tsdf /*[nz][ny][nx] or NULL*/, float* weight /*[nz][ny][nx] or NULL*/);
+cba_status cba_tsdf_upload(cba_tsdf_volume* h, const float* tsdf /*[nz][ny][nx] or NULL*/, const float* weight /*[nz][ny][nx] or NULL*/);
+cba_status cba_tsdf_reset(cba_tsdf_volume* h);
+cba_status cba_tsdf_extract(cba_tsdf_volume* h, double min_weight, int64_t* n_points);
+cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz /*[n_points][3]*/, double* normals /*[n_points][3] or NULL*/);
+void cba_tsdf_volume_destroy(cba_tsdf_volume* h);
+
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
  *
  * What a calibrated two-camera rig is used for: calibrated pair -> rectified pair -> dense disparity -> 3D points.
