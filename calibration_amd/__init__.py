@@ -134,10 +134,13 @@ from .registration import (  # noqa: F401
     register,
 )
 from .fusion import (  # noqa: F401
+    Mesh,
     TsdfOptions,
     TsdfVolume,
     depth_from_xyz,
     fuse,
+    read_ply,
+    write_ply,
 )
 from .structured_light import (  # noqa: F401
     Decoded,

@@ -543,6 +543,8 @@ PROTOTYPES = {
     "cba_tsdf_reset": (C.c_int32, [C.c_void_p]),
     "cba_tsdf_extract": (C.c_int32, [C.c_void_p, C.c_double, c_int64_p]),
     "cba_tsdf_extract_fetch": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
+    "cba_tsdf_mesh": (C.c_int32, [C.c_void_p, C.c_double, c_int64_p, c_int64_p]),
+    "cba_tsdf_mesh_fetch": (C.c_int32, [C.c_void_p, c_int32_p]),
     "cba_tsdf_volume_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (

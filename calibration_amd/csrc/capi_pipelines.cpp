@@ -1160,6 +1160,29 @@ cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz, double* norma
     });
 }
 
+static cba_status tsdf_mesh_impl(cba_tsdf_volume* h, double min_weight, int64_t* n_points, int64_t* n_triangles, double* stage_ms) {
+    return guarded([&] {
+        if (!h || !n_points || !n_triangles) throw std::invalid_argument("null argument");
+        if (!(min_weight >= 1.0)) throw std::invalid_argument("min_weight must be >= 1");
+        tsdf_volume_mesh(reinterpret_cast<TsdfVolume*>(h), min_weight, n_points, n_triangles, stage_ms);
+    });
+}
+
+cba_status cba_tsdf_mesh(cba_tsdf_volume* h, double min_weight, int64_t* n_points, int64_t* n_triangles) {
+    return tsdf_mesh_impl(h, min_weight, n_points, n_triangles, nullptr);
+}
+
+cba_status cba_tsdf_mesh_fetch(cba_tsdf_volume* h, int32_t* triangles) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (tsdf_volume_triangles(v) < 0) throw std::invalid_argument("this volume has no valid mesh: call cba_tsdf_mesh");
+        if (tsdf_volume_triangles(v) == 0) return;
+        if (!triangles) throw std::invalid_argument("null argument");
+        tsdf_volume_mesh_fetch(v, triangles);
+    });
+}
+
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h) { tsdf_volume_destroy(reinterpret_cast<TsdfVolume*>(h)); }
 
 #ifdef CBA_EXPERIMENTS
@@ -1173,6 +1196,11 @@ __attribute__((visibility("default"))) cba_status cba_tsdf_integrate_timed(cba_t
 __attribute__((visibility("default"))) cba_status cba_tsdf_extract_timed(cba_tsdf_volume* h, double min_weight, int64_t* n_points,
                                                                          double* stage_ms) {
     return timed(stage_ms, [&] { return tsdf_extract_impl(h, min_weight, n_points, stage_ms); });
+}
+// stage_ms [4] = the extract's count and scan, its place with the records, the triangles' count and scan, their place
+__attribute__((visibility("default"))) cba_status cba_tsdf_mesh_timed(cba_tsdf_volume* h, double min_weight, int64_t* n_points,
+                                                                      int64_t* n_triangles, double* stage_ms) {
+    return timed(stage_ms, [&] { return tsdf_mesh_impl(h, min_weight, n_points, n_triangles, stage_ms); });
 }
 #endif
 

@@ -123,7 +123,8 @@ void cloud_index_register(CloudIndex* h, int n_sources, const int64_t* source_of
                           cba_icp_result* results, double* stage_ms);
 void cloud_index_destroy(CloudIndex* h) noexcept;
 // tsdf_fusion.hip: the cba_tsdf_volume handle (checked by the caller).  integrate: stage_ms [2] optional: upload, kernel; extract:
-// stage_ms [2] optional: count and scan, place.  points: the count of the last extract, -1 before the first
+// stage_ms [2] optional: count and scan, place; mesh: stage_ms [4] optional: the extract's two, the triangles' count and scan, their
+// place.  points: the count of the last extract, -1 before the first; triangles: of the handle's mesh, -1 when there is none
 struct TsdfVolume;
 TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, const cba_tsdf_options& o, int device);
 int64_t tsdf_volume_points(const TsdfVolume* h);
@@ -134,6 +135,9 @@ void tsdf_volume_fetch(TsdfVolume* h, float* tsdf, float* weight);
 void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight);
 void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms);
 void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals);
+int64_t tsdf_volume_triangles(const TsdfVolume* h);
+void tsdf_volume_mesh(TsdfVolume* h, double min_weight, int64_t* n_points, int64_t* n_triangles, double* stage_ms);
+void tsdf_volume_mesh_fetch(TsdfVolume* h, int32_t* triangles);
 void tsdf_volume_destroy(TsdfVolume* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download

@@ -1,4 +1,5 @@
-// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, calibba.h: cba_tsdf_volume, cba_tsdf_integrate, cba_tsdf_extract).
+// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, tsdf_mesh_math.hpp, calibba.h: cba_tsdf_volume, cba_tsdf_integrate,
+// cba_tsdf_extract, cba_tsdf_mesh).
 //   k_tsdf_fill         D = 1, W = 0 in every stored voxel (create, reset).
 //   k_tsdf_integrate    one launch per call.  A lane owns two adjacent x voxels, one aligned 16-byte {D, W, D, W} word that it loads
 //                       once, keeps in registers while it walks the call's maps in order, and stores once: the whole word when both
@@ -12,6 +13,13 @@
 //   k_scan_tiles / k_scan_add   (scan_tiles.hpp) the exclusive scan of the tile counts; one extra entry receives the total.
 //   k_tsdf_extract<1>   the same walk again: an edge's place is its tile's start, the rounds and waves before it, and the popcount of
 //                       the ballots below its lane, so the order is the visiting order whatever the arrival order; tsdf_edge_point.
+//   k_tsdf_extract<1,1> the place pass of cba_tsdf_mesh: it also writes, per wave and round, the record {first place, three ballots} of
+//                       its 64 voxels (tsdf_mesh_math.hpp: TsdfEdgeGroup), from which an edge's place follows by popcounts.
+//   k_tsdf_mesh<0/1>    the same tiles: a lane owns the cell at its voxel.  It loads the {D, W} words of its voxel in the four rows
+//                       (j, k) .. (j + 1, k + 1), forms sign and weight bits and takes the +x neighbour's from the next lane (the last lane
+//                       of a wave loads its own): four 8-byte loads per cell.  The table of triangles per case (2 KiB, generated from
+//                       the rule at compile time) is staged in LDS.  Ballots of the three bits of a lane's triangle count give the
+//                       wave's prefix; count, scan and place as above.  A triangle is three lookups in the records.
 // The handle owns one stream and every buffer; a call grows a buffer that is too small and allocates nothing else; every call ends
 // with the stream synchronised.  No float atomics, and no integer ones either.
 #include <memory>
@@ -21,12 +29,15 @@
 #include "pipelines.hpp"
 #include "scan_tiles.hpp"
 #include "tsdf_math.hpp"
+#include "tsdf_mesh_math.hpp"
 
 namespace cba {
 
 constexpr int TSDF_BLOCK = 256;
 constexpr int TSDF_GRID = 8192;  // grid-stride cap of the fill and plane kernels
 static_assert(TSDF_EXTRACT_TILE == 4 * TSDF_BLOCK, "k_tsdf_extract walks a tile in four rounds");
+static_assert(TSDF_BLOCK == 256, "k_tsdf_mesh stages one table word per lane");
+static_assert(TSDF_MESH_GROUP == 64 && TSDF_EXTRACT_TILE % TSDF_MESH_GROUP == 0, "a record is one wave of one round of k_tsdf_extract");
 
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_fill(int64_t n_stored, float2* __restrict__ vol) {
     for (int64_t i = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x; i < n_stored; i += static_cast<int64_t>(gridDim.x) * TSDF_BLOCK)
@@ -80,9 +91,10 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_planes(TsdfGrid g, float* _
 }
 
 // PLACE false: count [tile] <- the tile's qualifying edges.  PLACE true: count holds the scanned starts; xyz, nrm [n_points][3] written.
-template <bool PLACE>
+// RECORD (with PLACE): rec [tiles * TSDF_EXTRACT_TILE / 64] written, one per wave and round.
+template <bool PLACE, bool RECORD = false>
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const float* __restrict__ vol, double min_weight, int32_t* __restrict__ count,
-                                                             double* __restrict__ xyz, double* __restrict__ nrm) {
+                                                             double* __restrict__ xyz, double* __restrict__ nrm, TsdfEdgeGroup* __restrict__ rec) {
     __shared__ int32_t wave_total[TSDF_BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
@@ -111,6 +123,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const f
             all += t;
         }
         __syncthreads();  // the next round writes wave_total again
+        if (RECORD && lane == 0) {  // l is a multiple of 64 here
+            TsdfEdgeGroup r;
+            r.ballot[0] = b0; r.ballot[1] = b1; r.ballot[2] = b2;
+            r.start = base + before;
+            r.pad = 0;
+            rec[l / TSDF_MESH_GROUP] = r;
+        }
         if (PLACE && mask) {
             int64_t at = base + before + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);
 #pragma unroll
@@ -132,12 +151,75 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const f
     if (!PLACE && threadIdx.x == 0) count[blockIdx.x] = base;
 }
 
+__constant__ TsdfMeshTable d_tsdf_mesh_table = TSDF_MESH_TABLE;
+
+// PLACE false: count [tile] <- the triangles of the tile's cells.  PLACE true: count holds the scanned starts; tri [n_triangles][3]
+// written from the records of the extract at the same min_weight.
+template <bool PLACE>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_mesh(TsdfGrid g, const float* __restrict__ vol, double min_weight,
+                                                          const TsdfEdgeGroup* __restrict__ rec, int32_t* __restrict__ count, int32_t* __restrict__ tri) {
+    __shared__ uint64_t table[256];
+    __shared__ int32_t wave_total[TSDF_BLOCK / 64];
+    table[threadIdx.x] = d_tsdf_mesh_table.w[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
+    int32_t base = PLACE ? count[blockIdx.x] : 0;
+#pragma unroll 1
+    for (int round = 0; round < TSDF_EXTRACT_TILE / TSDF_BLOCK; ++round) {
+        const int64_t l = static_cast<int64_t>(blockIdx.x) * TSDF_EXTRACT_TILE + round * TSDF_BLOCK + threadIdx.x;
+        int i = 0, j = 0, k = 0, own = 0;
+        bool rows = false;
+        if (l < n) {
+            const int64_t row = l / g.nx;
+            i = static_cast<int>(l - row * g.nx);
+            k = static_cast<int>(row / g.ny);
+            j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+            rows = tsdf_mesh_has_rows(g, j, k);
+            if (rows) own = tsdf_mesh_rows(vol, g, i, j, k, min_weight);
+        }
+        // every lane of the workgroup is here: the shuffle, the ballots and the barriers see all of them.  A cell's +x neighbour is the
+        // next voxel of its row, so the next lane holds it, and has loaded it: it shares j and k.
+        int next = __shfl_down(own, 1);
+        const bool cell = rows && i + 1 < g.nx;
+        if (cell && lane == 63) next = tsdf_mesh_rows(vol, g, i + 1, j, k, min_weight);
+        uint64_t word = 0;
+        if (cell && tsdf_mesh_live(own, next)) word = table[tsdf_mesh_case(own, next)];
+        const int mine = tsdf_mesh_word_count(word);  // 0 .. 5: three bits
+        const uint64_t c0 = __ballot(mine & 1), c1 = __ballot(mine & 2), c2 = __ballot(mine & 4);
+        const uint64_t below = (1ull << lane) - 1;
+        if (lane == 0) wave_total[wave] = __popcll(c0) + 2 * __popcll(c1) + 4 * __popcll(c2);
+        __syncthreads();
+        int32_t before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < TSDF_BLOCK / 64; ++w) {
+            const int32_t t = wave_total[w];
+            before += w < wave ? t : 0;
+            all += t;
+        }
+        __syncthreads();  // the next round writes wave_total again
+        if (PLACE && mine) {
+            int64_t at = base + before + __popcll(c0 & below) + 2 * __popcll(c1 & below) + 4 * __popcll(c2 & below);
+#pragma unroll 1
+            for (int t = 0; t < mine; ++t, ++at)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int e = tsdf_mesh_word_edge(word, 3 * t + c);
+                    tri[3 * at + c] = tsdf_mesh_edge_index(rec, tsdf_mesh_edge_voxel(g, i, j, k, e), e >> 2);
+                }
+        }
+        base += all;
+    }
+    if (!PLACE && threadIdx.x == 0) count[blockIdx.x] = base;
+}
+
 struct TsdfVolume : DeviceHandle {
     using DeviceHandle::DeviceHandle;
     TsdfGrid g{};
     cba_tsdf_options o{};
     int64_t n_voxels = 0, n_stored = 0, n_tiles = 0;
     int64_t n_points = -1;     // of the last extract; -1: none yet
+    int64_t n_triangles = -1;  // of the handle's mesh; -1: there is none (no mesh call yet, or a later call made it stale)
     DevBuf<float> vol;         // [nz][ny][pitch][2]
     DevBuf<float> planes;      // [2][n_voxels]: the staging of fetch and upload
     DevBuf<TsdfCam> cam;
@@ -145,6 +227,9 @@ struct TsdfVolume : DeviceHandle {
     DevBuf<double> depth;
     DevBuf<int32_t> count, tmp;  // [n_tiles + 1] and the scan's levels
     DevBuf<double> xyz, nrm;     // [n_points][3] of the last extract
+    DevBuf<TsdfEdgeGroup> rec;   // [n_tiles * TSDF_EXTRACT_TILE / 64], from the first mesh call on
+    DevBuf<int32_t> tcount;      // [n_tiles + 1] triangles per tile, from the first mesh call on
+    DevBuf<int32_t> tri;         // [n_triangles][3] of the mesh
     PinnedBuf<int32_t> total_h;
 };
 static_assert(!std::is_copy_constructible_v<TsdfVolume> && !std::is_copy_assignable_v<TsdfVolume>, "a handle owns its stream and buffers");
@@ -177,16 +262,19 @@ TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, con
 
 void tsdf_volume_reset(TsdfVolume* h) {
     const hipStream_t s = h->begin();
+    h->n_triangles = -1;
     tsdf_fill(h, s);
     CBA_HIP(hipStreamSynchronize(s));
 }
 
 int64_t tsdf_volume_points(const TsdfVolume* h) { return h->n_points; }
+int64_t tsdf_volume_triangles(const TsdfVolume* h) { return h->n_triangles; }
 
 // stage_ms [2] optional: upload, kernel
 void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
                            double* stage_ms) {
     const hipStream_t s = h->begin();
+    h->n_triangles = -1;
     TsdfCam cam;
     double intr12[12];
     ls_fill_intr(model, intr, intr12, cam.sd);
@@ -239,6 +327,7 @@ void tsdf_volume_fetch(TsdfVolume* h, float* tsdf, float* weight) {
 
 void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight) {
     const hipStream_t s = h->begin();
+    h->n_triangles = -1;
     const size_t n = static_cast<size_t>(h->n_voxels);
     h->planes.ensure(2 * n);
     if (tsdf) h->planes.upload(tsdf, n, s);
@@ -247,14 +336,13 @@ void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight) {
     CBA_HIP(hipStreamSynchronize(s));
 }
 
-// stage_ms [2] optional: count and scan, place
-void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms) {
-    const hipStream_t s = h->begin();
-    StageTimer<3> tm(s, stage_ms != nullptr);
+// The extract on s, ending synchronised; tm marks 0, 1, 2 around count and scan, and place.  record: the place pass also writes h->rec.
+template <class Timer>
+static int64_t tsdf_extract_run(TsdfVolume* h, hipStream_t s, double min_weight, bool record, Timer& tm) {
     const dim3 grid(static_cast<unsigned>(h->n_tiles));
     tm.mark(0);
     CBA_HIP(hipMemsetAsync(h->count.p + h->n_tiles, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_tsdf_extract<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr);
+    hipLaunchKernelGGL((k_tsdf_extract<false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr, nullptr);
     scan_exclusive(s, h->count.p, h->n_tiles + 1, h->tmp.p);
     CBA_HIP(hipGetLastError());
     h->count.download(h->total_h.p, 1, s, static_cast<size_t>(h->n_tiles));
@@ -265,14 +353,66 @@ void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, do
     if (total > 0) {
         h->xyz.ensure(3 * static_cast<size_t>(total));
         h->nrm.ensure(3 * static_cast<size_t>(total));
-        hipLaunchKernelGGL(k_tsdf_extract<true>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p);
+        if (record)
+            hipLaunchKernelGGL((k_tsdf_extract<true, true>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p,
+                               h->rec.p);
+        else
+            hipLaunchKernelGGL((k_tsdf_extract<true>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p,
+                               nullptr);
         CBA_HIP(hipGetLastError());
     }
     tm.mark(2);
     CBA_HIP(hipStreamSynchronize(s));
     h->n_points = total;
-    *n_points = total;
+    return total;
+}
+
+// stage_ms [2] optional: count and scan, place
+void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms) {
+    const hipStream_t s = h->begin();
+    h->n_triangles = -1;
+    StageTimer<3> tm(s, stage_ms != nullptr);
+    *n_points = tsdf_extract_run(h, s, min_weight, false, tm);
     tm.report(stage_ms);
+}
+
+// stage_ms [4] optional: the extract's count and scan, its place with the records, the triangles' count and scan, their place
+void tsdf_volume_mesh(TsdfVolume* h, double min_weight, int64_t* n_points, int64_t* n_triangles, double* stage_ms) {
+    const hipStream_t s = h->begin();
+    h->n_triangles = -1;
+    StageTimer<5> tm(s, stage_ms != nullptr);
+    h->rec.ensure(static_cast<size_t>(h->n_tiles) * (TSDF_EXTRACT_TILE / TSDF_MESH_GROUP));
+    h->tcount.ensure(static_cast<size_t>(h->n_tiles) + 1);
+    const int64_t points = tsdf_extract_run(h, s, min_weight, true, tm);
+    int64_t total = 0;
+    if (points > 0) {  // a triangle needs three points, and only then were the records written
+        const dim3 grid(static_cast<unsigned>(h->n_tiles));
+        CBA_HIP(hipMemsetAsync(h->tcount.p + h->n_tiles, 0, sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_tsdf_mesh<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->rec.p, h->tcount.p, nullptr);
+        scan_exclusive(s, h->tcount.p, h->n_tiles + 1, h->tmp.p);
+        CBA_HIP(hipGetLastError());
+        h->tcount.download(h->total_h.p, 1, s, static_cast<size_t>(h->n_tiles));
+        CBA_HIP(hipStreamSynchronize(s));
+        total = h->total_h.p[0];
+        tm.mark(3);
+        if (total > 0) {
+            h->tri.ensure(3 * static_cast<size_t>(total));
+            hipLaunchKernelGGL(k_tsdf_mesh<true>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->rec.p, h->tcount.p, h->tri.p);
+            CBA_HIP(hipGetLastError());
+        }
+        tm.mark(4);
+        CBA_HIP(hipStreamSynchronize(s));
+    }
+    h->n_triangles = total;
+    *n_points = points;
+    *n_triangles = total;
+    tm.report(stage_ms);
+}
+
+void tsdf_volume_mesh_fetch(TsdfVolume* h, int32_t* triangles) {
+    const hipStream_t s = h->begin();
+    h->tri.download(triangles, 3 * static_cast<size_t>(h->n_triangles), s);
+    CBA_HIP(hipStreamSynchronize(s));
 }
 
 void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals) {

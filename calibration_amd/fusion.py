@@ -1,17 +1,18 @@
-"""Scan fusion on the GPU (``cba_tsdf_volume``, ``cba_tsdf_integrate``, ``cba_tsdf_extract``): depth maps of one object, each with
-its pose, are merged into a truncated signed distance volume, and the surface is read off it as points with normals on the lattice
-edges, by the rules calibba.h states.  The reference has no counterpart.
+"""Scan fusion on the GPU (``cba_tsdf_volume``, ``cba_tsdf_integrate``, ``cba_tsdf_extract``, ``cba_tsdf_mesh``): depth maps of one
+object, each with its pose, are merged into a truncated signed distance volume, and the surface is read off it as points with normals
+on the lattice edges, and as triangles over those points, by the rules calibba.h states.  The reference has no counterpart.  The mesh
+statistics and the PLY files are host work in numpy.
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
 from . import capi
-from .capi import CbaTsdfOptions, dptr, i64ptr
+from .capi import CbaTsdfOptions, dptr, i32ptr, i64ptr
 
 
 def _fptr(a: Optional[np.ndarray]):
@@ -41,6 +42,109 @@ def depth_from_xyz(xyz) -> np.ndarray:
     if p.ndim < 3 or p.shape[-1] != 3:
         raise ValueError(f"xyz must be [height][width][3] or [n_maps][height][width][3], got {p.shape}")
     return np.where(np.isfinite(p).all(axis=-1), p[..., 2], np.nan)
+
+
+@dataclass
+class Mesh:
+    """Indexed triangles over surface points: xyz [n][3], normals [n][3] (NaN where a point has none), triangles int32 [m][3].
+    (p1 - p0) x (p2 - p0) of a triangle points into positive D: out of the scanned object."""
+    xyz: np.ndarray
+    normals: np.ndarray
+    triangles: np.ndarray
+
+    def _corners(self) -> np.ndarray:
+        return self.xyz[self.triangles.astype(np.int64)]
+
+    def area(self) -> float:
+        p = self._corners()
+        return float(0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1).sum())
+
+    def volume(self) -> float:
+        """The volume the surface encloses, by the divergence theorem (the sum of p0 . (p1 x p2) / 6): meaningful for a closed mesh."""
+        p = self._corners()
+        return float(np.einsum("ij,ij->i", p[:, 0], np.cross(p[:, 1], p[:, 2])).sum() / 6.0)
+
+    def boundary_edges(self) -> np.ndarray:
+        """The directed edges u -> v [n][2] that occur more often than their reverse v -> u, each once per surplus occurrence, sorted:
+        empty for a closed oriented mesh."""
+        t = self.triangles.astype(np.int64)
+        h = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]])
+        if len(h) == 0:
+            return np.zeros((0, 2), np.int64)
+        both = np.concatenate([h, h[:, ::-1]])
+        sign = np.concatenate([np.ones(len(h), np.int64), -np.ones(len(h), np.int64)])
+        uniq, inv = np.unique(both, axis=0, return_inverse=True)
+        net = np.bincount(inv.ravel(), weights=sign, minlength=len(uniq)).astype(np.int64)
+        return np.repeat(uniq, np.maximum(net, 0), axis=0)
+
+    def compact(self) -> "Mesh":
+        """Without the points no triangle refers to, renumbered, in the same order."""
+        used = np.zeros(len(self.xyz), bool)
+        used[self.triangles.ravel()] = True
+        new = (np.cumsum(used) - 1).astype(np.int32)
+        return Mesh(self.xyz[used], self.normals[used], new[self.triangles.astype(np.int64)].reshape(-1, 3))
+
+
+_PLY_XYZ = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+_PLY_NORMAL = [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+_PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def write_ply(path, mesh: Mesh, normals: Optional[bool] = None) -> None:
+    """A binary little-endian PLY file: vertices as float64 x y z, then nx ny nz when ``normals`` is True or, by default, when every
+    normal is finite; faces as ``list uchar int``."""
+    if normals is None:
+        normals = bool(np.isfinite(mesh.normals).all())
+    fields = _PLY_XYZ + (_PLY_NORMAL if normals else [])
+    v = np.empty(len(mesh.xyz), np.dtype(fields))
+    for c, (name, _) in enumerate(_PLY_XYZ):
+        v[name] = mesh.xyz[:, c]
+    if normals:
+        for c, (name, _) in enumerate(_PLY_NORMAL):
+            v[name] = mesh.normals[:, c]
+    f = np.empty(len(mesh.triangles), _PLY_FACE)
+    f["n"], f["v"] = 3, mesh.triangles
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    head += [f"property double {name}" for name, _ in fields]
+    head += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def read_ply(path) -> Mesh:
+    """What ``write_ply`` wrote, and only that dialect; normals are NaN when the file has none."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    if head[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError("not a binary little-endian PLY file")
+    names, n_vertex, n_face = [], None, None
+    for line in head[2:]:
+        w = line.split()
+        if w[:2] == ["element", "vertex"]:
+            n_vertex = int(w[2])
+        elif w[:2] == ["element", "face"]:
+            n_face = int(w[2])
+        elif w[:2] == ["property", "double"] and n_face is None:
+            names.append(w[2])
+        elif w and w != ["end_header"] and w != ["property", "list", "uchar", "int", "vertex_indices"]:
+            raise ValueError(f"not the dialect write_ply writes: {line!r}")
+    with_normals = names == [n for n, _ in _PLY_XYZ + _PLY_NORMAL]
+    if n_vertex is None or n_face is None or not (with_normals or names == [n for n, _ in _PLY_XYZ]):
+        raise ValueError("not the dialect write_ply writes")
+    vt = np.dtype(_PLY_XYZ + (_PLY_NORMAL if with_normals else []))
+    if len(data) != end + n_vertex * vt.itemsize + n_face * _PLY_FACE.itemsize:
+        raise ValueError("the file's length does not match its header")
+    v = np.frombuffer(data, vt, n_vertex, end)
+    f = np.frombuffer(data, _PLY_FACE, n_face, end + n_vertex * vt.itemsize)
+    if not (f["n"] == 3).all():
+        raise ValueError("a face is not a triangle")
+    xyz = np.stack([v[n] for n, _ in _PLY_XYZ], axis=1) if n_vertex else np.zeros((0, 3))
+    nrm = np.stack([v[n] for n, _ in _PLY_NORMAL], axis=1) if with_normals and n_vertex else np.full((n_vertex, 3), np.nan)
+    return Mesh(np.ascontiguousarray(xyz), np.ascontiguousarray(nrm), np.ascontiguousarray(f["v"]).reshape(-1, 3))
 
 
 class TsdfVolume(capi.Handle):
@@ -107,12 +211,25 @@ class TsdfVolume(capi.Handle):
         capi.check(self._lib, self._lib.cba_tsdf_extract_fetch(h, dptr(xyz), dptr(normals)))
         return xyz, normals
 
+    def mesh(self, min_weight: float = 1.0, compact: bool = False) -> Mesh:
+        """The surface as triangles over the points ``extract(min_weight)`` gives: a cell of eight voxels that all have W >= min_weight
+        is cut by the rule calibba.h states.  Points that no such cell touches stay in the list unreferenced; ``compact`` drops them."""
+        h = self._require_open("the volume is closed")
+        n, m = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        capi.check(self._lib, self._lib.cba_tsdf_mesh(h, float(min_weight), i64ptr(n), i64ptr(m)))
+        xyz, normals, tri = np.empty((int(n[0]), 3)), np.empty((int(n[0]), 3)), np.empty((int(m[0]), 3), np.int32)
+        capi.check(self._lib, self._lib.cba_tsdf_extract_fetch(h, dptr(xyz), dptr(normals)))
+        capi.check(self._lib, self._lib.cba_tsdf_mesh_fetch(h, i32ptr(tri)))
+        out = Mesh(xyz, normals, tri)
+        return out.compact() if compact else out
+
     def reset(self) -> None:
         capi.check(self._lib, self._lib.cba_tsdf_reset(self._require_open("the volume is closed")))
 
 
-def fuse(shape, origin, opts: TsdfOptions, camera_model: int, intr, poses, depth=None, xyz=None, min_weight: float = 1.0, device: int = 0):
-    """One volume, one integrate, one extract: -> (xyz [n][3], normals [n][3])"""
+def fuse(shape, origin, opts: TsdfOptions, camera_model: int, intr, poses, depth=None, xyz=None, min_weight: float = 1.0, device: int = 0,
+         mesh: bool = False) -> Union[Tuple[np.ndarray, np.ndarray], Mesh]:
+    """One volume, one integrate, one extract: -> (xyz [n][3], normals [n][3]); with ``mesh=True`` one mesh instead: -> Mesh"""
     with TsdfVolume(shape, origin, opts, device) as vol:
         vol.integrate(camera_model, intr, poses, depth=depth, xyz=xyz)
-        return vol.extract(min_weight)
+        return vol.mesh(min_weight) if mesh else vol.extract(min_weight)

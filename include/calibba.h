@@ -1161,6 +1161,54 @@ void cba_cloud_index_destroy(cba_cloud_index* h);
  *    orients towards.  The output order is the visiting order.  The points and normals stay on the device until
  *    cba_tsdf_extract_fetch(h, xyz [n_points][3], normals [n_points][3] or NULL) copies those of the last extract out.
  *
+ * 4. cba_tsdf_mesh(h, min_weight, &n_points, &n_triangles): rule 3's extract with min_weight, then triangles over its points.  The
+ *    vertices of the mesh are exactly the points of the extract, so the mesh is an index list: no second vertex set, no welding.
+ *    No table of cases is typed in anywhere: the triangles of a cell follow from the rule below, which a few lines of code evaluate
+ *    for all 256 sign patterns (tsdf_mesh_math.hpp does so at compile time).  Every output is an integer.
+ *
+ *    Cell.  Cell (i, j, k), 0 <= i < nx - 1, 0 <= j < ny - 1, 0 <= k < nz - 1, has corners q = dx + 2 dy + 4 dz at lattice point
+ *    (i + dx, j + dy, k + dz).  A cell is live when all eight corners have W >= min_weight; every sign-changing edge of a live cell
+ *    is therefore a point of rule 3's extract at the same min_weight.  case = sum_q (D_q < 0) 2^q: rule 3's sign test, so -0.0 is
+ *    non-negative.  Cases 0 and 255 give nothing.
+ *
+ *    Local edges.  e = 4 axis + u + 2 v, where (u, v) are the offsets of the edge's lower end along the other two axes in ascending
+ *    axis order: x edges 0..3 have (u, v) = (dy, dz), y edges 4..7 have (dx, dz), z edges 8..11 have (dx, dy).  Local edge e of
+ *    cell (i, j, k) is the extract's point (voxel at its lower end, axis).
+ *
+ *    Faces.  The face across axis a on side s (the plane where coordinate a of the corners is s) has its four corners taken in the
+ *    cycle (b, c) = (0,0), (1,0), (1,1), (0,1) with b = (a + 1) mod 3 and c = (a + 2) mod 3.  For s = 1 this cycle is
+ *    counter-clockwise seen from outside the cell; for s = 0 the cycle is reversed.  Every maximal run of negative corners in a
+ *    face's cycle gives one directed segment, FROM the edge on which the cycle enters the run (positive -> negative) TO the edge on
+ *    which it leaves the run (negative -> positive).  A face whose two diagonal corners are negative has two runs and so two
+ *    segments: negative corners are cut off separately.  The rule reads only the face's four signs, so the two cells that share a
+ *    face draw the same segments in opposite directions.
+ *
+ *    Loops and triangles.  In a cell every crossing edge is the tail of exactly one segment and the head of exactly one, so the
+ *    segments form disjoint closed loops.  Loops are taken in ascending order of their lowest local edge; each loop starts at its
+ *    lowest edge and is followed along the segments: e_0, e_1, ..., e_(n-1).  Its triangles are (e_0, e_i, e_(i+1)) for
+ *    i = 1 .. n - 2.  With this direction (p_1 - p_0) x (p_2 - p_0) points into positive D: the side rule 3's normals point to.
+ *
+ *    Output.  Cells are visited in ascending l of corner 0, the triangles of a cell in the order above.  A triangle is three int32
+ *    indices into the extract's point list (n_points <= 3 2^28 and n_triangles <= 5 2^28, both < 2^31).  The order is a property
+ *    of the volume and min_weight: it does not depend on the launch, and no atomic is used.  Afterwards cba_tsdf_extract_fetch
+ *    returns the mesh's vertices and normals and cba_tsdf_mesh_fetch(h, triangles [n_triangles][3]) its triangles.  A later
+ *    cba_tsdf_extract, cba_tsdf_integrate, cba_tsdf_upload or cba_tsdf_reset does not touch arrays already fetched, but
+ *    invalidates the handle's mesh: cba_tsdf_mesh_fetch then fails until the next cba_tsdf_mesh.  n_triangles == 0 is a valid
+ *    result.  An allocation failure leaves the handle usable and without a mesh.
+ *
+ *    What the rule gives, for all 256 cases: closed loops in each of the 254 non-trivial ones; at most 4 loops in a cell, at most
+ *    7 edges in a loop, at most 5 triangles in a cell; 820 triangles in all, {0: 2, 1: 16, 2: 50, 3: 80, 4: 76, 5: 32} cases per
+ *    triangle count.  Case 1 -> (0, 4, 8); case 5 -> (0, 1, 10), (0, 10, 8); case 0x69 -> (0,4,8), (1,5,11), (2,7,9), (3,6,10);
+ *    case 0x96 -> (0,9,5), (1,10,4), (2,8,6), (3,11,7).  A case fits one 64-bit word (15 four-bit edge numbers and a count), the
+ *    whole table 2 KiB.
+ *
+ *    Guarantees.  Over live cells the directed half-edges balance, count(u -> v) = count(v -> u), except on faces shared with a
+ *    cell that is not live or lies outside the grid, where the mesh has a boundary; on a random sign field this balance holds with
+ *    half-edge multiplicity up to 2.  The surface can be non-manifold along a fan diagonal, as with classic marching cubes.  On
+ *    smooth fields (a sphere, a torus of a few voxels' radius) it is a closed oriented 2-manifold.  A corner with D exactly +-0
+ *    against negative neighbours gives t = 0 and zero-area triangles (a sphere of radius 6 voxels centred on a lattice point: 96
+ *    of its 1304); they are kept.  Points of the extract that no live cell touches stay in the point list, unreferenced.
+ *
  * cba_tsdf_fetch copies the dense [nz][ny][nx] planes of D and W out and cba_tsdf_upload writes them (a saved volume restored; the
  * values are taken as they are); either pointer may be NULL.  cba_tsdf_reset restores D = 1 and W = 0.  The handle owns one stream
  * and all of its device buffers; every call ends synchronised.  Float atomics are used nowhere.
@@ -1169,8 +1217,8 @@ void cba_cloud_index_destroy(cba_cloud_index* h);
  * n_maps > 0, xyz for n_points > 0; a side outside [2, 1024] or nx ny nz > CBA_TSDF_MAX_VOXELS; voxel_size, truncation or origin not
  * finite, voxel_size or truncation not > 0; max_weight outside [1, 2^24] or not an integer value; max_depth not > 0; an unknown
  * camera model, fx or fy equal to 0; n_maps < 0; width or height outside [1, CBA_IMAGE_MAX_SIDE]; a zero or non-finite quaternion;
- * min_weight not >= 1; cba_tsdf_extract_fetch before any extract.  n_maps == 0 is no work; create without a device ->
- * CBA_ERR_NO_DEVICE. */
+ * min_weight not >= 1; cba_tsdf_extract_fetch before any extract; NULL n_triangles; NULL triangles for n_triangles > 0;
+ * cba_tsdf_mesh_fetch without a valid mesh.  n_maps == 0 is no work; create without a device -> CBA_ERR_NO_DEVICE. */
 #define CBA_TSDF_MAX_VOXELS (1 << 28)
 typedef struct cba_tsdf_options {
     double voxel_size; /* lattice spacing (no default: the caller sets it) */
@@ -1179,7 +1227,7 @@ typedef struct cba_tsdf_options {
     double max_depth;  /* depths beyond it are not used (default +inf) */
 } cba_tsdf_options;
 void cba_tsdf_options_default(cba_tsdf_options* o); /* voxel_size and truncation are left at 0: the caller sets them */
-typedef struct cba_tsdf_volume cba_tsdf_volume; /* opaque: the volume, the buffers of its calls, the last extract's points, one stream */
+typedef struct cba_tsdf_volume cba_tsdf_volume; /* opaque: the volume, the buffers of its calls, the last extract's points, the mesh, one stream */
 cba_status cba_tsdf_volume_create(int32_t nx, int32_t ny, int32_t nz, const double* origin /*[3]*/, const cba_tsdf_options* opts,
                                   int32_t device, cba_tsdf_volume** out);
 cba_status cba_tsdf_integrate(cba_tsdf_volume* h, int32_t camera_model, const double* intr /*[10 | 12]*/, int32_t n_maps, int32_t height,
@@ -1189,6 +1237,8 @@ cba_status cba_tsdf_upload(cba_tsdf_volume* h, const float* tsdf /*[nz][ny][nx] 
 cba_status cba_tsdf_reset(cba_tsdf_volume* h);
 cba_status cba_tsdf_extract(cba_tsdf_volume* h, double min_weight, int64_t* n_points);
 cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz /*[n_points][3]*/, double* normals /*[n_points][3] or NULL*/);
+cba_status cba_tsdf_mesh(cba_tsdf_volume* h, double min_weight, int64_t* n_points, int64_t* n_triangles);
+cba_status cba_tsdf_mesh_fetch(cba_tsdf_volume* h, int32_t* triangles /*[n_triangles][3]*/);
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h);
 
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
