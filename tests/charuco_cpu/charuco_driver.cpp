@@ -1,5 +1,6 @@
 // charuco_driver.cpp — TEST-ONLY: extern "C" wrapper of marker_math.hpp and marker_board.hpp for ctypes (tests/test_charuco_cpu.py)
-// and, built as a program, a self-check with its own main (the form a sanitizer run takes) over planted lattices, votes and a marker.
+// and, built with -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers) over planted lattices,
+// votes and a marker.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -55,6 +56,7 @@ int ch_match(int squares_x, int squares_y, int min_markers, int n, const int32_t
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 #define FAIL() (std::printf("charuco self-check: line %d\n", __LINE__), ++bad)
 
 // an axis-aligned lattice of nx x ny corners, `step` px apart, from (x0, y0): the angle alternates between +pi/4 and -pi/4
@@ -172,3 +174,4 @@ int main() {
     std::printf("charuco self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

@@ -1,6 +1,6 @@
 """Independent numpy restatement of ChArUco detection (calibba.h: cba_charuco_detector, cba_marker_dictionary_generate,
 cba_chessboard_lattice, cba_charuco_match), written from the header's rule and not from marker_math.hpp / marker_board.hpp, plus the
-renderer of the end-to-end scenes and the loader of the host build (tests/charuco_cpu).  Corners come from tests/corner_ref.py."""
+renderer of the end-to-end scenes and the wrappers of the host build (tests/charuco_cpu).  Corners come from tests/corner_ref.py."""
 import math
 from collections import namedtuple
 
@@ -8,6 +8,7 @@ import numpy as np
 
 from tests import camera_ref as R
 from tests import corner_ref as CR
+from tests.host_build import ptr
 
 Options = namedtuple("Options", "arm_lengths arm_offset arm_fan_deg min_arm_contrast min_marker_contrast min_component cell_samples "
                                 "max_border_errors max_correction min_markers")
@@ -540,19 +541,6 @@ def square_quad(side, margin, ratio):
 
 
 # ---- the host build of marker_math.hpp / marker_board.hpp (tests/charuco_cpu) -----------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "charuco_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libcharucocpu.so"))
-
-
-_p = CR._p
-
-
 def host_arms(Lb, images, xy, count, dirs, o):
     import ctypes as C
 
@@ -562,8 +550,8 @@ def host_arms(Lb, images, xy, count, dirs, o):
     xy, dirs = np.ascontiguousarray(xy, float), np.ascontiguousarray(dirs, float)
     count = np.ascontiguousarray(count, np.int32)
     out = np.empty((n, m))
-    Lb.ch_arms(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(m), _p(images), _p(count), _p(xy), _p(dirs), C.c_double(o.arm_lengths[0]),
-               C.c_double(o.arm_lengths[1]), C.c_double(o.arm_offset), _p(out))
+    Lb.ch_arms(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(m), ptr(images), ptr(count), ptr(xy), ptr(dirs), C.c_double(o.arm_lengths[0]),
+               C.c_double(o.arm_lengths[1]), C.c_double(o.arm_offset), ptr(out))
     return out
 
 
@@ -575,9 +563,9 @@ def host_read(Lb, images, cell_image, quads, board, o):
     ci, q = np.ascontiguousarray(cell_image, np.int32), np.ascontiguousarray(quads, float)
     codes = np.ascontiguousarray(board.codes, np.uint64)
     out = np.zeros(len(ci), READING)
-    Lb.ch_read(C.c_int(W), C.c_int(H), _p(images), C.c_int(board.marker_bits), C.c_double(board.marker_ratio), C.c_int(len(codes)), _p(codes),
+    Lb.ch_read(C.c_int(W), C.c_int(H), ptr(images), C.c_int(board.marker_bits), C.c_double(board.marker_ratio), C.c_int(len(codes)), ptr(codes),
                C.c_int(o.cell_samples), C.c_double(o.min_marker_contrast), C.c_int(o.max_border_errors), C.c_int(o.max_correction),
-               C.c_int(len(ci)), _p(ci), _p(q), _p(out))
+               C.c_int(len(ci)), ptr(ci), ptr(q), ptr(out))
     return out
 
 

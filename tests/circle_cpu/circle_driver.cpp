@@ -1,6 +1,6 @@
 // circle_driver.cpp — TEST-ONLY: extern "C" wrapper of blob_math.hpp and circle_grid.hpp for ctypes (tests/test_circle_cpu.py) and,
-// built as a program, a self-check with its own main (the form a sanitizer run takes).  It makes the ray table as blob_detect.hip's
-// host glue does and walks every pixel with blob_detect_image.
+// built with -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers).  It makes the ray table as
+// blob_detect.hip's host glue does and walks every pixel with blob_detect_image.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -42,6 +42,7 @@ int cc_order(int n, const double* xy, const double* shape, int pattern, int rows
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 // Self-check: an ideal asymmetric 5 x 3 grid of dark discs of radius 5 at pitch 14 must give its 15 blobs without a flag, every centre
 // within 0.1 px of the truth, one labelling (unique) equal to the construction; one blob less is not found; max_blobs = 3 overflows;
 // a constant image has no peak.
@@ -96,3 +97,4 @@ int main() {
     std::printf("circle self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

@@ -1,5 +1,5 @@
 """Independent numpy restatement of circle-grid detection (calibba.h: cba_blob_detector, cba_circle_grid_order), written from the
-header's rule and not from blob_math.hpp / circle_grid.hpp, plus the renderer of the end-to-end scenes and the loader of the host
+header's rule and not from blob_math.hpp / circle_grid.hpp, plus the renderer of the end-to-end scenes and the wrappers of the host
 build (tests/circle_cpu).  Box sums come from integral images and shifted slices; sums whose order the rule fixes are accumulated
 one term at a time."""
 import math
@@ -9,6 +9,7 @@ import numpy as np
 
 from tests import camera_ref as R
 from tests import corner_ref as K
+from tests.host_build import ptr
 
 Options = namedtuple("Options", "polarity a b min_contrast nms_radius max_radius rounds max_fit_error max_axis_ratio min_radius")
 DARK, BRIGHT = 0, 1
@@ -443,19 +444,6 @@ def rms(uv, truth):
 
 
 # ---- the host build of blob_math.hpp / circle_grid.hpp (tests/circle_cpu) ---------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "circle_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libcirclecpu.so"))
-
-
-_p = K._p
-
-
 def host_detect(Lb, images, o, max_blobs, want_response=False):
     import ctypes as C
 
@@ -468,8 +456,8 @@ def host_detect(Lb, images, o, max_blobs, want_response=False):
     Sm = np.empty((n, H, W), np.uint16) if want_response else None
     Lb.cc_detect(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(max_blobs), C.c_int(o.polarity), C.c_int(o.a), C.c_int(o.b),
                  C.c_int(o.min_contrast), C.c_int(o.nms_radius), C.c_int(o.max_radius), C.c_int(o.rounds), C.c_double(o.max_fit_error),
-                 C.c_double(o.max_axis_ratio), C.c_double(o.min_radius), _p(images), _p(count), _p(status), _p(xy), _p(shape), _p(fit),
-                 _p(resp), _p(flags), _p(Rm), _p(Sm))
+                 C.c_double(o.max_axis_ratio), C.c_double(o.min_radius), ptr(images), ptr(count), ptr(status), ptr(xy), ptr(shape), ptr(fit),
+                 ptr(resp), ptr(flags), ptr(Rm), ptr(Sm))
     return dict(count=count, status=status, xy=xy, shape=shape, fit_error=fit, response=resp, flags=flags, R=Rm, S=Sm)
 
 
@@ -480,7 +468,7 @@ def host_order(Lb, xy, shape, pattern, rows, cols):
     shape = None if shape is None else np.ascontiguousarray(shape, float)
     index, unique = np.full(rows * cols, -1, np.int32), C.c_int32(0)
     Lb.cc_order.restype = C.c_int
-    found = Lb.cc_order(C.c_int(len(xy)), _p(xy), _p(shape), C.c_int(pattern), C.c_int(rows), C.c_int(cols), _p(index), C.byref(unique))
+    found = Lb.cc_order(C.c_int(len(xy)), ptr(xy), ptr(shape), C.c_int(pattern), C.c_int(rows), C.c_int(cols), ptr(index), C.byref(unique))
     return (index, unique.value) if found else (None, 0)
 
 

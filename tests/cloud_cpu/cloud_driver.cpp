@@ -1,7 +1,7 @@
 // cloud_driver.cpp — TEST-ONLY: extern "C" wrapper of cloud_math.hpp for ctypes (tests/test_cloud_cpu.py).  The grid is built on the
 // host by a counting sort with the header's cell arithmetic (points of a cell in index order); the search, the normal, the rows, the
 // Cholesky and the update are the functions every lane runs.  A source's sums are added in index order into one accumulator.  Built
-// with -DCLOUD_DRIVER_MAIN it is a stand-alone program (for the sanitizers): it checks the grid search against brute force on a
+// with -DCBA_HOST_DRIVER_MAIN it is a stand-alone program (for the sanitizers): it checks the grid search against brute force on a
 // scattered cloud with planted ties and invalid points, the normals of a plane, and that both metrics recover a known small motion.
 #include <cstdint>
 #include <cstdio>
@@ -147,7 +147,7 @@ int cloud_host_register(int64_t n, const double* xyz, const double* normals, dou
 
 }  // extern "C"
 
-#ifdef CLOUD_DRIVER_MAIN
+#ifdef CBA_HOST_DRIVER_MAIN
 static double unit(uint64_t* s) {  // a fixed sequence in [0, 1)
     *s = *s * 6364136223846793005ull + 1442695040888963407ull;
     return static_cast<double>(*s >> 11) / 9007199254740992.0;

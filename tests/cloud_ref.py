@@ -3,13 +3,14 @@ cba_cloud_register): the normal of a pixel from its 5-point cross, the nearest n
 with the header's distance and tie rule, the rows and sums of a pose's system, the unpivoted 6 x 6 Cholesky, the pose update and the
 iteration with its stop rules.  numpy's elementwise operations do not contract, and the operation order is the header's, so normals
 and neighbours can be held to the bit; sums are formed in numpy's own order, and every sum comes with the sum of its terms'
-magnitudes for the bound on what a different order can change.  Also the scene builders of both tiers and the loader of the host
+magnitudes for the bound on what a different order can change.  Also the scene builders of both tiers and the wrappers of the host
 build (tests/cloud_cpu).  Test infrastructure: no product code is imported here.
 """
 import math
-import os
 
 import numpy as np
+
+from tests.host_build import ptr
 
 OK, NOT_CONVERGED, TOO_FEW, DEGENERATE = 0, 1, 2, 3
 SCAN_TILE = 1024  # cells per workgroup of the device's scan (cloud_register.hip: CLOUD_SCAN_TILE)
@@ -299,32 +300,6 @@ def scene_pair(seed, partial=False, step=False):
 
 
 # ---- the host build (tests/cloud_cpu) ---------------------------------------------------------------------------------------------------
-def cloud_cpu_dir():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "cloud_cpu")
-
-
-def load_host_build():
-    import ctypes as C
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", cloud_cpu_dir(), "_build/libcloudcpu.so"], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(cloud_cpu_dir(), "_build", "libcloudcpu.so"))
-
-
-def build_sanitized_driver():
-    """the driver's own main as a stand-alone program under -fsanitize=address,undefined: -> its path (the CPU tier runs it once)"""
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", cloud_cpu_dir(), "_build/cloud_driver_san"], check=True, stdout=subprocess.DEVNULL)
-    return os.path.join(cloud_cpu_dir(), "_build", "cloud_driver_san")
-
-
-def _dp(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_normals(L, xyz, viewpoint=None, max_jump=np.inf):
     import ctypes as C
 
@@ -332,7 +307,7 @@ def host_normals(L, xyz, viewpoint=None, max_jump=np.inf):
     maps = p if p.ndim == 4 else p[None]
     vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64)
     out = np.empty_like(p)
-    L.cloud_host_normals(C.c_int(maps.shape[0]), C.c_int(maps.shape[1]), C.c_int(maps.shape[2]), _dp(p), _dp(vp), C.c_double(max_jump), _dp(out))
+    L.cloud_host_normals(C.c_int(maps.shape[0]), C.c_int(maps.shape[1]), C.c_int(maps.shape[2]), ptr(p), ptr(vp), C.c_double(max_jump), ptr(out))
     return out
 
 
@@ -344,8 +319,8 @@ def host_nearest(L, target, cell_size, query, max_distance):
     Q = np.ascontiguousarray(np.asarray(query, dtype=np.float64).reshape(-1, 3))
     index, dist2 = np.empty(Q.shape[0], np.int64), np.empty(Q.shape[0])
     L.cloud_host_nearest.restype = C.c_int
-    st = L.cloud_host_nearest(C.c_int64(T.shape[0]), _dp(T), C.c_double(cell_size), C.c_int64(Q.shape[0]), _dp(Q), C.c_double(max_distance),
-                              _dp(index), _dp(dist2))
+    st = L.cloud_host_nearest(C.c_int64(T.shape[0]), ptr(T), C.c_double(cell_size), C.c_int64(Q.shape[0]), ptr(Q), C.c_double(max_distance),
+                              ptr(index), ptr(dist2))
     if st != 0:
         raise RuntimeError(f"host build: grid plan {st}")
     return index, dist2
@@ -365,9 +340,9 @@ def host_register(L, target, target_normals, cell_size, sources, max_distance, m
     init = None if init_pose7 is None else np.ascontiguousarray(np.asarray(init_pose7, dtype=np.float64).reshape(len(pts), 7))
     out = np.zeros((len(pts), 53))
     L.cloud_host_register.restype = C.c_int
-    st = L.cloud_host_register(C.c_int64(T.shape[0]), _dp(T), _dp(N), C.c_double(cell_size), C.c_int(len(pts)), _dp(off), _dp(S), _dp(init),
+    st = L.cloud_host_register(C.c_int64(T.shape[0]), ptr(T), ptr(N), C.c_double(cell_size), C.c_int(len(pts)), ptr(off), ptr(S), ptr(init),
                                C.c_int(metric), C.c_double(max_distance), C.c_int(max_iterations), C.c_double(step_tolerance),
-                               C.c_int(min_pairs), _dp(out))
+                               C.c_int(min_pairs), ptr(out))
     if st != 0:
         raise RuntimeError(f"host build: grid plan {st}")
     return [dict(pose7=o[:7].copy(), rms=o[7], H=o[8:44].reshape(6, 6).copy(), g=o[44:50].copy(), n_pairs=int(o[50]), iterations=int(o[51]),

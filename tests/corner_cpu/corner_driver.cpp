@@ -1,6 +1,6 @@
 // corner_driver.cpp — TEST-ONLY: extern "C" wrapper of corner_math.hpp and corner_grid.hpp for ctypes (tests/test_corner_cpu.py) and,
-// built as a program, a self-check with its own main (the form a sanitizer run takes).  It makes the tables as corner_detect.hip's
-// host glue does and walks every pixel with corner_detect_image.
+// built with -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers).  It makes the tables as
+// corner_detect.hip's host glue does and walks every pixel with corner_detect_image.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -41,6 +41,7 @@ int cr_order(int n, const double* xy, const double* angle, int rows, int cols, i
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 // Self-check: an ideal board of 14-pixel squares must give its 5 x 4 inner corners, every refinement within 0.6 px of the truth, and
 // the grid order must be the identity of the row-major list; a constant image has no peak; max_corners = 3 overflows; a lattice with
 // one corner missing is not found.
@@ -79,3 +80,4 @@ int main() {
     std::printf("corner self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

@@ -1,5 +1,5 @@
 """Independent numpy restatement of chessboard detection (calibba.h: cba_corner_detector, cba_chessboard_order), written from the
-header's rule and not from corner_math.hpp / corner_grid.hpp, plus the renderer of the end-to-end scenes and the loader of the host
+header's rule and not from corner_math.hpp / corner_grid.hpp, plus the renderer of the end-to-end scenes and the wrappers of the host
 build (tests/corner_cpu).  Sums whose order the rule fixes are accumulated with np.cumsum (strictly left to right)."""
 import math
 from collections import namedtuple
@@ -7,6 +7,7 @@ from collections import namedtuple
 import numpy as np
 
 from tests import camera_ref as R
+from tests.host_build import ptr
 
 Options = namedtuple("Options", "min_response nms_radius cog_radius refine refine_half_window refine_iterations")
 NONE, COG, GRADIENT = 0, 1, 2
@@ -367,22 +368,6 @@ def restatement_boards(refine):
 
 
 # ---- the host build of corner_math.hpp / corner_grid.hpp (tests/corner_cpu) -----------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "corner_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libcornercpu.so"))
-
-
-def _p(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_detect(Lb, images, o, max_corners, want_response=False):
     import ctypes as C
 
@@ -393,8 +378,8 @@ def host_detect(Lb, images, o, max_corners, want_response=False):
     resp, flags = np.empty((n, max_corners), np.int32), np.empty((n, max_corners), np.int32)
     Rm = np.empty((n, H, W), np.int16) if want_response else None
     Lb.cr_detect(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(max_corners), C.c_int(o.min_response), C.c_int(o.nms_radius),
-                 C.c_int(o.cog_radius), C.c_int(o.refine), C.c_int(o.refine_half_window), C.c_int(o.refine_iterations), _p(images), _p(count),
-                 _p(status), _p(xy), _p(angle), _p(resp), _p(flags), _p(Rm))
+                 C.c_int(o.cog_radius), C.c_int(o.refine), C.c_int(o.refine_half_window), C.c_int(o.refine_iterations), ptr(images), ptr(count),
+                 ptr(status), ptr(xy), ptr(angle), ptr(resp), ptr(flags), ptr(Rm))
     return dict(count=count, status=status, xy=xy, angle=angle, response=resp, flags=flags, R=Rm)
 
 
@@ -404,7 +389,7 @@ def host_order(Lb, xy, angle, rows, cols):
     xy, angle = np.ascontiguousarray(xy, float), np.ascontiguousarray(angle, float)
     index = np.full(rows * cols, -1, np.int32)
     Lb.cr_order.restype = C.c_int
-    found = Lb.cr_order(C.c_int(len(angle)), _p(xy), _p(angle), C.c_int(rows), C.c_int(cols), _p(index))
+    found = Lb.cr_order(C.c_int(len(angle)), ptr(xy), ptr(angle), C.c_int(rows), C.c_int(cols), ptr(index))
     return index if found else None
 
 

@@ -1,6 +1,6 @@
-// dispfilter_driver.cpp — TEST-ONLY: extern "C" wrapper of disparity_filter_math.hpp for ctypes (tests/dispfilter_ref.py) and, built as
-// a program, a self-check with its own main (the form a sanitizer run takes).  dispfilter_run walks the sequence of
-// disparity_filter.hip with the tiles one after the other: median, tile-local union-find on labels local to the tile, merges along
+// dispfilter_driver.cpp — TEST-ONLY: extern "C" wrapper of disparity_filter_math.hpp for ctypes (tests/dispfilter_ref.py) and, built
+// with -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers).  dispfilter_run walks the sequence
+// of disparity_filter.hip with the tiles one after the other: median, tile-local union-find on labels local to the tile, merges along
 // the tile borders on the batch-wide labels, flatten, sizes, apply.  The self-check compares it with a sort for the median and a
 // flood fill over whole images for the components.
 #include <algorithm>
@@ -107,6 +107,7 @@ void dispfilter_run(int W, int H, int n, int median_half, int max_size, double d
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 // ---- the self-check's own statement of the rule: a sort and a flood fill -------------------------------------------------------------
 static void plain_filter(int W, int H, int n, int m, int max_size, double diff, const float* in, float* out) {
     const size_t frame = static_cast<size_t>(W) * H;
@@ -186,3 +187,4 @@ int main() {
     std::printf("disparity filter self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

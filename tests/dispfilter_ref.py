@@ -1,5 +1,5 @@
 """Independent numpy restatement of the disparity filters as calibba.h states them (cba_disparity_filter): reading, the windowed lower
-median by a sort over the stacked window, and speckle removal by a flood fill over each map.  Also the loader of the host build
+median by a sort over the stacked window, and speckle removal by a flood fill over each map.  Also the wrappers of the host build
 (tests/dispfilter_cpu), the result cache both tiers share, the option grid and the planted scenes.  Test infrastructure: the host build
 and the device are checked against it."""
 import numpy as np
@@ -100,16 +100,6 @@ def same(got, ref):
 
 
 # ---- the host build of disparity_filter_math.hpp (tests/dispfilter_cpu) ---------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dispfilter_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libdispfiltercpu.so"))
-
-
 def host_filter(Lb, maps, o, inplace=False):
     import ctypes as C
 

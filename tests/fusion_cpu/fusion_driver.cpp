@@ -1,7 +1,7 @@
 // fusion_driver.cpp — TEST-ONLY: extern "C" wrapper of tsdf_math.hpp for ctypes (tests/test_fusion_cpu.py).  The volume is kept as the
 // device keeps it ({D, W} pairs in rows of an even pitch); the update and the edges are the functions every lane runs, walked here in
-// the order the rule states.  Built with -DFUSION_DRIVER_MAIN it is a stand-alone program (for the sanitizers): it fuses four views of
-// the plane z = 1 with both camera models, checks the extracted surface against the plane, and runs the planted edge cases.
+// the order the rule states.  Built with -DCBA_HOST_DRIVER_MAIN it is a stand-alone program (for the sanitizers): it fuses four
+// views of the plane z = 1 with both camera models, checks the extracted surface against the plane, and runs the planted edge cases.
 #include <cstdint>
 #include <cstdio>
 #include <limits>
@@ -97,7 +97,7 @@ int64_t fusion_host_extract(int nx, int ny, int nz, const double* origin, double
 
 }  // extern "C"
 
-#ifdef FUSION_DRIVER_MAIN
+#ifdef CBA_HOST_DRIVER_MAIN
 int main() {
     int bad = 0;
     const double nan = std::numeric_limits<double>::quiet_NaN();

@@ -4,15 +4,15 @@ numpy's elementwise operations do not contract and the operation order is the he
 held to the bit.  The projection is written out in cba_camera_project's own expression order (Horner radial polynomial, the
 Scheimpflug constants from libm's sine and cosine): tests/camera_ref.py states the same models in the reference's order, which
 differs in the last bits, so it serves as the cross-check of this one (test_fusion_cpu) and as the renderer's unprojection.  Also the
-scene builder of both tiers (analytic depth maps of a sphere and of a bumpy surface with a depth step and holes) and the loader of
+scene builder of both tiers (analytic depth maps of a sphere and of a bumpy surface with a depth step and holes) and the wrappers of
 the host build (tests/fusion_cpu).  Test infrastructure: no product code is imported here.
 """
 import math
-import os
 
 import numpy as np
 
 from tests import camera_ref as CR
+from tests.host_build import ptr
 
 PINHOLE, SCHEIMPFLUG = CR.PINHOLE, CR.SCHEIMPFLUG
 INTEGRATE_BLOCK = 256  # lanes per workgroup of k_tsdf_integrate (tsdf_fusion.hip: TSDF_BLOCK); a lane owns two adjacent x voxels
@@ -374,32 +374,6 @@ FLAT_SHAPE = (1024, 1024, 2)  # 2048 extract tiles: the scan of the tile counts 
 
 
 # ---- the host build (tests/fusion_cpu) ---------------------------------------------------------------------------------------------------
-def fusion_cpu_dir():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "fusion_cpu")
-
-
-def load_host_build():
-    import ctypes as C
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", fusion_cpu_dir(), "_build/libfusioncpu.so"], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(fusion_cpu_dir(), "_build", "libfusioncpu.so"))
-
-
-def build_sanitized_driver():
-    """the driver's own main as a stand-alone program under -fsanitize=address,undefined: -> its path (the CPU tier runs it once)"""
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", fusion_cpu_dir(), "_build/fusion_driver_san"], check=True, stdout=subprocess.DEVNULL)
-    return os.path.join(fusion_cpu_dir(), "_build", "fusion_driver_san")
-
-
-def _p(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_integrate(L, vol, model, intr, depth, poses):
     """the host build's update of vol's planes (a Volume; not changed) -> D, W"""
     import ctypes as C
@@ -411,9 +385,9 @@ def host_integrate(L, vol, model, intr, depth, poses):
     D, W = np.ascontiguousarray(vol.D.copy()), np.ascontiguousarray(vol.W.copy())
     nx, ny, nz = vol.shape
     o = np.ascontiguousarray(vol.origin)
-    L.fusion_host_integrate(C.c_int(nx), C.c_int(ny), C.c_int(nz), _p(o), C.c_double(vol.vs), C.c_double(vol.trunc), C.c_double(vol.max_weight),
-                            C.c_double(vol.max_depth), C.c_int(model), _p(k), C.c_int(depth.shape[0]), C.c_int(depth.shape[1]),
-                            C.c_int(depth.shape[2]), _p(depth), _p(poses), _p(D), _p(W))
+    L.fusion_host_integrate(C.c_int(nx), C.c_int(ny), C.c_int(nz), ptr(o), C.c_double(vol.vs), C.c_double(vol.trunc), C.c_double(vol.max_weight),
+                            C.c_double(vol.max_depth), C.c_int(model), ptr(k), C.c_int(depth.shape[0]), C.c_int(depth.shape[1]),
+                            C.c_int(depth.shape[2]), ptr(depth), ptr(poses), ptr(D), ptr(W))
     return D, W
 
 
@@ -425,8 +399,8 @@ def host_extract(L, vol, min_weight=1.0):
     nx, ny, nz = vol.shape
     o = np.ascontiguousarray(vol.origin)
     L.fusion_host_extract.restype = C.c_int64
-    args = (C.c_int(nx), C.c_int(ny), C.c_int(nz), _p(o), C.c_double(vol.vs), _p(D), _p(W), C.c_double(min_weight))
+    args = (C.c_int(nx), C.c_int(ny), C.c_int(nz), ptr(o), C.c_double(vol.vs), ptr(D), ptr(W), C.c_double(min_weight))
     n = L.fusion_host_extract(*args, C.c_int64(0), None, None)
     xyz, nrm = np.empty((n, 3)), np.empty((n, 3))
-    assert L.fusion_host_extract(*args, C.c_int64(n), _p(xyz), _p(nrm)) == n
+    assert L.fusion_host_extract(*args, C.c_int64(n), ptr(xyz), ptr(nrm)) == n
     return xyz, nrm

@@ -1,10 +1,11 @@
 """Independent numpy restatement of laser profile scanning as calibba.h states it (cba_laser_points, cba_laser_scanner): the peak of
 one line (maximum, lowest position, plateau, window, centre of gravity), the ray-plane intersection and the frame pose.  Unprojection
-comes from tests/camera_ref.py.  Also the scene maker of the laser-scan tests, the plants of their edge cases and the loader of the host
+comes from tests/camera_ref.py.  Also the scene maker of the laser-scan tests, the plants of their edge cases and the wrappers of the host
 build (tests/laser_scan_cpu).  Test infrastructure: the host build and the device are checked against it."""
 import numpy as np
 
 from tests import camera_ref as R
+from tests.host_build import ptr
 
 SIGMA = 2.0        # px, the rendered line's Gaussian cross-section along the search axis
 AMPLITUDE = 200.0  # its height (uint8: rounded to the nearest integer)
@@ -179,22 +180,6 @@ def frame_poses(n_frames):
 
 
 # ---- the host build of laser_scan_math.hpp (tests/laser_scan_cpu) ------------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "laser_scan_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "liblaserscancpu.so"))
-
-
-def _p(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_points(L, model, intr, inv, plane, uv, frame_offset=None, poses=None, want_plane_xy=False):
     import ctypes as C
 
@@ -206,8 +191,8 @@ def host_points(L, model, intr, inv, plane, uv, frame_offset=None, poses=None, w
     n_frames = 0 if poses is None else len(poses)
     xyz = np.empty((n, 3))
     pxy = np.empty((n, 2)) if want_plane_xy else None
-    L.ls_points(C.c_int(model), _p(intr), C.c_int(0 if inv is None else inv.size), _p(inv), _p(plane), C.c_int64(n), _p(uv), C.c_int(n_frames),
-                _p(off), _p(poses), _p(xyz), _p(pxy))
+    L.ls_points(C.c_int(model), ptr(intr), C.c_int(0 if inv is None else inv.size), ptr(inv), ptr(plane), C.c_int64(n), ptr(uv), C.c_int(n_frames),
+                ptr(off), ptr(poses), ptr(xyz), ptr(pxy))
     return (xyz, pxy) if want_plane_xy else xyz
 
 
@@ -223,10 +208,10 @@ def host_scan(L, model, intr, inv, plane, images, o, poses=None):
     n_lines = W if o.axis == 0 else H
     r = {k: np.empty((n_frames, n_lines)) for k in ("centre", "amplitude", "width_px")}
     r["xyz"] = np.empty((n_frames, n_lines, 3))
-    L.ls_scan(C.c_int(model), _p(intr), C.c_int(0 if inv is None else inv.size), _p(inv), _p(plane), C.c_int(W), C.c_int(H), C.c_int(o.axis),
+    L.ls_scan(C.c_int(model), ptr(intr), C.c_int(0 if inv is None else inv.size), ptr(inv), ptr(plane), C.c_int(W), C.c_int(H), C.c_int(o.axis),
               C.c_int(pb), C.c_int(pe), C.c_int(o.half_window), C.c_double(o.floor_level), C.c_double(o.min_peak), C.c_int(n_frames),
-              C.c_int(0 if images.dtype == np.uint8 else 1), _p(images), _p(poses), _p(r["centre"]), _p(r["amplitude"]), _p(r["width_px"]),
-              _p(r["xyz"]))
+              C.c_int(0 if images.dtype == np.uint8 else 1), ptr(images), ptr(poses), ptr(r["centre"]), ptr(r["amplitude"]), ptr(r["width_px"]),
+              ptr(r["xyz"]))
     return r
 
 

@@ -1,6 +1,6 @@
 // mesh_driver.cpp — TEST-ONLY: extern "C" wrapper of tsdf_mesh_math.hpp for ctypes (tests/test_mesh_cpu.py).  The volume is kept as the
 // device keeps it ({D, W} pairs in rows of an even pitch); the edge records are built per group of 64 voxels as the extract's waves
-// build them, and the cells are walked in ascending l with the functions every lane runs.  Built with -DMESH_DRIVER_MAIN it is a
+// build them, and the cells are walked in ascending l with the functions every lane runs.  Built with -DCBA_HOST_DRIVER_MAIN it is a
 // stand-alone program (for the sanitizers): it checks the table's counts and named cases, meshes a sphere and a volume whose rows
 // straddle the groups, and checks that every index is a point and every directed edge of the closed sphere has its reverse.
 #include <cmath>
@@ -88,7 +88,7 @@ int64_t mesh_host_triangles(int nx, int ny, int nz, const float* D, const float*
 
 }  // extern "C"
 
-#ifdef MESH_DRIVER_MAIN
+#ifdef CBA_HOST_DRIVER_MAIN
 static bool word_is(uint64_t word, std::vector<int> edges) {
     if (tsdf_mesh_word_count(word) * 3 != static_cast<int>(edges.size())) return false;
     for (size_t s = 0; s < edges.size(); ++s)

@@ -3,14 +3,14 @@ triangles per sign pattern, generated from the rule with code of its own (corner
 to start outside a run; tsdf_mesh_math.hpp works on bit patterns), and the mesh of a fusion_ref.Volume, vectorised: the index of an
 edge is a cumulative sum over the extract's mask, the cases and the table lookups are array operations.  Every output is an integer,
 so the device and the host build are held to it bit for bit.  Also the fields of both tiers (sphere, torus, all cases, random signs,
-the weight hole), the mesh statistics the tests use as checks, and the loader of the host build (tests/mesh_cpu).  Test
+the weight hole), the mesh statistics the tests use as checks, and the wrappers of the host build (tests/mesh_cpu).  Test
 infrastructure: no product code is imported here.
 """
-import os
 
 import numpy as np
 
 from tests import fusion_ref as F
+from tests.host_build import ptr
 
 MESH_BLOCK = 256  # lanes per workgroup of k_tsdf_mesh (tsdf_fusion.hip: TSDF_BLOCK)
 MESH_TILE = 1024  # cells per workgroup (tsdf_math.hpp: TSDF_EXTRACT_TILE; the mesh walks the extract's tiles)
@@ -325,26 +325,6 @@ def zero_sphere():
 
 
 # ---- the host build (tests/mesh_cpu) ---------------------------------------------------------------------------------------------------
-def mesh_cpu_dir():
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "mesh_cpu")
-
-
-def load_host_build():
-    import ctypes as C
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", mesh_cpu_dir(), "_build/libmeshcpu.so"], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(mesh_cpu_dir(), "_build", "libmeshcpu.so"))
-
-
-def build_sanitized_driver():
-    """the driver's own main as a stand-alone program under -fsanitize=address,undefined: -> its path (the CPU tier runs it once)"""
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", mesh_cpu_dir(), "_build/mesh_driver_san"], check=True, stdout=subprocess.DEVNULL)
-    return os.path.join(mesh_cpu_dir(), "_build", "mesh_driver_san")
-
-
 def host_table(L):
     import ctypes as C
 
@@ -359,11 +339,10 @@ def host_triangles(L, vol, min_weight=1.0):
 
     D, W = np.ascontiguousarray(vol.D), np.ascontiguousarray(vol.W)
     nx, ny, nz = vol.shape
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
     L.mesh_host_triangles.restype = C.c_int64
     n_points = np.zeros(1, np.int64)
-    args = (C.c_int(nx), C.c_int(ny), C.c_int(nz), p(D), p(W), C.c_double(min_weight), p(n_points))
+    args = (C.c_int(nx), C.c_int(ny), C.c_int(nz), ptr(D), ptr(W), C.c_double(min_weight), ptr(n_points))
     m = L.mesh_host_triangles(*args, C.c_int64(0), None)
     tri = np.zeros((m, 3), np.int32)
-    assert L.mesh_host_triangles(*args, C.c_int64(m), p(tri)) == m
+    assert L.mesh_host_triangles(*args, C.c_int64(m), ptr(tri)) == m
     return int(n_points[0]), tri

@@ -1,6 +1,7 @@
-// sgm_driver.cpp — TEST-ONLY: extern "C" wrapper of sgm_math.hpp for ctypes (tests/sgm_ref.py) and, built as a program, a self-check
-// with its own main (the form a sanitizer run takes).  It fills the geometry as the host glue of stereo_sgm.hip does and walks every
-// path of every pair with sgm_match_pair (the scalar recurrence that the packed kernel must reproduce).
+// sgm_driver.cpp — TEST-ONLY: extern "C" wrapper of sgm_math.hpp for ctypes (tests/sgm_ref.py) and, built with
+// -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers).  It fills the geometry as the host glue
+// of stereo_sgm.hip does and walks every path of every pair with sgm_match_pair (the scalar recurrence that the packed kernel must
+// reproduce).
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -25,6 +26,7 @@ void sgm_match(int W, int H, int n_pairs, int dmin, int D, int p1, int p2, int p
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 // Self-check: a textured pair moved by 5 columns must come back as disparity 5 in the interior (where no census window sees an image
 // border; the path sums there need not be 0, since a path carries what it met at the border), for 4 and 8 paths, an odd size and a D
 // that is no multiple of 16.
@@ -63,3 +65,4 @@ int main() {
     std::printf("sgm self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

@@ -1,8 +1,10 @@
 """Independent numpy restatement of semi-global matching as calibba.h states it (cba_sgm_matcher): the census bits by shifted copies of
 the zero-padded image, the Hamming cost volume, every path as a sweep over whole rows or columns of candidates arrays, the sum S, and
-argmin / uniqueness / left-right check / parabola taken on the S volume.  Also the loader of the host build (tests/sgm_cpu), the
+argmin / uniqueness / left-right check / parabola taken on the S volume.  Also the wrappers of the host build (tests/sgm_cpu), the
 result cache both tiers share, and option_cases().  Test infrastructure: the host build and the device are checked against it."""
 import numpy as np
+
+from tests.host_build import ptr
 
 from tests.stereo_ref import GEOM, POSE, bitwise, points, random_pairs, truth_pair  # noqa: F401  (scenes and comparisons)
 
@@ -178,22 +180,6 @@ def noise_pair(H=16, W=64, seed=5):
 
 
 # ---- the host build of sgm_math.hpp (tests/sgm_cpu) -------------------------------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sgm_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libsgmcpu.so"))
-
-
-def _p(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_match(Lb, left, right, o, geom=None, pose=None):
     import ctypes as C
 
@@ -204,8 +190,8 @@ def host_match(Lb, left, right, o, geom=None, pose=None):
     g = None if geom is None else np.ascontiguousarray(geom, float)
     p = None if pose is None else np.ascontiguousarray(pose, float)
     Lb.sgm_match(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(o.min_disparity), C.c_int(o.num_disparities), C.c_int(o.p1), C.c_int(o.p2),
-                 C.c_int(o.paths), C.c_int(o.uniqueness_percent), C.c_int(o.lr_max_diff), C.c_int(o.subpixel), _p(left), _p(right), _p(g), _p(p),
-                 _p(disp), _p(cost), _p(xyz))
+                 C.c_int(o.paths), C.c_int(o.uniqueness_percent), C.c_int(o.lr_max_diff), C.c_int(o.subpixel), ptr(left), ptr(right), ptr(g), ptr(p),
+                 ptr(disp), ptr(cost), ptr(xyz))
     return dict(disparity=disp, cost=cost, xyz=xyz)
 
 

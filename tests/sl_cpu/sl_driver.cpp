@@ -1,7 +1,7 @@
 // sl_driver.cpp — TEST-ONLY: extern "C" wrapper of structured_light_math.hpp for ctypes (tests/test_structured_light_cpu.py).  It
 // fills the rule as the library's host glue does, generates the patterns with the library's generator and decodes every pixel with
-// the functions every lane runs, four pixels of a row at a time and one image after the other.  Built with -DSL_DRIVER_MAIN it is a
-// stand-alone program (for the sanitizers): it generates a sequence, decodes it as a camera that is the projector and checks that
+// the functions every lane runs, four pixels of a row at a time and one image after the other.  Built with -DCBA_HOST_DRIVER_MAIN it is
+// a stand-alone program (for the sanitizers): it generates a sequence, decodes it as a camera that is the projector and checks that
 // every pixel decodes to its own index.
 #include <cstdint>
 #include <cstdio>
@@ -75,7 +75,7 @@ void sl_host_decode(int pw, int ph, int axes, int s, int N, int T, int min_contr
 
 }  // extern "C"
 
-#ifdef SL_DRIVER_MAIN
+#ifdef CBA_HOST_DRIVER_MAIN
 int main() {
     int bad = 0;
     const int cases[][5] = {{37, 21, 0, 0, 16}, {37, 21, 0, 4, 16}, {200, 120, 3, 3, 16}, {2, 2, 0, 0, 16}, {33, 5, 2, 8, 8}};  // pw ph s N T

@@ -1,6 +1,6 @@
 """Independent numpy restatement of structured-light decoding as calibba.h states it (cba_sl_patterns, cba_sl_decoder): the patterns,
 the per-pixel decode in plain integer and fp64 array arithmetic (weights and pattern cosines from math.sin / math.cos, the C
-library's), the scene renderer with its exact projector coordinates, and the ctypes loader of the host build (tests/sl_cpu).  Test
+library's), the scene renderer with its exact projector coordinates, and the ctypes wrappers of the host build (tests/sl_cpu).  Test
 infrastructure: the host build and the device are checked against it."""
 import math
 
@@ -331,30 +331,6 @@ def planted_images(W, H, places, plant_list=None):
 
 
 # ---- the host build of structured_light_math.hpp (tests/sl_cpu) ------------------------------------------------------------------------
-def sl_cpu_dir():
-    import os
-
-    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "sl_cpu")
-
-
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", sl_cpu_dir(), "_build/libslcpu.so"], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(sl_cpu_dir(), "_build", "libslcpu.so"))
-
-
-def build_sanitized_driver():
-    """the driver's own main as a stand-alone program under -fsanitize=address,undefined: -> its path (the CPU tier runs it once)"""
-    import os
-    import subprocess
-
-    subprocess.run(["make", "-s", "-C", sl_cpu_dir(), "_build/sl_driver_san"], check=True, stdout=subprocess.DEVNULL)
-    return os.path.join(sl_cpu_dir(), "_build", "sl_driver_san")
-
-
 def _opts_args(o):
     import ctypes as C
 

@@ -1,6 +1,7 @@
-// stereo_driver.cpp — TEST-ONLY: extern "C" wrapper of stereo_math.hpp for ctypes (tests/test_stereo_cpu.py) and, built as a program,
-// a self-check with its own main (the form a sanitizer run takes).  It fills the geometry as stereo_match.hip's host glue does and
-// walks every pixel with stereo_match_pair (the naive window sum that every tiling of the kernels must reproduce).
+// stereo_driver.cpp — TEST-ONLY: extern "C" wrapper of stereo_math.hpp for ctypes (tests/test_stereo_cpu.py) and, built with
+// -DCBA_HOST_DRIVER_MAIN, a stand-alone program whose main checks itself (for the sanitizers).  It fills the geometry as
+// stereo_match.hip's host glue does and walks every pixel with stereo_match_pair (the naive window sum that every tiling of the
+// kernels must reproduce).
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -37,6 +38,7 @@ void st_points(const double* geom, const double* pose7, int64_t n, const double*
 
 }  // extern "C"
 
+#ifdef CBA_HOST_DRIVER_MAIN
 // Self-check: a textured pair moved by 5 columns must come back as disparity 5 wherever 5 is admissible, at every window size and
 // with every switch on; rectification of a toe-in rig must give orthonormal rotations; the error paths return an error.
 int main() {
@@ -82,3 +84,4 @@ int main() {
     std::printf("stereo self-check: %s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
 }
+#endif

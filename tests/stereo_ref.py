@@ -1,8 +1,10 @@
 """Independent numpy restatement of stereo depth as calibba.h states it (cba_stereo_rectify, cba_stereo_matcher, cba_stereo_points):
 the closed-form rectification, the whole cost volume by integral images with argmin / uniqueness / left-right check / parabola taken on
-it, and disparity to 3D.  Also the scene makers of the stereo tests and the loader of the host build (tests/stereo_cpu).  Test
+it, and disparity to 3D.  Also the scene makers of the stereo tests and the wrappers of the host build (tests/stereo_cpu).  Test
 infrastructure: the host build and the device are checked against it."""
 import numpy as np
+
+from tests.host_build import ptr
 
 BIG = 1 << 40  # "not admissible" in the cost volume
 
@@ -185,30 +187,14 @@ def random_pairs(n, H, W, shift=3, seed=0):
 
 
 # ---- the host build of stereo_math.hpp (tests/stereo_cpu) -----------------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stereo_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libstereocpu.so"))
-
-
-def _p(a):
-    import ctypes as C
-
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def host_rectify(Lb, intr, c_T_r, W, H, focal=0.0, cx=0.0, cy=0.0):
     import ctypes as C
 
     intr, c_T_r = np.ascontiguousarray(intr, float), np.ascontiguousarray(c_T_r, float)
     R, K, B, rt = np.empty((2, 9)), np.empty((2, 5)), np.empty(1), np.empty(7)
     Lb.st_rectify.restype = C.c_int
-    st = Lb.st_rectify(_p(intr), C.c_int(intr.shape[1]), _p(c_T_r), C.c_int(W), C.c_int(H), C.c_double(focal), C.c_double(cx), C.c_double(cy),
-                       _p(R), _p(K), _p(B), _p(rt))
+    st = Lb.st_rectify(ptr(intr), C.c_int(intr.shape[1]), ptr(c_T_r), C.c_int(W), C.c_int(H), C.c_double(focal), C.c_double(cx), C.c_double(cy),
+                       ptr(R), ptr(K), ptr(B), ptr(rt))
     if st:
         raise ValueError("stereo_rectify refused the input")
     return dict(R=R.reshape(2, 3, 3), new_k5=K, baseline=float(B[0]), r_T_rect=rt)
@@ -224,8 +210,8 @@ def host_match(Lb, left, right, o, geom=None, pose=None):
     g = None if geom is None else np.ascontiguousarray(geom, float)
     p = None if pose is None else np.ascontiguousarray(pose, float)
     Lb.st_match(C.c_int(W), C.c_int(H), C.c_int(n), C.c_int(o.min_disparity), C.c_int(o.num_disparities), C.c_int(o.half_window),
-                C.c_int(o.uniqueness_percent), C.c_int(o.lr_max_diff), C.c_int(o.subpixel), _p(left), _p(right), _p(g), _p(p), _p(disp), _p(cost),
-                _p(xyz))
+                C.c_int(o.uniqueness_percent), C.c_int(o.lr_max_diff), C.c_int(o.subpixel), ptr(left), ptr(right), ptr(g), ptr(p), ptr(disp), ptr(cost),
+                ptr(xyz))
     return dict(disparity=disp, cost=cost, xyz=xyz)
 
 
@@ -236,7 +222,7 @@ def host_points(Lb, uvd, geom, pose=None):
     g = np.ascontiguousarray(geom, float)
     p = None if pose is None else np.ascontiguousarray(pose, float)
     xyz = np.empty_like(uvd)
-    Lb.st_points(_p(g), _p(p), C.c_int64(len(uvd)), _p(uvd), _p(xyz))
+    Lb.st_points(ptr(g), ptr(p), C.c_int64(len(uvd)), ptr(uvd), ptr(xyz))
     return xyz
 
 

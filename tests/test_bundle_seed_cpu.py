@@ -13,17 +13,16 @@ from calibration_amd.capi import dptr, i32ptr, i64ptr
 from calibration_amd.geometry import quat_to_rotmat, rotmat_to_quat
 from tests import bundle_seed_ref as bref
 from tests import extrinsic_dlt_ref as ref
+from tests import host_build
 from tests import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BSDIR = os.path.join(ROOT, "tests", "bundle_seed_cpu")
 I7 = np.array([1.0, 0, 0, 0, 0, 0, 0])
 
 
 @pytest.fixture(scope="module")
 def bs():
-    subprocess.run(["make", "-s", "-C", BSDIR], check=True, stdout=subprocess.DEVNULL)
-    lib = C.CDLL(os.path.join(BSDIR, "_build", "libbscpu.so"))
+    lib = host_build.load("bundle_seed_cpu")
     P, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
     lib.bs_pose_row_c.argtypes = [P, P, P]
     lib.bs_target_c.argtypes = [C.c_int, P, I, P, P, P]

@@ -2,8 +2,6 @@
 the literal numpy restatement tests/camera_ref.py and the oracle's projection, its unprojection against tests/linescan_cpu's
 ls_unproject bit for bit, and the C ABI's argument errors (raised before any device work)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,44 +9,34 @@ import pytest
 from calibration_amd import camera as cam
 from calibration_amd import capi
 from tests import camera_ref as R
+from tests import host_build
+from tests.host_build import ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-c_d = C.POINTER(C.c_double)
 c_f = C.POINTER(C.c_float)
-
-
-def _lib(sub, name):
-    d = os.path.join(ROOT, "tests", sub)
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", name))
 
 
 @pytest.fixture(scope="module")
 def camcpu():
-    return _lib("camera_cpu", "libcamcpu.so")
+    return host_build.load("camera_cpu")
 
 
 @pytest.fixture(scope="module")
 def lscpu():
-    return _lib("linescan_cpu", "liblscpu.so")
-
-
-def _p(a):
-    return a.ctypes.data_as(c_d)
+    return host_build.load("linescan_cpu")
 
 
 def host_project(L, model, intr, xyz):
     xyz = np.ascontiguousarray(xyz, float)
     uv = np.empty((xyz.shape[0], 2))
-    L.cam_project(model, _p(np.asarray(intr, float)), C.c_int64(xyz.shape[0]), _p(xyz), _p(uv))
+    L.cam_project(model, ptr(np.asarray(intr, float)), C.c_int64(xyz.shape[0]), ptr(xyz), ptr(uv))
     return uv
 
 
 def host_unproject(L, model, intr, uv, inv=None):
     uv = np.ascontiguousarray(uv, float)
     xy = np.empty_like(uv)
-    L.cam_unproject(model, _p(np.asarray(intr, float)), 0 if inv is None else len(inv), None if inv is None else _p(np.asarray(inv, float)),
-                    C.c_int64(uv.shape[0]), _p(uv), _p(xy))
+    L.cam_unproject(model, ptr(np.asarray(intr, float)), 0 if inv is None else len(inv), None if inv is None else ptr(np.asarray(inv, float)),
+                    C.c_int64(uv.shape[0]), ptr(uv), ptr(xy))
     return xy
 
 
@@ -57,9 +45,9 @@ def host_map(L, model, intrs, W, H, Rs=None, Kp=None):
     n = intrs.shape[0]
     mx = np.empty((n, H, W), np.float32)
     my = np.empty_like(mx)
-    Rp = None if Rs is None else _p(np.ascontiguousarray(Rs, float))
-    Kpp = None if Kp is None else _p(np.ascontiguousarray(Kp, float))
-    L.cam_map(model, n, _p(intrs), Rp, Kpp, W, H, mx.ctypes.data_as(c_f), my.ctypes.data_as(c_f))
+    Rp = None if Rs is None else ptr(np.ascontiguousarray(Rs, float))
+    Kpp = None if Kp is None else ptr(np.ascontiguousarray(Kp, float))
+    L.cam_map(model, n, ptr(intrs), Rp, Kpp, W, H, mx.ctypes.data_as(c_f), my.ctypes.data_as(c_f))
     return mx, my
 
 
@@ -89,7 +77,7 @@ def test_project_matches_restatement_and_oracle(camcpu, oracle, name, model, int
     ref = np.empty(2)
     orc = np.empty_like(uv)
     for i in range(0, xyz.shape[0], 7):
-        oracle.orc_project(model, _p(intr), _p(np.ascontiguousarray(xyz[i])), _p(ref))
+        oracle.orc_project(model, capi.dptr(intr), capi.dptr(np.ascontiguousarray(xyz[i])), capi.dptr(ref))
         orc[i] = ref
     assert _rel(uv[::7], orc[::7]) <= 1e-9
 
@@ -104,8 +92,8 @@ def test_unproject_matches_restatement_and_linescan_bitwise(camcpu, lscpu, name,
     # tests/linescan_cpu's ls_unproject: the same code, so the same bits
     u, v = np.ascontiguousarray(uv[:, 0]), np.ascontiguousarray(uv[:, 1])
     x, y = np.empty(len(u)), np.empty(len(u))
-    lscpu.ls_unproject(model, _p(intr), 0 if inv is None else len(inv), None if inv is None else _p(np.ascontiguousarray(inv)), len(u),
-                       _p(u), _p(v), _p(x), _p(y))
+    lscpu.ls_unproject(model, ptr(intr), 0 if inv is None else len(inv), None if inv is None else ptr(np.ascontiguousarray(inv)), len(u),
+                       ptr(u), ptr(v), ptr(x), ptr(y))
     assert np.array_equal(xy[:, 0], x) and np.array_equal(xy[:, 1], y)
     if not dual:  # the 5-step fixed point undoes project to well below a pixel's worth
         xyz = R.points(3000, seed=5)
@@ -125,8 +113,8 @@ def test_fill_camera_pads_with_zeros_and_builds_the_constants(camcpu, name, mode
     n_inv = 0 if inverse == "none" else 4
     m, k = C.c_int(-1), C.c_int(-1)
     intr12, inv16, sd, sd_ref = np.empty(12), np.empty(16), np.empty(36), np.empty(36)
-    camcpu.cam_fill_camera(model, _p(intr), n_inv, None if inv is None else _p(inv), C.byref(m), C.byref(k), _p(intr12), _p(inv16),
-                           _p(sd), _p(sd_ref))
+    camcpu.cam_fill_camera(model, ptr(intr), n_inv, None if inv is None else ptr(inv), C.byref(m), C.byref(k), ptr(intr12), ptr(inv16),
+                           ptr(sd), ptr(sd_ref))
     assert m.value == model
     assert k.value == (4 if inv is not None else 0)
     assert np.array_equal(intr12[:ni], intr)

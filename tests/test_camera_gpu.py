@@ -4,7 +4,6 @@ consistency; apply of whole image batches; repeatability; NaN and out-of-range m
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 from calibration_amd import camera as cam
 from calibration_amd import distortion as D
 from tests import camera_ref as R
+from tests import host_build
 
 pytestmark = pytest.mark.gpu
 
@@ -26,9 +26,7 @@ def _rel(a, b):
 
 @pytest.fixture(scope="module")
 def camcpu():
-    d = os.path.join(ROOT, "tests", "camera_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libcamcpu.so"))
+    return host_build.load("camera_cpu")
 
 
 @pytest.mark.parametrize("n", [1, 63, 65, 1_000_000])

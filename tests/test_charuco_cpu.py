@@ -4,13 +4,13 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, detect
 from tests import charuco_ref as S
+from tests import host_build
 
 READ_CASES = S.read_cases()
 ARM_CASES = S.arm_cases()
@@ -18,7 +18,7 @@ ARM_CASES = S.arm_cases()
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("charuco_cpu")
 
 
 @pytest.fixture(scope="module")
@@ -122,7 +122,7 @@ def _all_lattices(host, xy, ang, min_component=4):
     hc, hij = np.full(max(n, 1), -1, np.int32), np.zeros((max(n, 1), 2), np.int32)
     xyc, angc = np.ascontiguousarray(xy, float), np.ascontiguousarray(ang, float)
     host.ch_lattice.restype = C.c_int
-    hk = host.ch_lattice(C.c_int(n), S._p(xyc), S._p(angc), C.c_int(min_component), S._p(hc), S._p(hij))
+    hk = host.ch_lattice(C.c_int(n), host_build.ptr(xyc), host_build.ptr(angc), C.c_int(min_component), host_build.ptr(hc), host_build.ptr(hij))
     for got in ((comp, ij, k), (hc[:n], hij[:n], hk)):
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and got[2] == ref[2]
     return ref
@@ -163,9 +163,9 @@ def _all_matches(host, board, comp, ij, xy, cells, flags, ids, rots, min_markers
     oi, oxy, nm = np.full(nb, -1, np.int32), np.full((nb, 2), np.nan), np.zeros(1, np.int32)
     a = [np.ascontiguousarray(v, np.int32) for v in (comp, ij, cells, flags, ids, rots)]
     host.ch_match.restype = C.c_int
-    cnt = host.ch_match(C.c_int(board.squares_x), C.c_int(board.squares_y), C.c_int(min_markers), C.c_int(len(comp)), S._p(a[0]), S._p(a[1]),
-                        S._p(np.ascontiguousarray(xy, float)), C.c_int(len(cells)), S._p(a[2]), S._p(a[3]), S._p(a[4]), S._p(a[5]), S._p(oi), S._p(oxy),
-                        S._p(nm))
+    cnt = host.ch_match(C.c_int(board.squares_x), C.c_int(board.squares_y), C.c_int(min_markers), C.c_int(len(comp)), host_build.ptr(a[0]), host_build.ptr(a[1]),
+                        host_build.ptr(np.ascontiguousarray(xy, float)), C.c_int(len(cells)), host_build.ptr(a[2]), host_build.ptr(a[3]), host_build.ptr(a[4]), host_build.ptr(a[5]), host_build.ptr(oi), host_build.ptr(oxy),
+                        host_build.ptr(nm))
     for g in (got, (oi[:cnt], oxy[:cnt], int(nm[0]))):
         assert np.array_equal(g[0], ref[0]) and np.array_equal(g[1], ref[1]) and g[2] == ref[2]
     return ref
@@ -295,9 +295,9 @@ def test_host_calls_reject_bad_arguments(lib):
 
 
 def test_selfcheck_under_sanitizers():
-    """the stand-alone driver program (its own main), built with -fsanitize=address,undefined, runs clean over the planted cases"""
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "charuco_cpu")
-    r = subprocess.run(["make", "-s", "-C", d, "SANITIZE=1", "selfcheck"], capture_output=True, text=True)
+    """the stand-alone driver program (its own main), built under the address and undefined-behaviour sanitizers, runs clean over the
+    planted cases"""
+    r = host_build.run_sanitized("charuco_cpu")
     assert r.returncode == 0 and "charuco self-check: ok" in r.stdout, r.stdout + r.stderr
 
 

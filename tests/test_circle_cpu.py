@@ -6,18 +6,18 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, detect
 from tests import circle_ref as S
+from tests import host_build
 
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("circle_cpu")
 
 
 # ---- the header against the restatement ----------------------------------------------------------------------------------------------
@@ -120,9 +120,8 @@ def test_ray_table(host):
 
 
 def test_selfcheck_under_sanitizers():
-    """the stand-alone driver program (its own main), built with -fsanitize=address,undefined, runs clean"""
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "circle_cpu")
-    r = subprocess.run(["make", "-s", "-C", d, "SANITIZE=1", "selfcheck"], capture_output=True, text=True)
+    """the stand-alone driver program (its own main), built under the address and undefined-behaviour sanitizers, runs clean"""
+    r = host_build.run_sanitized("circle_cpu")
     assert r.returncode == 0 and "circle self-check: ok" in r.stdout, r.stdout + r.stderr
 
 

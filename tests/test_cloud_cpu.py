@@ -3,7 +3,6 @@
 the bars of the GPU tier - and against ground truth on rendered scenes; the conditions under which the GPU tier compares full solves;
 the stand-alone driver under the sanitizers; and what the library checks before it asks for a device."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import pytest
 from calibration_amd import capi
 from calibration_amd.capi import dptr, i64ptr
 from tests import cloud_ref as R
+from tests import host_build
 
 MD, CELL = 0.05, 0.0501
 # The scenes of the full solves (cloud_ref.scene_pair): (seed, partial, step).  "plain": the whole source lies on the target's surface;
@@ -28,7 +28,7 @@ NORMAL_SIZES = [(1, 1), (3, 2), (64, 4), (65, 3), (130, 33)]
 
 @pytest.fixture(scope="module")
 def host():
-    return R.load_host_build()
+    return host_build.load("cloud_cpu")
 
 
 _solved = {}
@@ -53,8 +53,7 @@ def normal_map(W, H):
 
 # ---- the stand-alone program under the sanitizers ------------------------------------------------------------------------------------
 def test_driver_runs_clean_under_sanitizers():
-    exe = R.build_sanitized_driver()
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    p = host_build.run_sanitized("cloud_cpu")
     assert p.returncode == 0, p.stdout + p.stderr
     assert "cloud_driver: 0 mismatches" in p.stdout and not p.stderr.strip(), p.stdout + p.stderr
 

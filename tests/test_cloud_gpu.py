@@ -13,6 +13,7 @@ import calibration_amd as cal
 from calibration_amd import capi
 from calibration_amd.registration import CloudIndex, IcpOptions, default_cell_size, point_normals, register
 from tests import cloud_ref as R
+from tests import host_build
 from tests import test_cloud_cpu as cpu
 from tests.test_cloud_cpu import CELL, INIT, MD, TRUTH_ERROR, check_sums, normal_map, planar_scene, ragged_sources, solved
 
@@ -23,7 +24,7 @@ SCAN_TILE = 1024  # the scan kernel's block of cells (cloud_register.hip: CLOUD_
 
 @pytest.fixture(scope="module")
 def host():
-    return R.load_host_build()
+    return host_build.load("cloud_cpu")
 
 
 def as_dict(r):

@@ -6,18 +6,18 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, detect
 from tests import corner_ref as S
+from tests import host_build
 
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("corner_cpu")
 
 
 # ---- the header against the restatement ----------------------------------------------------------------------------------------------
@@ -97,9 +97,8 @@ def test_tables(host):
 
 
 def test_selfcheck_under_sanitizers():
-    """the stand-alone driver program (its own main), built with -fsanitize=address,undefined, runs clean"""
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "corner_cpu")
-    r = subprocess.run(["make", "-s", "-C", d, "SANITIZE=1", "selfcheck"], capture_output=True, text=True)
+    """the stand-alone driver program (its own main), built under the address and undefined-behaviour sanitizers, runs clean"""
+    r = host_build.run_sanitized("corner_cpu")
     assert r.returncode == 0 and "corner self-check: ok" in r.stdout, r.stdout + r.stderr
 
 

@@ -5,20 +5,20 @@ argument errors of the C ABI and of the Python layer (raised before any device w
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, stereo
 from tests import dispfilter_ref as G
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host():
-    return G.load_host_build()
+    return host_build.load("dispfilter_cpu")
 
 
 def test_tile_constants_match_the_header():
@@ -53,9 +53,10 @@ def test_planted(host, case):
 
 
 def test_selfcheck_program(host):
-    """the stand-alone program of tests/dispfilter_cpu (its own main; the form a sanitizer run takes)"""
-    d = os.path.join(ROOT, "tests", "dispfilter_cpu")
-    subprocess.run(["make", "-s", "-C", d, "selfcheck"], check=True, stdout=subprocess.DEVNULL)
+    """the stand-alone program of tests/dispfilter_cpu (its own main), built under the address and undefined-behaviour sanitizers, runs
+    clean"""
+    r = host_build.run_sanitized("dispfilter_cpu")
+    assert r.returncode == 0, r.stdout + r.stderr
 
 
 # ---- argument errors, all before any device work ------------------------------------------------------------------------------------

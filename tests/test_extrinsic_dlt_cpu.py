@@ -2,8 +2,6 @@
 (tests/extrinsic_dlt_cpu) against the numpy restatement tests/extrinsic_dlt_ref.py, and the C ABI's argument errors, which are all
 raised before any device work."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +10,13 @@ from calibration_amd import capi, rig
 from calibration_amd.capi import dptr, i32ptr, i64ptr
 from calibration_amd.geometry import rotmat_to_quat
 from tests import extrinsic_dlt_ref as ref
+from tests import host_build
 from tests import synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXTDIR = os.path.join(ROOT, "tests", "extrinsic_dlt_cpu")
 
 
 @pytest.fixture(scope="module")
 def ext():
-    subprocess.run(["make", "-s", "-C", EXTDIR], check=True, stdout=subprocess.DEVNULL)
-    lib = C.CDLL(os.path.join(EXTDIR, "_build", "libextcpu.so"))
+    lib = host_build.load("extrinsic_dlt_cpu")
     P, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
     lib.ext_average_c.argtypes = [C.c_int, P, P]
     lib.ext_steps_c.argtypes = [C.c_int, C.c_int, P, I, P, P]

@@ -6,7 +6,6 @@ asks for a device."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from calibration_amd.capi import dptr
 from tests import camera_ref as CR
 from tests import cloud_ref as R
 from tests import fusion_ref as F
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -44,7 +44,7 @@ SPHERE_VIEWS = CHAIN["sphere"]["views"]
 
 @pytest.fixture(scope="module")
 def host():
-    return F.load_host_build()
+    return host_build.load("fusion_cpu")
 
 
 def same(a, b):
@@ -185,8 +185,7 @@ def test_constants_are_the_kernels():
 
 # ---- the stand-alone program under the sanitizers ------------------------------------------------------------------------------------
 def test_driver_runs_clean_under_sanitizers():
-    exe = F.build_sanitized_driver()
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    p = host_build.run_sanitized("fusion_cpu")
     assert p.returncode == 0, p.stdout + p.stderr
     assert "fusion_driver: 0 mismatches" in p.stdout and not p.stderr.strip(), p.stdout + p.stderr
 

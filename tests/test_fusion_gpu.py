@@ -14,6 +14,7 @@ from calibration_amd.fusion import TsdfOptions, TsdfVolume, fuse
 from calibration_amd.registration import CloudIndex, IcpOptions, default_cell_size
 from tests import cloud_ref as R
 from tests import fusion_ref as F
+from tests import host_build
 from tests import test_fusion_cpu as cpu
 from tests.test_fusion_cpu import same
 
@@ -22,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def host():
-    return F.load_host_build()
+    return host_build.load("fusion_cpu")
 
 
 def device_volume(ref):

@@ -12,16 +12,15 @@ from calibration_amd import capi, linear
 from calibration_amd.capi import CbaRansacOptions, dptr, i32ptr, i64ptr
 from calibration_amd.optim import CalibrationBounds
 from tests import hom_ransac_ref as ref
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HRDIR = os.path.join(ROOT, "tests", "hom_ransac_cpu")
 K_TRUE = np.array([820.0, 790.0, 640.0, 360.0, 0.0])
 
 
 @pytest.fixture(scope="module")
 def hr():
-    subprocess.run(["make", "-s", "-C", HRDIR], check=True, stdout=subprocess.DEVNULL)
-    lib = C.CDLL(os.path.join(HRDIR, "_build", "libhrcpu.so"))
+    lib = host_build.load("hom_ransac_cpu")
     P, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
     lib.hr_sample_c.argtypes = [C.c_uint64, C.c_int64, C.c_int64, I]
     lib.hr_degenerate_c.argtypes = [P, P]

@@ -9,6 +9,7 @@ import pytest
 from calibration_amd import capi, linescan
 from calibration_amd.linescan import LaserScanner, LaserScanOptions, laser_points
 from tests import camera_ref as R
+from tests import host_build
 from tests import laser_scan_ref as S
 
 MODELS = [R.PINHOLE, R.SCHEIMPFLUG]
@@ -23,7 +24,7 @@ CENTRE_BAR_PX = 2 * 0.0294
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("laser_scan_cpu")
 
 
 def _check(got, ref, u8):

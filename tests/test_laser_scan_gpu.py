@@ -12,6 +12,7 @@ import pytest
 from calibration_amd import capi, linescan
 from calibration_amd.linescan import LaserScanner, LaserScanOptions, LineScanView, laser_points
 from tests import camera_ref as R
+from tests import host_build
 from tests import laser_scan_ref as S
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ SIZES = [(1, 1), (3, 2), (67, 37), (64, 64), (130, 33), (257, 5)]
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("laser_scan_cpu")
 
 
 @functools.lru_cache(maxsize=None)

@@ -10,10 +10,10 @@ import pytest
 
 from calibration_amd import capi, linescan
 from calibration_amd.capi import CbaLaserPlaneResult, CbaPlaneFitOptions, dptr, i64ptr
+from tests import host_build
 from tests import linescan_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LSDIR = os.path.join(ROOT, "tests", "linescan_cpu")
 
 PINHOLE = np.array([800.0, 790.0, 640.0, 400.0, 0.5, -0.12, 0.03, -0.002, 0.0008, -0.0005])
 SCHEIM = np.r_[PINHOLE, 0.03, -0.02]
@@ -21,8 +21,7 @@ SCHEIM = np.r_[PINHOLE, 0.03, -0.02]
 
 @pytest.fixture(scope="module")
 def lscpu():
-    subprocess.run(["make", "-s", "-C", LSDIR], check=True, stdout=subprocess.DEVNULL)
-    lib = C.CDLL(os.path.join(LSDIR, "_build", "liblscpu.so"))
+    lib = host_build.load("linescan_cpu")
     P = C.POINTER(C.c_double)
     lib.ls_unproject.argtypes = [C.c_int, P, C.c_int, P, C.c_int, P, P, P, P]
     lib.ls_points_from_view.argtypes = [C.c_int, P, C.c_int, P, C.c_int, P, P, P, P, C.c_int, P, P, P]

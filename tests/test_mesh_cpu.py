@@ -6,7 +6,6 @@ zero-area triangles kept), the Python layer's statistics, compaction and PLY fil
 what the library checks before it asks for a device."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import pytest
 import calibration_amd as cal
 from calibration_amd import capi
 from tests import fusion_ref as F
+from tests import host_build
 from tests import mesh_ref as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,7 +31,7 @@ ZERO_SPHERE = (1304, 96)  # triangles, of them with zero area: the sphere centre
 
 @pytest.fixture(scope="module")
 def host():
-    return M.load_host_build()
+    return host_build.load("mesh_cpu")
 
 
 def same(a, b):
@@ -334,8 +334,7 @@ def test_ply_round_trip(tmp_path):
 
 # ---- the stand-alone program under the sanitizers ------------------------------------------------------------------------------------
 def test_driver_runs_clean_under_sanitizers():
-    exe = M.build_sanitized_driver()
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    p = host_build.run_sanitized("mesh_cpu")
     assert p.returncode == 0, p.stdout + p.stderr
     assert "mesh_driver: 0 mismatches" in p.stdout and not p.stderr.strip(), p.stdout + p.stderr
 

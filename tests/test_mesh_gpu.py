@@ -10,6 +10,7 @@ import pytest
 from calibration_amd import capi
 from calibration_amd.fusion import Mesh, TsdfOptions, TsdfVolume, fuse
 from tests import fusion_ref as F
+from tests import host_build
 from tests import mesh_ref as M
 from tests import test_fusion_cpu as fcpu
 from tests import test_mesh_cpu as cpu
@@ -20,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def host():
-    return M.load_host_build()
+    return host_build.load("mesh_cpu")
 
 
 def device_volume(ref):

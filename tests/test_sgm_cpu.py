@@ -3,19 +3,18 @@ independent numpy restatement tests/sgm_ref.py, bitwise; the ranges the rule pro
 restatement and the host build against rendered ground truth; and the argument errors of the C ABI and of the Python layer (raised
 before any device work)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, stereo
+from tests import host_build
 from tests import sgm_ref as G
 
 
 @pytest.fixture(scope="module")
 def host():
-    return G.load_host_build()
+    return host_build.load("sgm_cpu")
 
 
 def test_option_cases_cover_every_value_at_every_size():
@@ -39,9 +38,10 @@ def test_host_build_matches_restatement(host, case):
 
 
 def test_selfcheck_program(host):
-    """the stand-alone program of tests/sgm_cpu (its own main; the form a sanitizer run takes)"""
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sgm_cpu")
-    subprocess.run(["make", "-s", "-C", d, "selfcheck"], check=True, stdout=subprocess.DEVNULL)
+    """the stand-alone program of tests/sgm_cpu (its own main), built under the address and undefined-behaviour sanitizers, runs
+    clean"""
+    r = host_build.run_sanitized("sgm_cpu")
+    assert r.returncode == 0, r.stdout + r.stderr
 
 
 def test_path_costs_leave_8_bits_and_sums_leave_10(host):

@@ -3,20 +3,19 @@ calibration_amd/csrc/stereo_math.hpp (tests/stereo_cpu, compiled here) against t
 tests/stereo_ref.py, the restatement against rendered ground truth, and the argument errors of the C ABI and of the Python layer
 (raised before any device work)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from calibration_amd import capi, stereo
 from tests import camera_ref as R
+from tests import host_build
 from tests import stereo_ref as S
 
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("stereo_cpu")
 
 
 # ---- rectification ------------------------------------------------------------------------------------------------------------------
@@ -138,9 +137,10 @@ def test_host_points_match_restatement(host):
 
 
 def test_selfcheck_program(host):
-    """the stand-alone program of tests/stereo_cpu (its own main; the form a sanitizer run takes)"""
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "stereo_cpu")
-    subprocess.run(["make", "-s", "-C", d, "selfcheck"], check=True, stdout=subprocess.DEVNULL)
+    """the stand-alone program of tests/stereo_cpu (its own main), built under the address and undefined-behaviour sanitizers, runs
+    clean"""
+    r = host_build.run_sanitized("stereo_cpu")
+    assert r.returncode == 0, r.stdout + r.stderr
 
 
 # ---- ground truth, on the restatement ----------------------------------------------------------------------------------------------------

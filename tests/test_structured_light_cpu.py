@@ -5,7 +5,6 @@ against the renderer's exact projector coordinates, and the argument errors of t
 device work)."""
 import ctypes as C
 import math
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import calibration_amd as cal
 from calibration_amd import capi
 from calibration_amd.structured_light import StructuredLightDecoder, StructuredLightOptions
 from tests import camera_ref as R
+from tests import host_build
 from tests import sl_ref as S
 
 PROJECTORS = [(2, 2), (37, 21), (200, 120), (1024, 8)]
@@ -27,7 +27,7 @@ ACCURACY = {(0, 4, 16): 0.0798, (3, 3, 16): 0.0926}
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("sl_cpu")
 
 
 def _lib_options(o):
@@ -251,7 +251,7 @@ def test_python_layer_validates(lib):
 
 
 def test_driver_main_under_sanitizers():
-    """the driver's own main (patterns, decode, every pixel back at its index) as a stand-alone program built with
-    -fsanitize=address,undefined"""
-    r = subprocess.run([S.build_sanitized_driver()], capture_output=True, text=True, timeout=120)
+    """the driver's own main (patterns, decode, every pixel back at its index) as a stand-alone program built under the
+    address and undefined-behaviour sanitizers"""
+    r = host_build.run_sanitized("sl_cpu")
     assert r.returncode == 0 and "0 mismatches" in r.stdout, r.stdout + r.stderr

@@ -11,6 +11,7 @@ from calibration_amd import capi
 from calibration_amd.structured_light import StructuredLightDecoder, StructuredLightOptions
 from calibration_amd.triangulate import triangulate
 from tests import camera_ref as R
+from tests import host_build
 from tests import sl_ref as S
 from tests import triangulate_ref as T
 
@@ -32,7 +33,7 @@ CORNER_ERROR_PX = 0.003329
 
 @pytest.fixture(scope="module")
 def host():
-    return S.load_host_build()
+    return host_build.load("sl_cpu")
 
 
 def _opts(o):

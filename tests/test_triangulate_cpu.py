@@ -9,6 +9,7 @@ import pytest
 from calibration_amd import capi
 from calibration_amd.triangulate import TriangulateOptions, triangulate
 from tests import camera_ref as R
+from tests import host_build
 from tests import triangulate_ref as T
 
 MODELS = [R.PINHOLE, R.SCHEIMPFLUG]
@@ -16,7 +17,7 @@ MODELS = [R.PINHOLE, R.SCHEIMPFLUG]
 
 @pytest.fixture(scope="module")
 def tricpu():
-    return T.load_host_build()
+    return host_build.load("triangulate_cpu")
 
 
 def _rel(a, b):

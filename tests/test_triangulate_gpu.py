@@ -12,6 +12,7 @@ from calibration_amd import camera, capi, optim, rig
 from calibration_amd.geometry import make_pose
 from calibration_amd.triangulate import TriangulateOptions, triangulate
 from tests import camera_ref as R
+from tests import host_build
 from tests import triangulate_ref as T
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ SHAPES = [(1, 2), (63, 3), (64, 5), (65, 16), (257, 3)]  # (points, cameras)
 
 @pytest.fixture(scope="module")
 def tricpu():
-    return T.load_host_build()
+    return host_build.load("triangulate_cpu")
 
 
 def _dev(intrs, invs, poses, uv, o=None):

@@ -6,6 +6,7 @@ K2 . D . G in matrix form, and checked against central differences of camera_ref
 import numpy as np
 
 from tests import camera_ref as R
+from tests.host_build import ptr
 
 OK, NOT_CONVERGED, BEHIND, DEGENERATE, TOO_FEW = range(5)
 LAMBDA0, LAMBDA_MIN, PIVOT_MIN, COST_SLACK_PX = 1e-4, 1e-10, 1e-12, 4e-12
@@ -248,16 +249,6 @@ def status_cases():
 
 
 # ---- the host build of tri_math.hpp (tests/triangulate_cpu) --------------------------------------------------------------------
-def load_host_build():
-    import ctypes as C
-    import os
-    import subprocess
-
-    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "triangulate_cpu")
-    subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-    return C.CDLL(os.path.join(d, "_build", "libtricpu.so"))
-
-
 def host_triangulate(L, model, intrs, invs, poses, uv, o=None):
     """tri_point of the host build over uv [n_cams][n][2] -> the dict triangulate() returns"""
     import ctypes as C
@@ -271,7 +262,6 @@ def host_triangulate(L, model, intrs, invs, poses, uv, o=None):
     n_cams, n = uv.shape[0], uv.shape[1]
     xyz, rms, cov6 = np.empty((n, 3)), np.empty(n), np.empty((n, 6))
     mask, status, lin = np.empty(n, np.uint32), np.empty(n, np.int32), np.empty(n, np.int32)
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    L.tri_points(C.c_int(model), C.c_int(n_cams), p(intrs), C.c_int(0 if invs is None else invs.shape[1]), p(invs), p(poses), C.c_int64(n),
-                 p(uv), C.byref(co), p(xyz), p(rms), p(mask), p(status), p(cov6), p(lin))
+    L.tri_points(C.c_int(model), C.c_int(n_cams), ptr(intrs), C.c_int(0 if invs is None else invs.shape[1]), ptr(invs), ptr(poses), C.c_int64(n),
+                 ptr(uv), C.byref(co), ptr(xyz), ptr(rms), ptr(mask), ptr(status), ptr(cov6), ptr(lin))
     return dict(xyz=xyz, rms=rms, mask=mask, status=status, cov=cov6[:, [[0, 1, 2], [1, 3, 4], [2, 4, 5]]], linearisations=lin)
