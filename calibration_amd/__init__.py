@@ -135,11 +135,14 @@ from .registration import (  # noqa: F401
 )
 from .fusion import (  # noqa: F401
     Mesh,
+    RayCast,
+    RayCastOptions,
     TsdfOptions,
     TsdfVolume,
     depth_from_xyz,
     fuse,
     read_ply,
+    track,
     write_ply,
 )
 from .structured_light import (  # noqa: F401

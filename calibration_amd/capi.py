@@ -219,6 +219,17 @@ class CbaTsdfOptions(C.Structure):
 TSDF_MAX_VOXELS = 1 << 28
 
 
+class CbaTsdfRaycastOptions(C.Structure):
+    """``cba_tsdf_raycast_options`` (calibba.h)."""
+
+    _fields_ = [("step", C.c_double), ("skip", C.c_double), ("near_depth", C.c_double), ("far_depth", C.c_double), ("min_weight", C.c_double)]
+
+
+TSDF_MAX_RAYS = 1 << 26
+TSDF_RAY_MAX_SAMPLES = 65536
+TSDF_RAY_MISS, TSDF_RAY_HIT, TSDF_RAY_BEHIND, TSDF_RAY_NO_RAY = 0, 1, 2, 3
+
+
 class CbaStereoRectifyOptions(C.Structure):
     """``cba_stereo_rectify_options`` (calibba.h)."""
 
@@ -545,6 +556,10 @@ PROTOTYPES = {
     "cba_tsdf_extract_fetch": (C.c_int32, [C.c_void_p, c_double_p, c_double_p]),
     "cba_tsdf_mesh": (C.c_int32, [C.c_void_p, C.c_double, c_int64_p, c_int64_p]),
     "cba_tsdf_mesh_fetch": (C.c_int32, [C.c_void_p, c_int32_p]),
+    "cba_tsdf_raycast_options_default": (None, [C.POINTER(CbaTsdfRaycastOptions)]),
+    "cba_tsdf_raycast": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.POINTER(CbaTsdfRaycastOptions)]),
+    "cba_tsdf_raycast_fetch": (C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_uint8_p, c_double_p]),
     "cba_tsdf_volume_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (

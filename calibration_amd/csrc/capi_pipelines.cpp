@@ -1183,6 +1183,61 @@ cba_status cba_tsdf_mesh_fetch(cba_tsdf_volume* h, int32_t* triangles) {
     });
 }
 
+void cba_tsdf_raycast_options_default(cba_tsdf_raycast_options* o) {
+    if (!o) return;
+    o->step = 0.0;
+    o->skip = 0.5;
+    o->near_depth = 0.0;
+    o->far_depth = std::numeric_limits<double>::infinity();
+    o->min_weight = 1.0;
+}
+
+// wave_w: the width of a wavefront's pixel block (8; the experiment builds compare 64)
+static cba_status tsdf_raycast_impl(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_views, int32_t height, int32_t width,
+                                    const double* poses, const cba_tsdf_raycast_options* opts, int wave_w, double* stage_ms) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        check_camera(camera_model, intr, 0, nullptr);
+        if (intr[0] == 0.0 || intr[1] == 0.0) throw std::invalid_argument("fx and fy must not be 0");
+        if (n_views < 0) throw std::invalid_argument("n_views must be >= 0");
+        check_sides(width, height);
+        if (static_cast<int64_t>(n_views) * height * width > CBA_TSDF_MAX_RAYS) throw std::invalid_argument("n_views height width must be <= 2^26");
+        cba_tsdf_raycast_options o;
+        cba_tsdf_raycast_options_default(&o);
+        if (opts) o = *opts;
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        const double vs = tsdf_volume_voxel_size(v);
+        if (o.step != 0.0 && !(std::isfinite(o.step) && o.step >= vs / 16.0)) throw std::invalid_argument("step must be 0 or finite and >= voxel_size / 16");
+        if (!(o.skip >= 0.0 && o.skip <= 1.0)) throw std::invalid_argument("skip must be in [0, 1]");
+        if (!(o.near_depth >= 0.0) || !std::isfinite(o.near_depth)) throw std::invalid_argument("near_depth must be finite and >= 0");
+        if (!(o.far_depth > o.near_depth)) throw std::invalid_argument("far_depth must be > near_depth");
+        if (!(o.min_weight >= 1.0)) throw std::invalid_argument("min_weight must be >= 1");
+        if (n_views == 0) return;
+        if (!poses) throw std::invalid_argument("null argument");
+        for (int32_t m = 0; m < n_views; ++m) {
+#pragma clang fp contract(off)
+            const double* q = poses + 7 * static_cast<size_t>(m);
+            const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+            if (!(nq > 0.0) || !std::isfinite(nq)) throw std::invalid_argument("poses needs a non-zero finite quaternion");
+        }
+        tsdf_volume_raycast(v, camera_model, intr, n_views, height, width, poses, o, wave_w, stage_ms);
+    });
+}
+
+cba_status cba_tsdf_raycast(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_views, int32_t height, int32_t width,
+                            const double* poses, const cba_tsdf_raycast_options* opts) {
+    return tsdf_raycast_impl(h, camera_model, intr, n_views, height, width, poses, opts, 8, nullptr);
+}
+
+cba_status cba_tsdf_raycast_fetch(cba_tsdf_volume* h, double* depth, double* xyz, double* normals, uint8_t* status, double* rays) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (tsdf_volume_ray_views(v) < 0) throw std::invalid_argument("no ray cast has run on this volume");
+        if (depth || xyz || normals || status || rays) tsdf_volume_raycast_fetch(v, depth, xyz, normals, status, rays);
+    });
+}
+
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h) { tsdf_volume_destroy(reinterpret_cast<TsdfVolume*>(h)); }
 
 #ifdef CBA_EXPERIMENTS
@@ -1201,6 +1256,13 @@ __attribute__((visibility("default"))) cba_status cba_tsdf_extract_timed(cba_tsd
 __attribute__((visibility("default"))) cba_status cba_tsdf_mesh_timed(cba_tsdf_volume* h, double min_weight, int64_t* n_points,
                                                                       int64_t* n_triangles, double* stage_ms) {
     return timed(stage_ms, [&] { return tsdf_mesh_impl(h, min_weight, n_points, n_triangles, stage_ms); });
+}
+// stage_ms [2] = upload and the rays table, the cast; wave_w: 8 or 64 (tools/bench_raycast.py compares the two pixel blocks)
+__attribute__((visibility("default"))) cba_status cba_tsdf_raycast_timed(cba_tsdf_volume* h, int32_t camera_model, const double* intr,
+                                                                         int32_t n_views, int32_t height, int32_t width, const double* poses,
+                                                                         const cba_tsdf_raycast_options* opts, int32_t wave_w, double* stage_ms) {
+    if (wave_w != 8 && wave_w != 64) return CBA_ERR_INVALID_ARGUMENT;
+    return timed(stage_ms, [&] { return tsdf_raycast_impl(h, camera_model, intr, n_views, height, width, poses, opts, wave_w, stage_ms); });
 }
 #endif
 

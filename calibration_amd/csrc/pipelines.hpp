@@ -128,6 +128,7 @@ void cloud_index_destroy(CloudIndex* h) noexcept;
 struct TsdfVolume;
 TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, const cba_tsdf_options& o, int device);
 int64_t tsdf_volume_points(const TsdfVolume* h);
+double tsdf_volume_voxel_size(const TsdfVolume* h);
 void tsdf_volume_reset(TsdfVolume* h);
 void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
                            double* stage_ms);
@@ -138,6 +139,11 @@ void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals);
 int64_t tsdf_volume_triangles(const TsdfVolume* h);
 void tsdf_volume_mesh(TsdfVolume* h, double min_weight, int64_t* n_points, int64_t* n_triangles, double* stage_ms);
 void tsdf_volume_mesh_fetch(TsdfVolume* h, int32_t* triangles);
+// the ray cast: the views of the last one (-1: none yet); stage_ms [2] optional: upload and the rays table, the cast
+int64_t tsdf_volume_ray_views(const TsdfVolume* h);
+void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_views, int H, int W, const double* c_T_v,
+                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms);
+void tsdf_volume_raycast_fetch(TsdfVolume* h, double* depth, double* xyz, double* normals, uint8_t* status, double* rays);
 void tsdf_volume_destroy(TsdfVolume* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download

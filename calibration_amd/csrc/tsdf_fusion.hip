@@ -1,5 +1,5 @@
-// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, tsdf_mesh_math.hpp, calibba.h: cba_tsdf_volume, cba_tsdf_integrate,
-// cba_tsdf_extract, cba_tsdf_mesh).
+// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, tsdf_mesh_math.hpp, tsdf_ray_math.hpp, calibba.h: cba_tsdf_volume,
+// cba_tsdf_integrate, cba_tsdf_extract, cba_tsdf_mesh, cba_tsdf_raycast).
 //   k_tsdf_fill         D = 1, W = 0 in every stored voxel (create, reset).
 //   k_tsdf_integrate    one launch per call.  A lane owns two adjacent x voxels, one aligned 16-byte {D, W, D, W} word that it loads
 //                       once, keeps in registers while it walks the call's maps in order, and stores once: the whole word when both
@@ -20,6 +20,13 @@
 //                       of a wave loads its own): four 8-byte loads per cell.  The table of triangles per case (2 KiB, generated from
 //                       the rule at compile time) is staged in LDS.  Ballots of the three bits of a lane's triangle count give the
 //                       wave's prefix; count, scan and place as above.  A triangle is three lookups in the records.
+//   k_tsdf_rays         the rays table of a ray cast: one lane per pixel, ls_unproject as it is, one 16-byte store.
+//   k_tsdf_raycast      one launch per call over views x pixel tiles.  A wavefront owns a compact 8 x 8 block of pixels of one view, so its
+//                       64 rays walk neighbouring cells and share cache lines; the view is a table indexed by a wave-uniform value
+//                       alone.  A lane marches its ray by tsdf_ray_pixel: per sample four rows of two {D, W} pairs, one 16-byte load
+//                       per row where the cell's x is even, two 8-byte loads where it is odd; every decision in fp64.  The loop has
+//                       the rule's exits and no other (hit, behind, past the range, no progress, the sample cap).  No LDS, no
+//                       atomics, no scratch; a lane writes its own pixel only.
 // The handle owns one stream and every buffer; a call grows a buffer that is too small and allocates nothing else; every call ends
 // with the stream synchronised.  No float atomics, and no integer ones either.
 #include <memory>
@@ -30,6 +37,7 @@
 #include "scan_tiles.hpp"
 #include "tsdf_math.hpp"
 #include "tsdf_mesh_math.hpp"
+#include "tsdf_ray_math.hpp"
 
 namespace cba {
 
@@ -213,6 +221,51 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_mesh(TsdfGrid g, const floa
     if (!PLACE && threadIdx.x == 0) count[blockIdx.x] = base;
 }
 
+constexpr int TSDF_RAY_BLOCK = 256;  // four wavefronts, each with a block of pixels of its own
+constexpr int TSDF_RAY_WAVE_W = 8;   // a wavefront's pixels are TSDF_RAY_WAVE_W x (64 / TSDF_RAY_WAVE_W)
+
+// rays [H][W][2] <- ls_unproject(c, col, row)
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_rays(int H, int W, double* __restrict__ rays, LsCamera c) {
+    const int64_t n = static_cast<int64_t>(H) * W;
+    for (int64_t l = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x; l < n; l += static_cast<int64_t>(gridDim.x) * TSDF_BLOCK) {
+        const int64_t row = l / W;
+        double2 o;
+        ls_unproject(c, static_cast<double>(l - row * W), static_cast<double>(row), &o.x, &o.y);
+        reinterpret_cast<double2*>(rays)[l] = o;
+    }
+}
+
+// BW: the width of a wavefront's pixel block (8: compact; 64: one row segment, instantiated by the experiment builds for the comparison)
+template <int BW>
+__global__ __launch_bounds__(TSDF_RAY_BLOCK) void k_tsdf_raycast(TsdfGrid g, const float* __restrict__ vol, const TsdfRayView* __restrict__ views,
+                                                                 const double* __restrict__ rays, int n_views, int H, int W, TsdfRayRule r,
+                                                                 double* __restrict__ depth, double* __restrict__ xyz, double* __restrict__ nrm,
+                                                                 uint8_t* __restrict__ status) {
+    constexpr int BH = 64 / BW;
+    const int tiles_x = (W + BW - 1) / BW, tiles_y = (H + BH - 1) / BH;
+    const int64_t tiles = static_cast<int64_t>(tiles_x) * tiles_y;
+    const int64_t wave = blockIdx.x * static_cast<int64_t>(TSDF_RAY_BLOCK / 64) + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    if (wave >= tiles * n_views) return;
+    const int view = static_cast<int>(wave / tiles);  // wave-uniform: the view is read with scalar loads
+    const int tile = static_cast<int>(wave - view * tiles);
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int lane = threadIdx.x & 63;
+    const int col = tx * BW + lane % BW, row = ty * BH + lane / BW;
+    if (col >= W || row >= H) return;
+    const int64_t px = static_cast<int64_t>(row) * W + col;
+    const double2 ray = reinterpret_cast<const double2*>(rays)[px];
+    TsdfRayOut o;
+    tsdf_ray_pixel(vol, g, views[view], r, ray.x, ray.y, &o);
+    const int64_t at = static_cast<int64_t>(view) * H * W + px;
+    depth[at] = o.depth;  // NaN unless the ray hit, and then NaN times the ray is NaN
+    xyz[3 * at] = ray.x * o.depth;
+    xyz[3 * at + 1] = ray.y * o.depth;
+    xyz[3 * at + 2] = o.depth;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) nrm[3 * at + c] = o.nrm[c];
+    status[at] = static_cast<uint8_t>(o.status);
+}
+
 struct TsdfVolume : DeviceHandle {
     using DeviceHandle::DeviceHandle;
     TsdfGrid g{};
@@ -231,6 +284,13 @@ struct TsdfVolume : DeviceHandle {
     DevBuf<int32_t> tcount;      // [n_tiles + 1] triangles per tile, from the first mesh call on
     DevBuf<int32_t> tri;         // [n_triangles][3] of the mesh
     PinnedBuf<int32_t> total_h;
+    // the last ray cast: ray_views < 0: none yet
+    int64_t ray_views = -1;
+    int ray_H = 0, ray_W = 0;
+    DevBuf<TsdfRayView> views;       // [ray_views]
+    DevBuf<double> rays;             // [ray_H][ray_W][2]
+    DevBuf<double> rdepth, rxyz, rnrm;  // [ray_views][ray_H][ray_W] ([3])
+    DevBuf<uint8_t> rstatus;
 };
 static_assert(!std::is_copy_constructible_v<TsdfVolume> && !std::is_copy_assignable_v<TsdfVolume>, "a handle owns its stream and buffers");
 
@@ -268,6 +328,7 @@ void tsdf_volume_reset(TsdfVolume* h) {
 }
 
 int64_t tsdf_volume_points(const TsdfVolume* h) { return h->n_points; }
+double tsdf_volume_voxel_size(const TsdfVolume* h) { return h->g.vs; }
 int64_t tsdf_volume_triangles(const TsdfVolume* h) { return h->n_triangles; }
 
 // stage_ms [2] optional: upload, kernel
@@ -420,6 +481,66 @@ void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals) {
     const size_t n = 3 * static_cast<size_t>(h->n_points);
     h->xyz.download(xyz, n, s);
     if (normals) h->nrm.download(normals, n, s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+int64_t tsdf_volume_ray_views(const TsdfVolume* h) { return h->ray_views; }
+
+// The ray cast reads the volume and writes only its own buffers: the extract's points and the mesh stay as they are.
+// wave_w: TSDF_RAY_WAVE_W; the experiment builds also take 64 for the comparison.  stage_ms [2] optional: upload and the rays table, the cast
+void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_views, int H, int W, const double* c_T_v,
+                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms) {
+    const hipStream_t s = h->begin();
+    LsCamera cam;
+    ls_fill_camera(model, intr, 0, nullptr, &cam);
+    std::vector<TsdfRayView> views(static_cast<size_t>(n_views));
+    for (int m = 0; m < n_views; ++m) tsdf_ray_view(c_T_v + 7 * static_cast<size_t>(m), &views[m]);
+    TsdfRayRule r;
+    r.step = o.step > 0.0 ? o.step : 0.5 * h->g.vs;
+    r.skip = o.skip; r.near_depth = o.near_depth; r.far_depth = o.far_depth; r.min_weight = o.min_weight; r.trunc = h->o.truncation;
+    const size_t plane = static_cast<size_t>(H) * W, n_px = plane * n_views;
+    StageTimer<3> tm(s, stage_ms != nullptr);
+    h->ray_views = -1;  // a buffer that grows loses its contents: an allocation failure leaves the handle without a ray cast
+    h->views.ensure(static_cast<size_t>(n_views));
+    h->rays.ensure(2 * plane);
+    h->rdepth.ensure(n_px);
+    h->rxyz.ensure(3 * n_px);
+    h->rnrm.ensure(3 * n_px);
+    h->rstatus.ensure(n_px);
+    tm.mark(0);
+    h->views.upload(views.data(), static_cast<size_t>(n_views), s);
+    hipLaunchKernelGGL(k_tsdf_rays, dim3(launch_grid(static_cast<int64_t>(plane), TSDF_BLOCK, TSDF_GRID)), dim3(TSDF_BLOCK), 0, s, H, W, h->rays.p, cam);
+    CBA_HIP(hipGetLastError());
+    tm.mark(1);
+    const int wave_h = 64 / wave_w;
+    const int64_t waves = static_cast<int64_t>((W + wave_w - 1) / wave_w) * ((H + wave_h - 1) / wave_h) * n_views;
+    const dim3 grid(static_cast<unsigned>((waves + TSDF_RAY_BLOCK / 64 - 1) / (TSDF_RAY_BLOCK / 64)));
+#ifdef CBA_EXPERIMENTS
+    if (wave_w == 64)
+        hipLaunchKernelGGL(k_tsdf_raycast<64>, grid, dim3(TSDF_RAY_BLOCK), 0, s, h->g, h->vol.p, h->views.p, h->rays.p, n_views, H, W, r, h->rdepth.p,
+                           h->rxyz.p, h->rnrm.p, h->rstatus.p);
+    else
+#endif
+        hipLaunchKernelGGL(k_tsdf_raycast<TSDF_RAY_WAVE_W>, grid, dim3(TSDF_RAY_BLOCK), 0, s, h->g, h->vol.p, h->views.p, h->rays.p, n_views, H, W, r,
+                           h->rdepth.p, h->rxyz.p, h->rnrm.p, h->rstatus.p);
+    CBA_HIP(hipGetLastError());
+    tm.mark(2);
+    CBA_HIP(hipStreamSynchronize(s));  // views goes out of scope
+    h->ray_views = n_views;
+    h->ray_H = H;
+    h->ray_W = W;
+    tm.report(stage_ms);
+}
+
+// each pointer may be NULL
+void tsdf_volume_raycast_fetch(TsdfVolume* h, double* depth, double* xyz, double* normals, uint8_t* status, double* rays) {
+    const hipStream_t s = h->begin();
+    const size_t plane = static_cast<size_t>(h->ray_H) * h->ray_W, n = plane * static_cast<size_t>(h->ray_views);
+    if (depth) h->rdepth.download(depth, n, s);
+    if (xyz) h->rxyz.download(xyz, 3 * n, s);
+    if (normals) h->rnrm.download(normals, 3 * n, s);
+    if (status) h->rstatus.download(status, n, s);
+    if (rays) h->rays.download(rays, 2 * plane, s);
     CBA_HIP(hipStreamSynchronize(s));
 }
 

@@ -1,7 +1,8 @@
-"""Scan fusion on the GPU (``cba_tsdf_volume``, ``cba_tsdf_integrate``, ``cba_tsdf_extract``, ``cba_tsdf_mesh``): depth maps of one
-object, each with its pose, are merged into a truncated signed distance volume, and the surface is read off it as points with normals
-on the lattice edges, and as triangles over those points, by the rules calibba.h states.  The reference has no counterpart.  The mesh
-statistics and the PLY files are host work in numpy.
+"""Scan fusion on the GPU (``cba_tsdf_volume``, ``cba_tsdf_integrate``, ``cba_tsdf_extract``, ``cba_tsdf_mesh``, ``cba_tsdf_raycast``):
+depth maps of one object, each with its pose, are merged into a truncated signed distance volume, and the surface is read off it as
+points with normals on the lattice edges, as triangles over those points, and as what a camera at a given pose sees of it (depth,
+points and normals per pixel), by the rules calibba.h states.  ``track`` registers a new scan against the model's ray cast.  The
+reference has no counterpart.  The mesh statistics, the PLY files and the clouds of a ray cast are host work in numpy.
 """
 from __future__ import annotations
 
@@ -12,7 +13,8 @@ from typing import Optional, Tuple, Union
 import numpy as np
 
 from . import capi
-from .capi import CbaTsdfOptions, dptr, i32ptr, i64ptr
+from .capi import CbaTsdfOptions, CbaTsdfRaycastOptions, dptr, i32ptr, i64ptr, u8ptr
+from .geometry import quat_to_rotmat
 
 
 def _fptr(a: Optional[np.ndarray]):
@@ -42,6 +44,60 @@ def depth_from_xyz(xyz) -> np.ndarray:
     if p.ndim < 3 or p.shape[-1] != 3:
         raise ValueError(f"xyz must be [height][width][3] or [n_maps][height][width][3], got {p.shape}")
     return np.where(np.isfinite(p).all(axis=-1), p[..., 2], np.nan)
+
+
+@dataclass
+class RayCastOptions:
+    """``cba_tsdf_raycast_options``: the march's step (0: half a voxel; at least voxel_size / 16), the share of F times the truncation
+    that a valid sample may advance by (in [0, 1]; 0: fixed steps), the depth range of the rays, and the weight all eight voxels of a
+    sampled cell must have."""
+    step: float = 0.0
+    skip: float = 0.5
+    near_depth: float = 0.0
+    far_depth: float = np.inf
+    min_weight: float = 1.0
+
+    def _c(self) -> CbaTsdfRaycastOptions:
+        return CbaTsdfRaycastOptions(float(self.step), float(self.skip), float(self.near_depth), float(self.far_depth), float(self.min_weight))
+
+
+MISS, HIT, BEHIND, NO_RAY = capi.TSDF_RAY_MISS, capi.TSDF_RAY_HIT, capi.TSDF_RAY_BEHIND, capi.TSDF_RAY_NO_RAY
+
+
+def _rigid(pose7) -> Tuple[np.ndarray, np.ndarray]:
+    """R, t of a rigid pose7 (the quaternion normalised)"""
+    p = np.asarray(pose7, dtype=np.float64).reshape(7)
+    return quat_to_rotmat(p[:4] / np.linalg.norm(p[:4])), p[4:]
+
+
+def pose_inverse(pose7) -> np.ndarray:
+    """The inverse of a rigid pose7."""
+    p = np.asarray(pose7, dtype=np.float64).reshape(7)
+    q = p[:4] / np.linalg.norm(p[:4]) * np.array([1.0, -1.0, -1.0, -1.0])
+    return np.concatenate([q, -(quat_to_rotmat(q) @ p[4:])])
+
+
+@dataclass
+class RayCast:
+    """What cameras at n_views poses see of a volume: depth [n_views][height][width], xyz and normals [..][3] in each camera's frame
+    (organised maps, NaN where a pixel is no hit; a hit's normal is NaN where there is none), status uint8 [..] (MISS, HIT, BEHIND,
+    NO_RAY) and the rays table [height][width][2]."""
+    depth: np.ndarray
+    xyz: np.ndarray
+    normals: np.ndarray
+    status: np.ndarray
+    rays: np.ndarray
+
+    @property
+    def hits(self) -> np.ndarray:
+        return self.status == HIT
+
+    def cloud(self, view: int, pose7) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (xyz [n][3], normals [n][3]) of view's hits in the volume frame, in row-major pixel order; pose7: that view's rigid pose,
+        volume frame -> camera"""
+        R, t = _rigid(pose7)
+        m = self.hits[view]
+        return (self.xyz[view][m] - t) @ R, self.normals[view][m] @ R
 
 
 @dataclass
@@ -223,6 +279,25 @@ class TsdfVolume(capi.Handle):
         out = Mesh(xyz, normals, tri)
         return out.compact() if compact else out
 
+    def raycast(self, camera_model: int, intr, poses, shape: Tuple[int, int], opts: Optional[RayCastOptions] = None) -> RayCast:
+        """The model as cameras at poses [n_views][7] (volume frame -> camera) see it, in views of shape = (height, width)."""
+        h = self._require_open("the volume is closed")
+        H, W = (int(v) for v in shape)
+        pose = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 7))
+        k = np.ascontiguousarray(np.asarray(intr, dtype=np.float64).reshape(-1))
+        if k.size != (12 if camera_model == 1 else 10):
+            raise ValueError(f"intr has {k.size} entries")
+        co = (opts or RayCastOptions())._c()
+        capi.check(self._lib, self._lib.cba_tsdf_raycast(h, int(camera_model), dptr(k), pose.shape[0], H, W, dptr(pose), C.byref(co)))
+        n = pose.shape[0]
+        out = RayCast(np.empty((n, H, W)), np.empty((n, H, W, 3)), np.empty((n, H, W, 3)), np.empty((n, H, W), np.uint8), np.empty((H, W, 2)))
+        if n > 0:
+            capi.check(self._lib, self._lib.cba_tsdf_raycast_fetch(h, dptr(out.depth), dptr(out.xyz), dptr(out.normals), u8ptr(out.status),
+                                                                   dptr(out.rays)))
+        else:
+            out.rays[:] = np.nan  # no work was done: there is no table
+        return out
+
     def reset(self) -> None:
         capi.check(self._lib, self._lib.cba_tsdf_reset(self._require_open("the volume is closed")))
 
@@ -233,3 +308,35 @@ def fuse(shape, origin, opts: TsdfOptions, camera_model: int, intr, poses, depth
     with TsdfVolume(shape, origin, opts, device) as vol:
         vol.integrate(camera_model, intr, poses, depth=depth, xyz=xyz)
         return vol.mesh(min_weight) if mesh else vol.extract(min_weight)
+
+
+def track(vol: TsdfVolume, camera_model: int, intr, init_pose7, depth=None, xyz=None, icp=None, opts: Optional[RayCastOptions] = None):
+    """Frame-to-model registration of one new scan (a depth map [height][width], or an organised map ``xyz`` in the camera's frame):
+    the model is ray cast at init_pose7 (volume frame -> camera), a ``CloudIndex`` is put over that view's hits in the volume frame,
+    and the scan's points are registered onto it from the inverse of init_pose7.  icp: ``IcpOptions`` (default: point to plane within
+    two voxels).  -> (the refined pose7 volume frame -> camera, the ``IcpResult``, whose pose7 maps the camera to the volume frame)."""
+    from .registration import CloudIndex, IcpOptions, default_cell_size
+
+    if (depth is None) == (xyz is None):
+        raise ValueError("give depth or xyz, one of them")
+    init = np.asarray(init_pose7, dtype=np.float64).reshape(7)
+    if depth is not None:
+        d = np.asarray(depth, dtype=np.float64)
+        if d.ndim != 2:
+            raise ValueError(f"depth must be [height][width], got {d.shape}")
+        shape = d.shape
+    else:
+        pts = np.asarray(xyz, dtype=np.float64)
+        if pts.ndim != 3 or pts.shape[-1] != 3:
+            raise ValueError(f"xyz must be [height][width][3], got {pts.shape}")
+        shape = pts.shape[:2]
+    icp = icp or IcpOptions(2.0 * vol.opts.voxel_size)
+    cast = vol.raycast(camera_model, intr, init[None], shape, opts)
+    if depth is not None:
+        pts = np.concatenate([cast.rays * d[..., None], d[..., None]], axis=-1)  # the scan's points on the model's own rays
+    src = pts.reshape(-1, 3)
+    src = src[np.isfinite(src).all(axis=1)]
+    target, normals = cast.cloud(0, init)
+    with CloudIndex(target, normals, default_cell_size(icp.max_distance)) as index:
+        res = index.register([src], icp, init_pose7=pose_inverse(init)[None])[0]
+    return pose_inverse(res.pose7), res

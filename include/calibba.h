@@ -1209,6 +1209,60 @@ void cba_cloud_index_destroy(cba_cloud_index* h);
  *    against negative neighbours gives t = 0 and zero-area triangles (a sphere of radius 6 voxels centred on a lattice point: 96
  *    of its 1304); they are kept.  Points of the extract that no live cell touches stay in the point list, unreferenced.
  *
+ * 5. cba_tsdf_raycast(h, camera_model, intr, n_views, height, width, poses [n_views][7], opts): what a camera at each pose sees of
+ *    the model: depth, camera-frame points and normals per pixel, organised as the front ends write their maps.  Only + - * /
+ *    sqrt floor and comparisons are used, each rounded once in the order written; min(a, b) is a < b ? a : b and max(a, b) is
+ *    a > b ? a : b.
+ *
+ *    Options {step, skip, near_depth, far_depth, min_weight}, defaults {0, 0.5, 0, +inf, 1}.  step_eff = step > 0 ? step :
+ *    0.5 voxel_size.  Argument errors: step not 0 and not in [voxel_size / 16, +inf), or non-finite; skip not in [0, 1];
+ *    near_depth not >= 0 or non-finite; far_depth not > near_depth (NaN included); min_weight not >= 1.  The lower bound on step
+ *    and the guards of the march are what make every ray end.
+ *
+ *    Rays.  Pixel (col, row) of a height x width view has the ray (x, y) = cba_camera_unproject's arithmetic at u = col, v = row
+ *    (the iterative undistortion; no inverse coefficients).  It is computed once per pixel and call and kept as a table
+ *    rays [height][width][2] that can be fetched; the unprojection is not reproducible to the bit between compilers, so
+ *    everything below is a function of the table's stored values.  A pixel whose x or y is non-finite has status 3 (NO_RAY).
+ *
+ *    View.  R and t of a pose as rule 2 takes them (volume frame -> camera).  Centre c_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2);
+ *    direction d_r = (R_0r x + R_1r y) + R_2r.  The point at parameter z is p_r = c_r + z d_r (the product rounded, then the sum):
+ *    z is the camera-frame depth.
+ *
+ *    Range.  z0 = near_depth, z1 = far_depth.  For each axis a with lo = o_a and hi = o_a + (n_a - 1) vs (rule 1's position): if
+ *    d_a == 0 the ray is a miss when c_a < lo or c_a > hi, and otherwise the axis sets no bound; else ta = (lo - c_a) / d_a,
+ *    tb = (hi - c_a) / d_a, z0 = max(z0, min(ta, tb)), z1 = min(z1, max(ta, tb)).  The ray is a miss unless z0 <= z1 (false for NaN).
+ *
+ *    Sample at z.  g_a = (p_a - o_a) / vs.  The sample is invalid unless 0 <= g_a <= n_a - 1 for every axis (false for NaN; decided
+ *    before any conversion to an integer).  i_a = min(floor(g_a), n_a - 2), f_a = g_a - i_a.  The sample is invalid unless all eight
+ *    voxels of cell i have W >= min_weight.  F is the trilinear value with lerp(a, b, t) = a + t (b - a): four lerps along x for
+ *    (y, z) = (0,0), (1,0), (0,1), (1,1), two along y, one along z.  No address outside the stored volume is formed.
+ *
+ *    March.  z = z0, "previous" = invalid, count = 0.  Loop:
+ *      1. Sample at z; count += 1.
+ *      2. If the sample is valid and F < 0: previous valid with F_prev >= 0 -> HIT (1) with
+ *         z_hit = z_prev + (z - z_prev) (F_prev / (F_prev - F)), end; previous invalid -> BEHIND (2), end (the ray enters observed
+ *         space inside a surface).
+ *      3. If the sample is valid, F >= 0, and the previous sample was valid with F_prev < 0 -> BEHIND, end.
+ *      4. adv = step_eff for an invalid sample, max(step_eff, (skip F) truncation) otherwise (step_eff when that product is NaN).
+ *      5. z_next = z + adv.
+ *      6. The ray ends as MISS (0) when not z_next <= z1, or not z_next > z (no progress at a large z), or
+ *         count == CBA_TSDF_RAY_MAX_SAMPLES.
+ *      7. The current sample becomes "previous"; z = z_next.
+ *    "Negative" is F < 0 throughout: -0.0 and 0 count as positive, as in rule 3.
+ *
+ *    Outputs of a hit.  depth = z_hit; xyz = (x z_hit, y z_hit, z_hit) in the camera frame.  Normal: F sampled at p_hit +- vs e_a
+ *    for the three axes (six samples by the rule above, the same min_weight); n_a = F(+) - F(-); len = sqrt((n_0 n_0 + n_1 n_1) +
+ *    n_2 n_2).  If any of the six is invalid, or len is not > 0 or not finite, the normal is NaN in all three components and the
+ *    hit stays a hit.  Otherwise m = n / len by three divisions and the camera-frame normal is (R_r0 m_0 + R_r1 m_1) + R_r2 m_2:
+ *    it points into positive D, as rule 3's normals do.  Every pixel that is no hit has NaN in depth, xyz and normals.
+ *
+ *    Every output is a function of the volume, the rays table, the pose and the options alone: not of the launch, the batch (n
+ *    views in one call give the bits of n calls), or what ran before.  The results stay in the handle until
+ *    cba_tsdf_raycast_fetch(h, depth [n_views][height][width], xyz [..][3], normals [..][3], status uint8 [..],
+ *    rays [height][width][2]) copies them out; each pointer may be NULL.  The ray cast reads the volume and writes only its own
+ *    buffers: it does not invalidate the handle's extract or mesh, and a later integrate, upload, reset, extract or mesh does not
+ *    invalidate its results.  n_views == 0 is no work and leaves earlier results as they are, as does every argument error.
+ *
  * cba_tsdf_fetch copies the dense [nz][ny][nx] planes of D and W out and cba_tsdf_upload writes them (a saved volume restored; the
  * values are taken as they are); either pointer may be NULL.  cba_tsdf_reset restores D = 1 and W = 0.  The handle owns one stream
  * and all of its device buffers; every call ends synchronised.  Float atomics are used nowhere.
@@ -1218,8 +1272,16 @@ void cba_cloud_index_destroy(cba_cloud_index* h);
  * finite, voxel_size or truncation not > 0; max_weight outside [1, 2^24] or not an integer value; max_depth not > 0; an unknown
  * camera model, fx or fy equal to 0; n_maps < 0; width or height outside [1, CBA_IMAGE_MAX_SIDE]; a zero or non-finite quaternion;
  * min_weight not >= 1; cba_tsdf_extract_fetch before any extract; NULL n_triangles; NULL triangles for n_triangles > 0;
- * cba_tsdf_mesh_fetch without a valid mesh.  n_maps == 0 is no work; create without a device -> CBA_ERR_NO_DEVICE. */
+ * cba_tsdf_mesh_fetch without a valid mesh; for cba_tsdf_raycast the camera, side and pose errors of cba_tsdf_integrate, n_views < 0,
+ * n_views height width > CBA_TSDF_MAX_RAYS and rule 5's option errors; cba_tsdf_raycast_fetch before any ray cast.  n_maps == 0 is
+ * no work; create without a device -> CBA_ERR_NO_DEVICE. */
 #define CBA_TSDF_MAX_VOXELS (1 << 28)
+#define CBA_TSDF_MAX_RAYS (1 << 26)
+#define CBA_TSDF_RAY_MAX_SAMPLES 65536
+#define CBA_TSDF_RAY_MISS 0
+#define CBA_TSDF_RAY_HIT 1
+#define CBA_TSDF_RAY_BEHIND 2
+#define CBA_TSDF_RAY_NO_RAY 3
 typedef struct cba_tsdf_options {
     double voxel_size; /* lattice spacing (no default: the caller sets it) */
     double truncation; /* the band, in the volume's unit (no default: the caller sets it; a few voxel sizes) */
@@ -1227,7 +1289,7 @@ typedef struct cba_tsdf_options {
     double max_depth;  /* depths beyond it are not used (default +inf) */
 } cba_tsdf_options;
 void cba_tsdf_options_default(cba_tsdf_options* o); /* voxel_size and truncation are left at 0: the caller sets them */
-typedef struct cba_tsdf_volume cba_tsdf_volume; /* opaque: the volume, the buffers of its calls, the last extract's points, the mesh, one stream */
+typedef struct cba_tsdf_volume cba_tsdf_volume; /* opaque: the volume, the buffers of its calls, the last extract's points, the mesh, the last ray cast, one stream */
 cba_status cba_tsdf_volume_create(int32_t nx, int32_t ny, int32_t nz, const double* origin /*[3]*/, const cba_tsdf_options* opts,
                                   int32_t device, cba_tsdf_volume** out);
 cba_status cba_tsdf_integrate(cba_tsdf_volume* h, int32_t camera_model, const double* intr /*[10 | 12]*/, int32_t n_maps, int32_t height,
@@ -1239,6 +1301,18 @@ cba_status cba_tsdf_extract(cba_tsdf_volume* h, double min_weight, int64_t* n_po
 cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz /*[n_points][3]*/, double* normals /*[n_points][3] or NULL*/);
 cba_status cba_tsdf_mesh(cba_tsdf_volume* h, double min_weight, int64_t* n_points, int64_t* n_triangles);
 cba_status cba_tsdf_mesh_fetch(cba_tsdf_volume* h, int32_t* triangles /*[n_triangles][3]*/);
+typedef struct cba_tsdf_raycast_options {
+    double step;       /* the march's step; 0: half a voxel (default 0) */
+    double skip;       /* the share of F truncation a valid sample may advance by, in [0, 1] (default 0.5) */
+    double near_depth; /* rays start here (default 0) */
+    double far_depth;  /* and end here (default +inf) */
+    double min_weight; /* a sample needs W >= min_weight in all eight voxels of its cell (default 1) */
+} cba_tsdf_raycast_options;
+void cba_tsdf_raycast_options_default(cba_tsdf_raycast_options* o);
+cba_status cba_tsdf_raycast(cba_tsdf_volume* h, int32_t camera_model, const double* intr /*[10 | 12]*/, int32_t n_views, int32_t height,
+                            int32_t width, const double* poses /*[n_views][7]*/, const cba_tsdf_raycast_options* opts /*NULL: defaults*/);
+cba_status cba_tsdf_raycast_fetch(cba_tsdf_volume* h, double* depth /*[n_views][height][width]*/, double* xyz /*[..][3]*/,
+                                  double* normals /*[..][3]*/, uint8_t* status /*[..]*/, double* rays /*[height][width][2]*/);
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h);
 
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
