@@ -127,9 +127,14 @@ from .triangulate import (  # noqa: F401
     triangulate,
 )
 from .registration import (  # noqa: F401
+    AlignEdge,
+    AlignResult,
     CloudIndex,
+    CloudSet,
     IcpOptions,
     IcpResult,
+    align,
+    edges_from_overlaps,
     point_normals,
     register,
 )

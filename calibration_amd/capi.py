@@ -208,6 +208,37 @@ class CbaIcpResult(C.Structure):
 
 ICP_OK, ICP_NOT_CONVERGED, ICP_TOO_FEW, ICP_DEGENERATE = 0, 1, 2, 3
 CLOUD_MAX_CELLS = 1 << 24
+ALIGN_MAX_SCANS, ALIGN_MAX_EDGES = 64, 1024
+
+
+class CbaAlignOptions(C.Structure):
+    """``cba_align_options`` (calibba.h)."""
+
+    _fields_ = [("icp", CbaIcpOptions), ("fixed", C.c_int32)]
+
+
+class CbaAlignEdge(C.Structure):
+    """``cba_align_edge`` (calibba.h)."""
+
+    _fields_ = [
+        ("H", C.c_double * 36),
+        ("g", C.c_double * 6),
+        ("ss", C.c_double),
+        ("n_pairs", C.c_int64),
+        ("used", C.c_int32),
+    ]
+
+
+class CbaAlignResult(C.Structure):
+    """``cba_align_result`` (calibba.h)."""
+
+    _fields_ = [
+        ("rms", C.c_double),
+        ("n_pairs", C.c_int64),
+        ("n_used_edges", C.c_int32),
+        ("iterations", C.c_int32),
+        ("status", C.c_int32),
+    ]
 
 
 class CbaTsdfOptions(C.Structure):
@@ -545,6 +576,13 @@ PROTOTYPES = {
     "cba_cloud_register": (
         C.c_int32, [C.c_void_p, C.c_int32, c_int64_p, c_double_p, c_double_p, C.POINTER(CbaIcpOptions), C.POINTER(CbaIcpResult)]),
     "cba_cloud_index_destroy": (None, [C.c_void_p]),
+    "cba_cloud_set_create": (
+        C.c_int32, [C.c_int32, c_int64_p, c_double_p, c_double_p, C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
+    "cba_align_options_default": (None, [C.POINTER(CbaAlignOptions)]),
+    "cba_cloud_align": (
+        C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), c_double_p, C.POINTER(CbaAlignOptions), c_double_p,
+                    C.POINTER(CbaAlignEdge), C.POINTER(CbaAlignResult)]),
+    "cba_cloud_set_destroy": (None, [C.c_void_p]),
     "cba_tsdf_options_default": (None, [C.POINTER(CbaTsdfOptions)]),
     "cba_tsdf_volume_create": (
         C.c_int32, [C.c_int32, C.c_int32, C.c_int32, c_double_p, C.POINTER(CbaTsdfOptions), C.c_int32, C.POINTER(C.c_void_p)]),

@@ -985,9 +985,30 @@ cba_status cba_cloud_index_create(int64_t n, const double* xyz, const double* no
     });
 }
 
-static void check_cloud_distance(const CloudIndex* h, double max_distance) {
-    if (!std::isfinite(max_distance) || !(max_distance > 0.0) || max_distance > 0.999 * cloud_index_cell_size(h))
+static void check_cloud_distance(double cell_size, double max_distance) {
+    if (!std::isfinite(max_distance) || !(max_distance > 0.0) || max_distance > 0.999 * cell_size)
         throw std::invalid_argument("max_distance must be > 0 and <= 0.999 cell_size");
+}
+static void check_cloud_distance(const CloudIndex* h, double max_distance) { check_cloud_distance(cloud_index_cell_size(h), max_distance); }
+
+// the checks of cba_icp_options against a grid (what: "an index", "a set")
+static void check_icp_options(const cba_icp_options& o, bool has_normals, double cell_size, const char* what) {
+    if (o.metric != 0 && o.metric != 1) throw std::invalid_argument("metric must be 0 or 1");
+    if (o.metric == 0 && !has_normals) throw std::invalid_argument(std::string("metric 0 needs ") + what + " with normals");
+    check_cloud_distance(cell_size, o.max_distance);
+    if (o.max_iterations < 0 || o.max_iterations > CBA_ICP_MAX_ITERATIONS) throw std::invalid_argument("max_iterations must be in [0, 10000]");
+    if (!std::isfinite(o.step_tolerance) || o.step_tolerance < 0.0) throw std::invalid_argument("step_tolerance must be finite and >= 0");
+}
+
+// out [7] = in [7] with its quaternion normalised by the rule of cba_cloud_register
+static void normalised_pose(const double* in, double* out) {
+#pragma clang fp contract(off)
+    const double q[4] = {in[0], in[1], in[2], in[3]};
+    const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    if (!(nq > 0.0) || !std::isfinite(nq) || !std::isfinite(in[4]) || !std::isfinite(in[5]) || !std::isfinite(in[6]))
+        throw std::invalid_argument("init_pose7 needs a non-zero finite quaternion and a finite translation");
+    for (int k = 0; k < 4; ++k) out[k] = q[k] / nq;
+    for (int k = 4; k < 7; ++k) out[k] = in[k];
 }
 
 cba_status cba_cloud_nearest(cba_cloud_index* h, int64_t m, const double* query, double max_distance, int64_t* index, double* dist2) {
@@ -1017,12 +1038,7 @@ static cba_status cloud_register_impl(cba_cloud_index* h, int32_t n_sources, con
         if (!h || !opts) throw std::invalid_argument("null argument");
         CloudIndex* c = reinterpret_cast<CloudIndex*>(h);
         if (n_sources < 0) throw std::invalid_argument("n_sources must be >= 0");
-        if (opts->metric != 0 && opts->metric != 1) throw std::invalid_argument("metric must be 0 or 1");
-        if (opts->metric == 0 && !cloud_index_has_normals(c)) throw std::invalid_argument("metric 0 needs an index with normals");
-        check_cloud_distance(c, opts->max_distance);
-        if (opts->max_iterations < 0 || opts->max_iterations > CBA_ICP_MAX_ITERATIONS)
-            throw std::invalid_argument("max_iterations must be in [0, 10000]");
-        if (!std::isfinite(opts->step_tolerance) || opts->step_tolerance < 0.0) throw std::invalid_argument("step_tolerance must be finite and >= 0");
+        check_icp_options(*opts, cloud_index_has_normals(c), cloud_index_cell_size(c), "an index");
         if (n_sources == 0) return;
         if (!source_offset || !results) throw std::invalid_argument("null argument");
         check_offsets(source_offset, n_sources, "source ", OFF_FROM_ZERO | OFF_INT32_GROUPS);
@@ -1031,16 +1047,7 @@ static cba_status cloud_register_impl(cba_cloud_index* h, int32_t n_sources, con
             cba_icp_result& r = results[i];
             r = cba_icp_result{};
             r.pose7[0] = 1.0;
-            if (init_pose7) {
-#pragma clang fp contract(off)
-                double q[4] = {init_pose7[7 * i], init_pose7[7 * i + 1], init_pose7[7 * i + 2], init_pose7[7 * i + 3]};
-                const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-                if (!(nq > 0.0) || !std::isfinite(nq) || !std::isfinite(init_pose7[7 * i + 4]) || !std::isfinite(init_pose7[7 * i + 5]) ||
-                    !std::isfinite(init_pose7[7 * i + 6]))
-                    throw std::invalid_argument("init_pose7 needs a non-zero finite quaternion and a finite translation");
-                for (int k = 0; k < 4; ++k) r.pose7[k] = q[k] / nq;
-                for (int k = 4; k < 7; ++k) r.pose7[k] = init_pose7[7 * i + k];
-            }
+            if (init_pose7) normalised_pose(init_pose7 + 7 * i, r.pose7);
             r.status = CBA_ICP_NOT_CONVERGED;
         }
         cloud_index_register(c, n_sources, source_offset, source_xyz, *opts, results, stage_ms);
@@ -1062,6 +1069,91 @@ __attribute__((visibility("default"))) cba_status cba_cloud_register_timed(cba_c
                                                                            const cba_icp_options* opts, cba_icp_result* results,
                                                                            double* stage_ms) {
     return timed(stage_ms, [&] { return cloud_register_impl(h, n_sources, source_offset, source_xyz, init_pose7, opts, results, stage_ms); });
+}
+#endif
+
+// ---- alignment of many scans (cloud_register.hip, cloud_math.hpp) -----------------------------------------------------------------
+cba_status cba_cloud_set_create(int32_t n_scans, const int64_t* offset, const double* xyz, const double* normals, double cell_size,
+                                int32_t device, cba_cloud_set** out) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        if (n_scans < 2 || n_scans > CBA_ALIGN_MAX_SCANS) throw std::invalid_argument("n_scans must be in [2, 64]");
+        if (!offset || !xyz) throw std::invalid_argument("null argument");
+        check_offsets(offset, n_scans, "scan ", OFF_FROM_ZERO | OFF_INT32_GROUPS);
+        if (!std::isfinite(cell_size) || !(cell_size > 0.0)) throw std::invalid_argument("cell_size must be finite and > 0");
+        for (int32_t k = 0; k < n_scans; ++k)
+            if (offset[k + 1] == offset[k]) throw std::invalid_argument("scan " + std::to_string(k) + " has no valid point");
+        double fit = 0.0;
+        int scan = 0;
+        const int plan = cloud_set_plan(n_scans, offset, xyz, cell_size, &scan, &fit);
+        if (plan == 1) throw std::invalid_argument("scan " + std::to_string(scan) + " has no valid point");
+        if (plan == 2) {
+            char fits[32];
+            std::snprintf(fits, sizeof fits, "%.6g", fit);
+            throw std::invalid_argument("cell_size gives scan " + std::to_string(scan) + " more than 2^24 cells; a cell_size of " + fits +
+                                        " or more fits it");
+        }
+        require_device(device);
+        *out = reinterpret_cast<cba_cloud_set*>(cloud_set_create(n_scans, offset, xyz, normals, cell_size, device));
+    });
+}
+
+void cba_align_options_default(cba_align_options* o) {
+    if (!o) return;
+    cba_icp_options_default(&o->icp);
+    o->fixed = 0;
+}
+
+static cba_status cloud_align_impl(cba_cloud_set* h, int32_t n_edges, const int32_t* edges, const double* init_pose7,
+                                   const cba_align_options* opts, double* pose7, cba_align_edge* edge_out, cba_align_result* result,
+                                   double* stage_ms) {
+    return guarded([&] {
+        if (!h || !opts || !pose7 || !result) throw std::invalid_argument("null argument");
+        CloudSet* c = reinterpret_cast<CloudSet*>(h);
+        const int32_t n_scans = cloud_set_scans(c);
+        if (n_edges < 0 || n_edges > CBA_ALIGN_MAX_EDGES) throw std::invalid_argument("n_edges must be in [0, 1024]");
+        if (n_edges > 0 && !edges) throw std::invalid_argument("null argument");
+        for (int32_t e = 0; e < n_edges; ++e) {
+            const int32_t a = edges[2 * e], b = edges[2 * e + 1];
+            if (a < 0 || a >= n_scans || b < 0 || b >= n_scans)
+                throw std::invalid_argument("edge " + std::to_string(e) + " names a scan outside [0, n_scans)");
+            if (a == b) throw std::invalid_argument("edge " + std::to_string(e) + " joins a scan to itself");
+        }
+        if (opts->fixed < 0 || opts->fixed >= n_scans) throw std::invalid_argument("fixed must be in [0, n_scans)");
+        check_icp_options(opts->icp, cloud_set_has_normals(c), cloud_set_cell_size(c), "a set");
+        std::vector<double> pose(7 * static_cast<size_t>(n_scans), 0.0);
+        for (int32_t k = 0; k < n_scans; ++k) {
+            pose[7 * static_cast<size_t>(k)] = 1.0;
+            if (init_pose7) normalised_pose(init_pose7 + 7 * k, &pose[7 * static_cast<size_t>(k)]);
+        }
+        if (n_edges == 0) {  // no work
+            std::copy(pose.begin(), pose.end(), pose7);
+            *result = cba_align_result{};
+            result->rms = std::numeric_limits<double>::quiet_NaN();
+            result->status = CBA_ICP_TOO_FEW;
+            return;
+        }
+        cloud_set_align(c, n_edges, edges, opts->icp, opts->fixed, pose.data(), edge_out, result, stage_ms);
+        std::copy(pose.begin(), pose.end(), pose7);
+    });
+}
+
+cba_status cba_cloud_align(cba_cloud_set* h, int32_t n_edges, const int32_t* edges, const double* init_pose7, const cba_align_options* opts,
+                           double* pose7, cba_align_edge* edge_out, cba_align_result* result) {
+    return cloud_align_impl(h, n_edges, edges, init_pose7, opts, pose7, edge_out, result, nullptr);
+}
+
+void cba_cloud_set_destroy(cba_cloud_set* h) { cloud_set_destroy(reinterpret_cast<CloudSet*>(h)); }
+
+#ifdef CBA_EXPERIMENTS
+// Experiment builds only (tools/bench_align.py): cba_cloud_align timing its stages on the device (stage_ms [3] = upload, rounds,
+// download).  Not part of calibba.h.
+__attribute__((visibility("default"))) cba_status cba_cloud_align_timed(cba_cloud_set* h, int32_t n_edges, const int32_t* edges,
+                                                                        const double* init_pose7, const cba_align_options* opts,
+                                                                        double* pose7, cba_align_edge* edge_out, cba_align_result* result,
+                                                                        double* stage_ms) {
+    return timed(stage_ms, [&] { return cloud_align_impl(h, n_edges, edges, init_pose7, opts, pose7, edge_out, result, stage_ms); });
 }
 #endif
 

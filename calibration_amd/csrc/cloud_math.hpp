@@ -1,11 +1,14 @@
 // cloud_math.hpp — the one copy of the scan-registration rule (calibba.h: cba_point_normals, cba_cloud_index, cba_cloud_nearest,
-// cba_cloud_register), for the device (cloud_register.hip) and for the host build of the tests (tests/cloud_cpu):
+// cba_cloud_register, cba_cloud_align), for the device (cloud_register.hip) and for the host build of the tests (tests/cloud_cpu):
 //   cloud_plan_grid      box, cell counts and extent of a target cloud (host: the handle's create and its argument check)
 //   cloud_cell           the cell of a coordinate: one subtraction, one division, floor
 //   cloud_nearest_point  the 3 x 3 x 3 neighbourhood as 9 runs of the sorted records; distance and tie rule
 //   cloud_normal         the normal of a pixel from its 5-point cross
 //   icp_rotation, icp_transform, icp_add_plane, icp_add_point   the rows of a pair, added to the 29 sums
 //   icp_cholesky6, icp_update, icp_advance                      the solve, the pose update, one step of the iteration
+//   align_relative, align_adjoint, align_edge_blocks, align_assemble_entry, align_cholesky, align_begin / align_update / align_advance
+//                        cba_cloud_align: an edge's relative pose, Ad(T_b^-1), its blocks M and c, their place in the system of all
+//                        scans, the width-n solve, the stop tests and updates
 // Every product and sum is rounded on its own: the file is compiled without contraction into FMAs, and an including translation
 // unit is too from here on (cloud_register.hip and the tests' driver include nothing after it that wants them).
 #pragma once
@@ -311,5 +314,158 @@ CBA_HD void icp_advance(const double* acc, const cba_icp_options& o, int32_t min
 }
 
 CBA_HD int32_t icp_min_pairs(const cba_icp_options& o) { return std::max(o.min_pairs, o.metric == 0 ? 6 : 3); }
+
+// ---- alignment of many scans (calibba.h: cba_cloud_align) ---------------------------------------------------------------------------
+constexpr int ALIGN_EDGE = 42;  // an edge's assembled blocks: M [36] row-major, then c [6]
+
+// The pose of scan a in the frame of scan b, T_b^-1 T_a: Rab [9] and tab [3] from the rotations Ra, Rb [9] and translations ta, tb.
+// With T_b the identity they are Ra and ta (up to the sign of a zero).
+CBA_HD void align_relative(const double* Ra, const double* ta, const double* Rb, const double* tb, double* Rab, double* tab) {
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) Rab[3 * i + k] = (Rb[i] * Ra[k] + Rb[3 + i] * Ra[3 + k]) + Rb[6 + i] * Ra[6 + k];
+    const double d[3] = {ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2]};
+    for (int i = 0; i < 3; ++i) tab[i] = (Rb[i] * d[0] + Rb[3 + i] * d[1]) + Rb[6 + i] * d[2];
+}
+
+// A [36] = Ad(T_b^-1) on (omega, v): [[R^T, 0], [-R^T [t]x, R^T]] of the pose (R [9], t [3]) of scan b
+CBA_HD void align_adjoint(const double* R, const double* t, double* A) {
+    for (int i = 0; i < 3; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            A[6 * i + k] = R[3 * k + i];
+            A[6 * i + 3 + k] = 0.0;
+            A[6 * (3 + i) + 3 + k] = R[3 * k + i];
+        }
+        A[6 * (3 + i)] = R[6 + i] * t[1] - R[3 + i] * t[2];
+        A[6 * (3 + i) + 1] = R[i] * t[2] - R[6 + i] * t[0];
+        A[6 * (3 + i) + 2] = R[3 + i] * t[0] - R[i] * t[1];
+    }
+}
+
+// entry (i, j) of M = A^T (H A): B_kj = sum_l H_kl A_lj, M_ij = sum_k A_ki B_kj, every sum left to right from its first product
+CBA_HD double align_block_entry(const double* H, const double* A, int i, int j) {
+    double m = 0.0;
+    for (int k = 0; k < 6; ++k) {
+        double b = H[6 * k] * A[j];
+        for (int l = 1; l < 6; ++l) b = b + H[6 * k + l] * A[6 * l + j];
+        const double p = A[6 * k + i] * b;
+        m = k == 0 ? p : m + p;
+    }
+    return m;
+}
+
+// entry i of c = A^T g
+CBA_HD double align_block_gradient(const double* g, const double* A, int i) {
+    double c = A[i] * g[0];
+    for (int k = 1; k < 6; ++k) c = c + A[6 * k + i] * g[k];
+    return c;
+}
+
+// out [ALIGN_EDGE]: M and c of an edge's H [36], g [6] under A [36]; A = I gives H and g back
+CBA_HD void align_edge_blocks(const double* H, const double* g, const double* A, double* out) {
+    for (int i = 0; i < 6; ++i) {
+        for (int j = 0; j < 6; ++j) out[6 * i + j] = align_block_entry(H, A, i, j);
+        out[36 + i] = align_block_gradient(g, A, i);
+    }
+}
+
+// What scan p (row block rp of the reduced system; -1: the fixed scan) receives from the used edge (a, b) with blocks mc
+// [ALIGN_EDGE], for the entry r of its row: r < 36: entry (i, j) = (r / 6, r % 6) of the blocks of row rp of H [n][n]; r >= 36:
+// entry r - 36 of its part of g.  ra, rb: the row blocks of a and b.  Called for the edges in list order, so every entry gets its
+// contributions in that order: +M on (a, a) and (b, b), -M on (a, b), -M^T on (b, a), +c on g_a, -c on g_b.
+CBA_HD void align_assemble_entry(int n, double* H, double* g, int rp, int r, int ra, int rb, const double* mc) {
+    if (rp < 0 || (ra != rp && rb != rp)) return;
+    if (r >= 36) {
+        const int i = r - 36;
+        if (ra == rp) g[6 * rp + i] += mc[36 + i];
+        if (rb == rp) g[6 * rp + i] -= mc[36 + i];
+        return;
+    }
+    const int i = r / 6, j = r - 6 * i;
+    double* row = H + static_cast<int64_t>(6 * rp + i) * n;
+    if (ra == rp) {
+        row[6 * rp + j] += mc[r];
+        if (rb >= 0) row[6 * rb + j] -= mc[r];
+    }
+    if (rb == rp) {
+        row[6 * rp + j] += mc[r];
+        if (ra >= 0) row[6 * ra + j] -= mc[6 * j + i];
+    }
+}
+
+// The width-n Cholesky in place in the lower triangle of H [n][n], icp_cholesky6's sequence: the entry (i, k), i >= k, before its
+// division: H_ik - sum_j<k L_ij L_kj, j from 0 (columns 0 .. k-1 are done)
+CBA_HD double align_cholesky_entry(int n, const double* H, int i, int k) {
+    const double* ri = H + static_cast<int64_t>(i) * n;
+    const double* rk = H + static_cast<int64_t>(k) * n;
+    double s = ri[k];
+    for (int j = 0; j < k; ++j) s -= ri[j] * rk[j];
+    return s;
+}
+
+// the test of a squared diagonal entry d against the system's own H_kk
+CBA_HD bool align_pivot_ok(double d, double hkk) { return d > 1e-12 * hkk; }
+
+// H xi = -g at width n: H is overwritten by L (lower triangle), z [n] is work.  false: a pivot failed (xi is then not meaningful; the
+// loops run to their ends all the same, as the device's do)
+CBA_HD bool align_cholesky(int n, double* H, const double* g, double* z, double* xi) {
+    bool ok = true;
+    for (int k = 0; k < n; ++k) {
+        const double d = align_cholesky_entry(n, H, k, k);
+        ok = ok && align_pivot_ok(d, H[static_cast<int64_t>(k) * n + k]);
+        const double lkk = std::sqrt(d);
+        for (int i = k + 1; i < n; ++i) H[static_cast<int64_t>(i) * n + k] = align_cholesky_entry(n, H, i, k) / lkk;
+        H[static_cast<int64_t>(k) * n + k] = lkk;
+    }
+    for (int i = 0; i < n; ++i) {
+        double s = -g[i];
+        for (int j = 0; j < i; ++j) s -= H[static_cast<int64_t>(i) * n + j] * z[j];
+        z[i] = s / H[static_cast<int64_t>(i) * n + i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double s = z[i];
+        for (int j = i + 1; j < n; ++j) s -= H[static_cast<int64_t>(j) * n + i] * xi[j];
+        xi[i] = s / H[static_cast<int64_t>(i) * n + i];
+    }
+    return ok;
+}
+
+// what the iteration carries between the rounds, beside the poses
+struct AlignState {
+    cba_align_result res;
+    int32_t phase;  // ICP_RUN, ICP_LAST, ICP_DONE
+};
+
+// The tests before the solve, on the totals of the used edges (already in st->res).  -> true: solve and update; false: the call
+// has ended (st->phase is ICP_DONE) with its status set, or this was the evaluation after the last update (the status stands).
+CBA_HD bool align_begin(const cba_icp_options& o, AlignState* st) {
+    const int32_t was = st->phase;
+    st->phase = ICP_DONE;
+    if (was == ICP_LAST) return false;
+    if (st->res.n_used_edges == 0) { st->res.status = CBA_ICP_TOO_FEW; return false; }
+    if (st->res.iterations >= o.max_iterations) { st->res.status = CBA_ICP_NOT_CONVERGED; return false; }
+    return true;
+}
+
+// The update of one scan by its xi [6]; -> whether its step is inside the tolerance
+CBA_HD bool align_update(double* pose7, const double* xi, const cba_icp_options& o, double extent) {
+    double w, vn;
+    icp_update(pose7, xi, &w, &vn);
+    return w <= o.step_tolerance && vn <= o.step_tolerance * extent;
+}
+
+// After the solve (solved: no pivot failed; on a failure no pose was touched) and the updates (all_small: every scan's step was
+// inside the tolerance): iterations, status and phase as icp_advance sets them for one source.
+CBA_HD void align_advance(bool solved, bool all_small, const cba_icp_options& o, AlignState* st) {
+    if (!solved) { st->res.status = CBA_ICP_DEGENERATE; st->phase = ICP_DONE; return; }
+    st->res.iterations += 1;
+    st->phase = ICP_RUN;
+    if (all_small) {
+        st->res.status = CBA_ICP_OK;
+        st->phase = ICP_LAST;
+    } else if (st->res.iterations >= o.max_iterations) {
+        st->res.status = CBA_ICP_NOT_CONVERGED;
+        st->phase = ICP_LAST;
+    }
+}
 
 }  // namespace cba

@@ -122,6 +122,17 @@ void cloud_index_nearest(CloudIndex* h, int64_t m, const double* query, double m
 void cloud_index_register(CloudIndex* h, int n_sources, const int64_t* source_offset, const double* source_xyz, const cba_icp_options& o,
                           cba_icp_result* results, double* stage_ms);
 void cloud_index_destroy(CloudIndex* h) noexcept;
+// cloud_register.hip: the cba_cloud_set handle (checked by the caller).  cloud_set_plan: cloud_plan of every scan, *scan the first one
+// that has no grid.  align: pose7 holds the normalised initial poses on entry; stage_ms [3] optional: upload, rounds, download
+int cloud_set_plan(int n_scans, const int64_t* offset, const double* xyz, double cell_size, int* scan, double* fit);
+struct CloudSet;
+CloudSet* cloud_set_create(int n_scans, const int64_t* offset, const double* xyz, const double* normals, double cell_size, int device);
+int cloud_set_scans(const CloudSet* h);
+double cloud_set_cell_size(const CloudSet* h);
+bool cloud_set_has_normals(const CloudSet* h);
+void cloud_set_align(CloudSet* h, int n_edges, const int32_t* edges, const cba_icp_options& o, int fixed, double* pose7, cba_align_edge* edge_out,
+                     cba_align_result* result, double* stage_ms);
+void cloud_set_destroy(CloudSet* h) noexcept;
 // tsdf_fusion.hip: the cba_tsdf_volume handle (checked by the caller).  integrate: stage_ms [2] optional: upload, kernel; extract:
 // stage_ms [2] optional: count and scan, place; mesh: stage_ms [4] optional: the extract's two, the triangles' count and scan, their
 // place.  points: the count of the last extract, -1 before the first; triangles: of the handle's mesh, -1 when there is none

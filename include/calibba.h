@@ -1125,6 +1125,86 @@ cba_status cba_cloud_register(cba_cloud_index* h, int32_t n_sources, const int64
                               const cba_icp_options* opts, cba_icp_result* results /*[n_sources]*/);
 void cba_cloud_index_destroy(cba_cloud_index* h);
 
+/* ---- alignment of many scans: ICP over a graph of scans (no counterpart in the reference) ---------------------------------------
+ *
+ * What comes between registration and fusion: the poses of N scans are made consistent with each other over a caller's list of
+ * overlapping pairs, all at once, with one pose held.  It is a bundle adjustment whose observations are ICP pairs.  "Rule 2, 3, 4"
+ * below are those of the registration block above; everything is fp64 and nothing is contracted into an FMA.
+ *
+ * The set (cba_cloud_set_create): 2 <= n_scans <= CBA_ALIGN_MAX_SCANS; scan k is xyz[offset[k] .. offset[k+1]) with optional normals
+ * of the same layout.  Every scan gets a grid of its own by rule 2 (its own lo, hi and cell counts; one cell_size for all), built on
+ * the device by the kernels of cba_cloud_index; every scan needs a valid point and at most CBA_CLOUD_MAX_CELLS cells (the message
+ * names a cell size that fits).  The set also keeps each scan's points in their original order: they are the sources.  One stream,
+ * one device, all buffers owned by the handle.  extent: the largest box diagonal of the scans, each by rule 4's form.
+ *
+ * cba_cloud_align: pose7 [n_scans][7] receives poses that map each scan into the common frame.  init_pose7 [n_scans][7], NULL =
+ * identities, quaternions normalised once on entry by rule 4.  edges [n_edges][2] = (source a, target b), a != b; duplicates and
+ * both directions are allowed and count separately.  The pose of scan opts->fixed never changes.
+ *
+ * A round at poses T_k = (q_k, t_k), R_k by rule 4:
+ * 1. Per edge (a, b): R_ab[i][k] = (R_b[0][i] R_a[0][k] + R_b[1][i] R_a[1][k]) + R_b[2][i] R_a[2][k]; d = t_a - t_b;
+ *    t_ab[i] = (R_b[0][i] d_0 + R_b[1][i] d_1) + R_b[2][i] d_2 (with T_b the identity these are R_a and t_a).  The edge's system is
+ *    rule 4's system of scan a's valid points, in index order, at (R_ab, t_ab) against scan b's grid and normals with
+ *    icp.max_distance and icp.metric: H_e [36], g_e [6], ss_e, n_pairs_e.  Its sums are added in exactly cba_cloud_register's order,
+ *    so with T_b the identity they are, to the bit, what that call returns for scan a on an index of scan b at max_iterations = 0 from
+ *    T_a.  The edge is used when n_pairs_e >= min_pairs (rule 4's floor of 6 or 3).
+ * 2. Totals over the used edges in list order: ss, n_pairs, n_used_edges.  No used edge ends with CBA_ICP_TOO_FEW.
+ *    iterations == max_iterations ends with CBA_ICP_NOT_CONVERGED.
+ * 3. Assembly.  Under the left updates of rule 4 the relative pose moves by A_b (xi_a - xi_b), A_b = Ad(T_b^-1) on (omega, v), 6 x 6
+ *    row-major with R = R_b, t = t_b: A[i][k] = A[3+i][3+k] = R[k][i]; A[i][3+k] = 0; A[3+i][0] = R[2][i] t_1 - R[1][i] t_2;
+ *    A[3+i][1] = R[0][i] t_2 - R[2][i] t_0; A[3+i][2] = R[1][i] t_0 - R[0][i] t_1 (i, k = 0..2; each product rounded).
+ *    B = H_e A, M = A^T B, c = A^T g_e: B[k][j] = sum_l H_e[k][l] A[l][j], M[i][j] = sum_k A[k][i] B[k][j], c[i] = sum_k A[k][i]
+ *    g_e[k], every sum left to right over 0..5 from its first product (so A = I gives M = H_e and c = g_e exactly).  Per used edge,
+ *    in list order: +M onto the blocks (a, a) and (b, b), -M onto (a, b) and -M^T onto (b, a), +c onto g_a, -c onto g_b of the
+ *    6 n_scans wide system.  Every entry receives its contributions in edge order.
+ * 4. Solve.  The rows and columns of `fixed` are deleted; the width is n = 6 (n_scans - 1) <= 378.  H xi = -g by rule 4's unpivoted
+ *    Cholesky at width n: row k has d = H_kk - sum_j<k L_kj L_kj, every chain sequential in j from 0, forward and back substitution
+ *    in rule 4's order; the solve fails unless every d > 1e-12 H_kk, and a failed solve ends with CBA_ICP_DEGENERATE (no pose is
+ *    touched).  This is how a scan that no used edge connects to `fixed` is reported.
+ * 5. Update: every scan but `fixed` by rule 4's update with its own xi (the device's sine and cosine).  iterations counts the rounds
+ *    with an update.  The round after which every scan has th <= step_tolerance and |v| <= step_tolerance extent is the last and
+ *    gives CBA_ICP_OK; otherwise the max_iterations-th is the last and gives CBA_ICP_NOT_CONVERGED.  The iteration can enter a
+ *    two-cycle in which one pair flips between two neighbours for ever, so CBA_ICP_NOT_CONVERGED at the cap is a normal ending.
+ * 6. After the last update the edge systems are formed once more: edge_out [n_edges] (optional: H, g, ss, n_pairs, used of every
+ *    edge), rms = sqrt(ss / n_pairs) (NaN without pairs), n_pairs and n_used_edges are those of the returned poses, in every status.
+ * A result depends on the scans, the edge list in its order, the poses and the options, not on how the device splits the work; two
+ * calls give the same bits; an edge's edge_out does not depend on the other edges of the call.
+ *
+ * Errors (CBA_ERR_INVALID_ARGUMENT, all before any device work): NULL out, offset, xyz, handle, opts, pose7, result, edges (with
+ * n_edges > 0); n_scans outside [2, CBA_ALIGN_MAX_SCANS]; offsets that decrease, do not start at 0 or give a scan more than
+ * 2^31 - 1 points; cell_size not finite and > 0; a scan without a valid point; a scan with too many cells; n_edges outside
+ * [0, CBA_ALIGN_MAX_EDGES]; a scan number out of range; a == b; fixed out of range; the icp checks of rule 4 (metric 0 on a set
+ * without normals among them; max_distance against the set's cell_size); a bad initial quaternion.  n_edges == 0 is no work: the
+ * (normalised) poses are copied, the status is CBA_ICP_TOO_FEW, rms is NaN. */
+#define CBA_ALIGN_MAX_SCANS 64
+#define CBA_ALIGN_MAX_EDGES 1024
+typedef struct cba_cloud_set cba_cloud_set; /* opaque: the scans, their grids, the buffers of its calls, one stream */
+cba_status cba_cloud_set_create(int32_t n_scans, const int64_t* offset /*[n_scans + 1]*/, const double* xyz /*[m][3]*/,
+                                const double* normals /*[m][3] or NULL*/, double cell_size, int32_t device, cba_cloud_set** out);
+typedef struct cba_align_options {
+    cba_icp_options icp;
+    int32_t fixed; /* the scan whose pose is held (default 0) */
+} cba_align_options;
+typedef struct cba_align_edge {
+    double H[36];
+    double g[6];
+    double ss;
+    int64_t n_pairs;
+    int32_t used;
+} cba_align_edge;
+typedef struct cba_align_result {
+    double rms;
+    int64_t n_pairs;
+    int32_t n_used_edges;
+    int32_t iterations; /* rounds with an update */
+    int32_t status;     /* cba_icp_status */
+} cba_align_result;
+void cba_align_options_default(cba_align_options* o); /* cba_icp_options_default and fixed = 0 */
+cba_status cba_cloud_align(cba_cloud_set* h, int32_t n_edges, const int32_t* edges /*[n_edges][2]: source, target*/,
+                           const double* init_pose7 /*[n_scans][7] or NULL*/, const cba_align_options* opts,
+                           double* pose7 /*[n_scans][7]*/, cba_align_edge* edge_out /*[n_edges] or NULL*/, cba_align_result* result);
+void cba_cloud_set_destroy(cba_cloud_set* h);
+
 /* ---- scan fusion: a truncated signed distance volume from depth maps, surface points (no counterpart in the reference) ---------
  *
  * What comes after registration: the views of one object, each with its pose, are merged into one surface.  Storage is float32;
