@@ -965,21 +965,37 @@ cba_status cba_point_normals(int32_t n_maps, int32_t height, int32_t width, cons
     });
 }
 
+static void check_cell_size(double c) { if (!std::isfinite(c) || !(c > 0.0)) throw std::invalid_argument("cell_size must be finite and > 0"); }
+// the text of a grid plan's answer 2: whom ("" or "scan k ") the cell size gives too many cells, and the one that fits
+static std::string too_many_cells(const std::string& whom, double fit, const char* tail) {
+    char fits[32];
+    std::snprintf(fits, sizeof fits, "%.6g", fit);
+    return "cell_size gives " + whom + "more than 2^24 cells; a cell_size of " + fits + tail;
+}
+
+// the n poses of pose7 [n][7] have non-zero finite quaternions, or invalid_argument(message) -> the last one's norm, nothing contracted
+static double check_pose_quaternions(const double* pose7, int64_t n, const char* message) {
+#pragma clang fp contract(off)
+    double nq = 0.0;
+    for (int64_t m = 0; m < n; ++m) {
+        const double* q = pose7 + 7 * static_cast<size_t>(m);
+        nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+        if (!(nq > 0.0) || !std::isfinite(nq)) throw std::invalid_argument(message);
+    }
+    return nq;
+}
+
 cba_status cba_cloud_index_create(int64_t n, const double* xyz, const double* normals, double cell_size, int32_t device, cba_cloud_index** out) {
     return guarded([&] {
         if (!out) throw std::invalid_argument("null argument");
         *out = nullptr;
         if (n < 1 || n > 0x7fffffff) throw std::invalid_argument("n must be in [1, 2^31 - 1]");
         if (!xyz) throw std::invalid_argument("null argument");
-        if (!std::isfinite(cell_size) || !(cell_size > 0.0)) throw std::invalid_argument("cell_size must be finite and > 0");
+        check_cell_size(cell_size);
         double fit = 0.0;
         const int plan = cloud_plan(n, xyz, cell_size, &fit);
         if (plan == 1) throw std::invalid_argument("the target has no valid point");
-        if (plan == 2) {
-            char fits[32];
-            std::snprintf(fits, sizeof fits, "%.6g", fit);
-            throw std::invalid_argument(std::string("cell_size gives more than 2^24 cells; a cell_size of ") + fits + " or more fits");
-        }
+        if (plan == 2) throw std::invalid_argument(too_many_cells("", fit, " or more fits"));
         require_device(device);
         *out = reinterpret_cast<cba_cloud_index*>(cloud_index_create(n, xyz, normals, cell_size, device));
     });
@@ -1002,12 +1018,10 @@ static void check_icp_options(const cba_icp_options& o, bool has_normals, double
 
 // out [7] = in [7] with its quaternion normalised by the rule of cba_cloud_register
 static void normalised_pose(const double* in, double* out) {
-#pragma clang fp contract(off)
-    const double q[4] = {in[0], in[1], in[2], in[3]};
-    const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    if (!(nq > 0.0) || !std::isfinite(nq) || !std::isfinite(in[4]) || !std::isfinite(in[5]) || !std::isfinite(in[6]))
-        throw std::invalid_argument("init_pose7 needs a non-zero finite quaternion and a finite translation");
-    for (int k = 0; k < 4; ++k) out[k] = q[k] / nq;
+    const char* message = "init_pose7 needs a non-zero finite quaternion and a finite translation";
+    const double nq = check_pose_quaternions(in, 1, message);
+    if (!std::isfinite(in[4]) || !std::isfinite(in[5]) || !std::isfinite(in[6])) throw std::invalid_argument(message);
+    for (int k = 0; k < 4; ++k) out[k] = in[k] / nq;
     for (int k = 4; k < 7; ++k) out[k] = in[k];
 }
 
@@ -1081,19 +1095,14 @@ cba_status cba_cloud_set_create(int32_t n_scans, const int64_t* offset, const do
         if (n_scans < 2 || n_scans > CBA_ALIGN_MAX_SCANS) throw std::invalid_argument("n_scans must be in [2, 64]");
         if (!offset || !xyz) throw std::invalid_argument("null argument");
         check_offsets(offset, n_scans, "scan ", OFF_FROM_ZERO | OFF_INT32_GROUPS);
-        if (!std::isfinite(cell_size) || !(cell_size > 0.0)) throw std::invalid_argument("cell_size must be finite and > 0");
+        check_cell_size(cell_size);
         for (int32_t k = 0; k < n_scans; ++k)
             if (offset[k + 1] == offset[k]) throw std::invalid_argument("scan " + std::to_string(k) + " has no valid point");
         double fit = 0.0;
         int scan = 0;
         const int plan = cloud_set_plan(n_scans, offset, xyz, cell_size, &scan, &fit);
         if (plan == 1) throw std::invalid_argument("scan " + std::to_string(scan) + " has no valid point");
-        if (plan == 2) {
-            char fits[32];
-            std::snprintf(fits, sizeof fits, "%.6g", fit);
-            throw std::invalid_argument("cell_size gives scan " + std::to_string(scan) + " more than 2^24 cells; a cell_size of " + fits +
-                                        " or more fits it");
-        }
+        if (plan == 2) throw std::invalid_argument(too_many_cells("scan " + std::to_string(scan) + " ", fit, " or more fits it"));
         require_device(device);
         *out = reinterpret_cast<cba_cloud_set*>(cloud_set_create(n_scans, offset, xyz, normals, cell_size, device));
     });
@@ -1195,12 +1204,7 @@ static cba_status tsdf_integrate_impl(cba_tsdf_volume* h, int32_t camera_model, 
         check_sides(width, height);
         if (n_maps == 0) return;
         if (!depth || !c_T_v) throw std::invalid_argument("null argument");
-        for (int32_t m = 0; m < n_maps; ++m) {
-#pragma clang fp contract(off)
-            const double* q = c_T_v + 7 * static_cast<size_t>(m);
-            const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-            if (!(nq > 0.0) || !std::isfinite(nq)) throw std::invalid_argument("c_T_v needs a non-zero finite quaternion");
-        }
+        check_pose_quaternions(c_T_v, n_maps, "c_T_v needs a non-zero finite quaternion");
         tsdf_volume_integrate(reinterpret_cast<TsdfVolume*>(h), camera_model, intr, n_maps, height, width, depth, c_T_v, stage_ms);
     });
 }
@@ -1306,12 +1310,7 @@ static cba_status tsdf_raycast_impl(cba_tsdf_volume* h, int32_t camera_model, co
         if (!(o.min_weight >= 1.0)) throw std::invalid_argument("min_weight must be >= 1");
         if (n_views == 0) return;
         if (!poses) throw std::invalid_argument("null argument");
-        for (int32_t m = 0; m < n_views; ++m) {
-#pragma clang fp contract(off)
-            const double* q = poses + 7 * static_cast<size_t>(m);
-            const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-            if (!(nq > 0.0) || !std::isfinite(nq)) throw std::invalid_argument("poses needs a non-zero finite quaternion");
-        }
+        check_pose_quaternions(poses, n_views, "poses needs a non-zero finite quaternion");
         tsdf_volume_raycast(v, camera_model, intr, n_views, height, width, poses, o, wave_w, stage_ms);
     });
 }

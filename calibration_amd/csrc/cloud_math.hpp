@@ -1,16 +1,17 @@
 // cloud_math.hpp — the one copy of the scan-registration rule (calibba.h: cba_point_normals, cba_cloud_index, cba_cloud_nearest,
-// cba_cloud_register, cba_cloud_align), for the device (cloud_register.hip) and for the host build of the tests (tests/cloud_cpu):
+// cba_cloud_register, cba_cloud_align), for the device (cloud_register.hip) and the tests' host builds (tests/cloud_cpu, tests/align_cpu):
 //   cloud_plan_grid      box, cell counts and extent of a target cloud (host: the handle's create and its argument check)
 //   cloud_cell           the cell of a coordinate: one subtraction, one division, floor
 //   cloud_nearest_point  the 3 x 3 x 3 neighbourhood as 9 runs of the sorted records; distance and tie rule
 //   cloud_normal         the normal of a pixel from its 5-point cross
 //   icp_rotation, icp_transform, icp_add_plane, icp_add_point   the rows of a pair, added to the 29 sums
+//   icp_add_source_point, icp_add_match   the point rule: what one source point adds to a system against a CloudTarget
 //   icp_cholesky6, icp_update, icp_advance                      the solve, the pose update, one step of the iteration
 //   align_relative, align_adjoint, align_edge_blocks, align_assemble_entry, align_cholesky, align_begin / align_update / align_advance
 //                        cba_cloud_align: an edge's relative pose, Ad(T_b^-1), its blocks M and c, their place in the system of all
 //                        scans, the width-n solve, the stop tests and updates
 // Every product and sum is rounded on its own: the file is compiled without contraction into FMAs, and an including translation
-// unit is too from here on (cloud_register.hip and the tests' driver include nothing after it that wants them).
+// unit is too from here on (cloud_register.hip and the tests' drivers include nothing after it that wants them).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -39,6 +40,14 @@ struct CloudGrid {
 struct alignas(32) CloudRec {
     double x, y, z;
     int64_t idx;  // the point's index in the caller's array
+};
+
+// a target of the search and of ICP
+struct CloudTarget {
+    CloudGrid g;
+    const int32_t* start;      // [n_cells + 1]: the first record of each cell
+    const CloudRec* rec;       // the valid points in cell order
+    const double* rec_normal;  // [][3]: their normals in the same order; NULL: the target has none
 };
 
 CBA_HD bool cloud_valid(double x, double y, double z) { return std::isfinite(x) && std::isfinite(y) && std::isfinite(z); }
@@ -208,6 +217,33 @@ CBA_HD void icp_add_point(const double* Q, const double* y, double* acc) {
     icp_add_row(Jy, Q[1] - y[1], acc);
     icp_add_row(Jz, Q[2] - y[2], acc);
     acc[ICP_NP] += 1.0;
+}
+
+// the pair of Q and the target record at pos into the sums; METRIC 0: point-to-plane, nothing without a normal (NaN); 1: point-to-point
+template <int METRIC>
+CBA_HD void icp_add_match(const double* Q, const CloudRec* __restrict__ rec, const double* __restrict__ rec_normal, int32_t pos, double* acc) {
+    const CloudRec r = rec[pos];
+    const double y[3] = {r.x, r.y, r.z};
+    if (METRIC == 0) {
+        const double* np = rec_normal + 3 * static_cast<int64_t>(pos);
+        const double n[3] = {np[0], np[1], np[2]};
+        if (n[0] != n[0]) return;
+        icp_add_plane(Q, y, n, acc);
+    } else {
+        icp_add_point(Q, y, acc);
+    }
+}
+
+// The point rule: the source point p [3] at the pose (R, t) against target (md, md2 = md md: max_distance) into the sums.  An invalid
+// point, one without a target point within md and, for METRIC 0, one whose match has no normal add nothing.
+template <int METRIC>
+CBA_HD void icp_add_source_point(const CloudTarget& target, const double* R, const double* t, const double* p, double md, double md2, double* acc) {
+    if (!cloud_valid(p[0], p[1], p[2])) return;
+    double Q[3], d2;
+    int32_t pos;
+    icp_transform(R, t, p, Q);
+    if (cloud_nearest_point(target.g, target.start, target.rec, Q[0], Q[1], Q[2], md, md2, &pos, &d2) < 0) return;
+    icp_add_match<METRIC>(Q, target.rec, target.rec_normal, pos, acc);
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------------

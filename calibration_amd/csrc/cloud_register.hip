@@ -3,26 +3,24 @@
 //   k_point_normals     one lane per pixel: the centre and its four neighbours straight from global memory (a row is read by three
 //                       rows of lanes, which the caches serve), cloud_normal.
 //   k_cloud_count       one lane per target point: its cell into cell_of (-1: invalid), integer atomicAdd on the cell's count.
-//   k_scan_tiles / k_scan_add   (scan_tiles.hpp) exclusive scan of the counts in tiles of CLOUD_SCAN_TILE = 1024 cells (256 lanes, 4 cells
-//                       each, the lanes' sums scanned in LDS); the tile sums are scanned by the same kernels, up to three levels at the cap.
+//   k_scan_tiles / k_scan_add   (scan_tiles.hpp) exclusive scan of the counts in tiles of SCAN_TILE = 1024 cells, up to three levels at the cap.
 //   k_cloud_scatter     one lane per valid point: its place by integer atomicAdd on the cell's start, the 32-byte record and the
 //                       normal into cell order.  The starts live at start + 1 while they are bumped: afterwards start[c + 1] is the
 //                       end of cell c, which is the start of cell c + 1, and start[0] = 0 was never touched.
 //   k_cloud_nearest     one lane per query, grid-stride: cloud_nearest_point.  No LDS.
-//   k_icp_accumulate    ICP_BLOCKS workgroups per source, grid-striding its points: transform, search, rows, 29 sums in registers;
-//                       wave_transpose_sum inside the wave, LDS across the four waves, one slab row per (source, block).
-//   k_icp_step          one wavefront per source: lane e adds entry e of the source's slab rows in block order; lane 0 runs
-//                       icp_advance (Cholesky, update, stop tests) and writes pose, phase and, when the source ends, the done count.
-// The host queues max_iterations + 1 rounds of the two ICP kernels without reading values; every ICP_POLL rounds it reads the done
-// count and stops when every source has ended.  A source that has ended is not touched again, so results do not depend on when the
-// host looks.  No float atomics anywhere; integer atomics only for counts and places.
+//   k_icp_accumulate    ICP_BLOCKS workgroups per source, grid-striding its points: the point rule (icp_add_source_point), 29 sums in
+//                       registers; wave_transpose_sum inside the wave, LDS across the four waves, one slab row per (source, block).
+//   k_icp_step          one wavefront per source: lane e adds entry e of the source's slab rows in block order (icp_slab_entry); lane 0
+//                       runs icp_advance (Cholesky, update, stop tests) and writes pose, phase and, when the source ends, the done count.
+// The host builds a grid by cloud_build_grid and runs both pipelines by icp_rounds: max_iterations + 1 rounds of the two kernels queued
+// without reading values; every ICP_POLL rounds it reads the done count (the set: the state) and stops when every system has ended.  One
+// that has ended is not touched again, so results do not depend on when the host looks.  No float atomics; integer ones for counts and places.
 // cba_cloud_set / cba_cloud_align (the alignment of many scans over a graph of pairs):
 //   k_align_accumulate  ICP_BLOCKS workgroups per edge (a, b): k_icp_accumulate's body (icp_accumulate_block, one copy for both) on scan
-//                       a's points at T_b^-1 T_a against scan b's grid; the edge, the scans' table rows and the poses from blockIdx.
+//                       a's points at T_b^-1 T_a against scan b (a CloudTarget); the edge, the scans' table rows and the poses from blockIdx.
 //   k_align_step        one workgroup per call: the edges' slab rows in workgroup order, their statistics and blocks M = A^T H A,
 //                       c = A^T g, the system of all scans but the fixed one in a global workspace (every entry walks the edges in list
 //                       order), the width-n Cholesky by columns with two barriers each, both substitutions, the updates, the state.
-// The host queues the two kernels as for cba_cloud_register and reads the state every ICP_POLL rounds.
 #include <memory>
 #include <type_traits>
 #include <vector>
@@ -36,7 +34,6 @@ namespace cba {
 
 constexpr int CLOUD_BLOCK = 256;
 constexpr int CLOUD_GRID = 8192;        // grid-stride cap
-constexpr int CLOUD_SCAN_TILE = SCAN_TILE;  // cells per workgroup of the scan (scan_tiles.hpp)
 constexpr int ICP_BLOCKS = 128;         // workgroups per source: fixed, so a source's sums do not depend on the call
 constexpr int ICP_POLL = 4;             // rounds between two looks at the done count
 
@@ -108,24 +105,20 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_scatter(int64_t n, const 
     }
 }
 
-__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_nearest(int64_t m, const double* __restrict__ query, CloudGrid g,
-                                                               const int32_t* __restrict__ start, const CloudRec* __restrict__ rec, double md,
+__global__ __launch_bounds__(CLOUD_BLOCK) void k_cloud_nearest(int64_t m, const double* __restrict__ query, CloudTarget t, double md,
                                                                int64_t* __restrict__ index, double* __restrict__ dist2) {
     const double md2 = md * md;
     for (int64_t i = blockIdx.x * static_cast<int64_t>(CLOUD_BLOCK) + threadIdx.x; i < m; i += static_cast<int64_t>(gridDim.x) * CLOUD_BLOCK) {
         int32_t pos;
         double d2;
-        index[i] = cloud_nearest_point(g, start, rec, query[3 * i], query[3 * i + 1], query[3 * i + 2], md, md2, &pos, &d2);
+        index[i] = cloud_nearest_point(t.g, t.start, t.rec, query[3 * i], query[3 * i + 1], query[3 * i + 2], md, md2, &pos, &d2);
         dist2[i] = d2;
     }
 }
 
 // ---- ICP --------------------------------------------------------------------------------------------------------------------------
 struct IcpArgs {
-    CloudGrid g;
-    const int32_t* start;
-    const CloudRec* rec;
-    const double* rec_normal;
+    CloudTarget target;
     const int64_t* offset;   // [n_sources + 1]
     const double* src;       // [m][3]
     cba_icp_result* res;     // [n_sources]: pose7, iterations and status live here between the rounds
@@ -136,38 +129,20 @@ struct IcpArgs {
     double extent;
 };
 
-// The body of both accumulate kernels (k_icp_accumulate, k_align_accumulate): workgroup blk of the ICP_BLOCKS of one system, the m
-// points at src at the pose (R, t) against one grid; the sums of the workgroup go to slab_row [ICP_ROW].  Every value that selects
-// the system is wave-uniform.
+// The body of both accumulate kernels (k_icp_accumulate, k_align_accumulate): workgroup blockIdx.x is one of the ICP_BLOCKS of system
+// blockIdx.x / ICP_BLOCKS; the m points at src at the pose (R, t) against one target; the sums of the workgroup go to its row of
+// slab [systems][ICP_BLOCKS][ICP_ROW].  Every value that selects the system is wave-uniform.
 template <int METRIC>
-__device__ __forceinline__ void icp_accumulate_block(const CloudGrid& g, const int32_t* __restrict__ start, const CloudRec* __restrict__ rec,
-                                                     const double* __restrict__ rec_normal, const double* __restrict__ src, int64_t m,
-                                                     const double* R, const double* t, double md, int blk, double* __restrict__ slab_row,
+__device__ __forceinline__ void icp_accumulate_block(const CloudTarget& target, const double* __restrict__ src, int64_t m, const double* R,
+                                                     const double* t, double md, int blk, double* __restrict__ slab_row,
                                                      double (*part)[ICP_ROW]) {
     const double md2 = md * md;
     double acc[ICP_ROW];
 #pragma unroll
     for (int e = 0; e < ICP_ROW; ++e) acc[e] = 0.0;
 #pragma unroll 1
-    for (int64_t i = static_cast<int64_t>(blk) * CLOUD_BLOCK + threadIdx.x; i < m; i += static_cast<int64_t>(ICP_BLOCKS) * CLOUD_BLOCK) {
-        const double* pp = src + 3 * i;
-        const double p[3] = {pp[0], pp[1], pp[2]};
-        if (!cloud_valid(p[0], p[1], p[2])) continue;
-        double Q[3], d2;
-        int32_t pos;
-        icp_transform(R, t, p, Q);
-        if (cloud_nearest_point(g, start, rec, Q[0], Q[1], Q[2], md, md2, &pos, &d2) < 0) continue;
-        const CloudRec r = rec[pos];
-        const double y[3] = {r.x, r.y, r.z};
-        if (METRIC == 0) {
-            const double* np = rec_normal + 3 * static_cast<int64_t>(pos);
-            const double n[3] = {np[0], np[1], np[2]};
-            if (n[0] != n[0]) continue;  // no normal: all three are NaN
-            icp_add_plane(Q, y, n, acc);
-        } else {
-            icp_add_point(Q, y, acc);
-        }
-    }
+    for (int64_t i = static_cast<int64_t>(blk) * CLOUD_BLOCK + threadIdx.x; i < m; i += static_cast<int64_t>(ICP_BLOCKS) * CLOUD_BLOCK)
+        icp_add_source_point<METRIC>(target, R, t, src + 3 * i, md, md2, acc);
     // every lane of every wave is here: the grid-stride loop has no early exit
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool owner;
@@ -196,21 +171,24 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_icp_accumulate(IcpArgs a) {
         icp_rotation(q, R);
         t[0] = pose[4]; t[1] = pose[5]; t[2] = pose[6];
     }
-    icp_accumulate_block<METRIC>(a.g, a.start, a.rec, a.rec_normal, a.src + 3 * first, m, R, t, a.o.max_distance, blk,
+    icp_accumulate_block<METRIC>(a.target, a.src + 3 * first, m, R, t, a.o.max_distance, blk,
                                  a.slab + (static_cast<int64_t>(s) * ICP_BLOCKS + blk) * ICP_ROW, part);
+}
+
+// entry c of a system's sums: its ICP_BLOCKS slab rows (slab: the first) added in block order from row 0 on; the order is the result
+__device__ __forceinline__ double icp_slab_entry(const double* __restrict__ slab, int c) {
+    const double* row = slab + c;
+    double v = row[0];
+#pragma unroll 4
+    for (int b = 1; b < ICP_BLOCKS; ++b) v += row[static_cast<int64_t>(b) * ICP_ROW];
+    return v;
 }
 
 __global__ __launch_bounds__(64) void k_icp_step(IcpArgs a) {
     __shared__ double sums[ICP_ROW];
     const int s = blockIdx.x, lane = threadIdx.x;
     if (a.phase[s] == ICP_DONE) return;
-    if (lane < ICP_ROW) {
-        const double* row = a.slab + static_cast<int64_t>(s) * ICP_BLOCKS * ICP_ROW + lane;
-        double v = row[0];
-#pragma unroll 1
-        for (int b = 1; b < ICP_BLOCKS; ++b) v += row[static_cast<int64_t>(b) * ICP_ROW];
-        sums[lane] = v;
-    }
+    if (lane < ICP_ROW) sums[lane] = icp_slab_entry(a.slab + static_cast<int64_t>(s) * ICP_BLOCKS * ICP_ROW, lane);
     __syncthreads();
     if (lane == 0) {
         double acc[ICP_SUMS];
@@ -228,9 +206,9 @@ __global__ __launch_bounds__(64) void k_icp_step(IcpArgs a) {
 // ends with its stream synchronised.
 struct CloudIndex : DeviceHandle {
     using DeviceHandle::DeviceHandle;
-    CloudGrid g{};
+    CloudTarget target{};      // the grid, and the three buffers below as the kernels read them
     double extent = 0.0;
-    int64_t n = 0, n_cells = 0;
+    int64_t n_cells = 0;
     bool has_normals = false;
     DevBuf<int32_t> start;     // [n_cells + 1]
     DevBuf<CloudRec> rec;      // [n]: the valid points in cell order
@@ -250,12 +228,33 @@ int cloud_plan(int64_t n, const double* xyz, double cell_size, double* fit) {
     return cloud_plan_grid(n, xyz, cell_size, &g, &extent, &n_cells, fit);
 }
 
+// The target of grid g queued on s from its n points on the device (normals NULL: none): count into start + 1, scan, scatter.
+// start [n_cells + 1] comes zeroed; cell_of [n] and tmp [scan_tmp_size(n_cells)] are work.
+static CloudTarget cloud_build_grid(hipStream_t s, const CloudGrid& g, int64_t n_cells, int64_t n, const double* pts, const double* normals,
+                                    int32_t* cell_of, int32_t* tmp, int32_t* start, CloudRec* rec, double* rec_normal) {
+    const dim3 grid(launch_grid(n, CLOUD_BLOCK, CLOUD_GRID));
+    hipLaunchKernelGGL(k_cloud_count, grid, dim3(CLOUD_BLOCK), 0, s, n, pts, g, cell_of, start + 1);
+    scan_exclusive(s, start + 1, n_cells, tmp);
+    hipLaunchKernelGGL(k_cloud_scatter, grid, dim3(CLOUD_BLOCK), 0, s, n, pts, normals, cell_of, start + 1, rec, rec_normal);
+    CBA_HIP(hipGetLastError());
+    return CloudTarget{g, start, rec, rec_normal};
+}
+
+// The rounds of an ICP call: queue_round() queues one; all_done() reads back, synchronised, whether every system has ended.
+template <class Queue, class Done>
+static void icp_rounds(int max_iterations, Queue queue_round, Done all_done) {
+    for (int round = 0; round <= max_iterations; ++round) {
+        queue_round();
+        CBA_HIP(hipGetLastError());
+        if (round % ICP_POLL == ICP_POLL - 1 && round < max_iterations && all_done()) break;
+    }
+}
+
 CloudIndex* cloud_index_create(int64_t n, const double* xyz, const double* normals, double cell_size, int device) {
     auto h = std::make_unique<CloudIndex>(device);
     double fit;
-    if (cloud_plan_grid(n, xyz, cell_size, &h->g, &h->extent, &h->n_cells, &fit) != 0) throw std::invalid_argument("no grid for these points");
+    if (cloud_plan_grid(n, xyz, cell_size, &h->target.g, &h->extent, &h->n_cells, &fit) != 0) throw std::invalid_argument("no grid for these points");
     const hipStream_t s = h->begin();
-    h->n = n;
     h->has_normals = normals != nullptr;
     DevBuf<double> pts, nrm;
     DevBuf<int32_t> cell_of, tmp;
@@ -269,17 +268,13 @@ CloudIndex* cloud_index_create(int64_t n, const double* xyz, const double* norma
     if (normals) h->rec_normal.alloc(static_cast<size_t>(3 * n));
     h->n_done.alloc(1);
     h->done_h.reserve(1);
-    const dim3 grid(launch_grid(n, CLOUD_BLOCK, CLOUD_GRID));
-    hipLaunchKernelGGL(k_cloud_count, grid, dim3(CLOUD_BLOCK), 0, s, n, pts.p, h->g, cell_of.p, h->start.p + 1);
-    scan_exclusive(s, h->start.p + 1, h->n_cells, tmp.p);
-    hipLaunchKernelGGL(k_cloud_scatter, grid, dim3(CLOUD_BLOCK), 0, s, n, pts.p, normals ? nrm.p : nullptr, cell_of.p, h->start.p + 1, h->rec.p,
-                       h->rec_normal.p);
-    CBA_HIP(hipGetLastError());
+    h->target = cloud_build_grid(s, h->target.g, h->n_cells, n, pts.p, normals ? nrm.p : nullptr, cell_of.p, tmp.p, h->start.p, h->rec.p,
+                                 h->rec_normal.p);
     CBA_HIP(hipStreamSynchronize(s));  // the build's buffers go out of scope
     return h.release();
 }
 
-double cloud_index_cell_size(const CloudIndex* h) { return h->g.cell; }
+double cloud_index_cell_size(const CloudIndex* h) { return h->target.g.cell; }
 bool cloud_index_has_normals(const CloudIndex* h) { return h->has_normals; }
 
 void cloud_index_nearest(CloudIndex* h, int64_t m, const double* query, double max_distance, int64_t* index, double* dist2) {
@@ -288,8 +283,8 @@ void cloud_index_nearest(CloudIndex* h, int64_t m, const double* query, double m
     h->index.ensure(static_cast<size_t>(m));
     h->dist2.ensure(static_cast<size_t>(m));
     h->query.upload(query, static_cast<size_t>(3 * m), s);
-    hipLaunchKernelGGL(k_cloud_nearest, dim3(launch_grid(m, CLOUD_BLOCK, CLOUD_GRID)), dim3(CLOUD_BLOCK), 0, s, m, h->query.p, h->g, h->start.p,
-                       h->rec.p, max_distance, h->index.p, h->dist2.p);
+    hipLaunchKernelGGL(k_cloud_nearest, dim3(launch_grid(m, CLOUD_BLOCK, CLOUD_GRID)), dim3(CLOUD_BLOCK), 0, s, m, h->query.p, h->target,
+                       max_distance, h->index.p, h->dist2.p);
     CBA_HIP(hipGetLastError());
     h->index.download(index, static_cast<size_t>(m), s);
     if (dist2) h->dist2.download(dist2, static_cast<size_t>(m), s);
@@ -316,23 +311,18 @@ void cloud_index_register(CloudIndex* h, int n_sources, const int64_t* source_of
     CBA_HIP(hipMemsetAsync(h->n_done.p, 0, sizeof(int32_t), s));
     tm.mark(1);
     IcpArgs a;
-    a.g = h->g; a.start = h->start.p; a.rec = h->rec.p; a.rec_normal = h->rec_normal.p;
-    a.offset = h->offset.p; a.src = h->src.p; a.res = h->res.p; a.phase = h->phase.p; a.slab = h->slab.p; a.n_done = h->n_done.p;
+    a.target = h->target; a.offset = h->offset.p; a.src = h->src.p; a.res = h->res.p; a.phase = h->phase.p; a.slab = h->slab.p; a.n_done = h->n_done.p;
     a.o = o; a.extent = h->extent;
     const dim3 grid(static_cast<unsigned>(n_sources) * ICP_BLOCKS);
-    for (int round = 0; round <= o.max_iterations; ++round) {
-        if (o.metric == 0)
-            hipLaunchKernelGGL(k_icp_accumulate<0>, grid, dim3(CLOUD_BLOCK), 0, s, a);
-        else
-            hipLaunchKernelGGL(k_icp_accumulate<1>, grid, dim3(CLOUD_BLOCK), 0, s, a);
+    const auto queue_round = [&] {
+        hipLaunchKernelGGL(o.metric == 0 ? k_icp_accumulate<0> : k_icp_accumulate<1>, grid, dim3(CLOUD_BLOCK), 0, s, a);
         hipLaunchKernelGGL(k_icp_step, dim3(static_cast<unsigned>(n_sources)), dim3(64), 0, s, a);
-        CBA_HIP(hipGetLastError());
-        if (round % ICP_POLL == ICP_POLL - 1 && round < o.max_iterations) {
-            h->n_done.download(h->done_h.p, 1, s);
-            CBA_HIP(hipStreamSynchronize(s));
-            if (h->done_h.p[0] == n_sources) break;
-        }
-    }
+    };
+    icp_rounds(o.max_iterations, queue_round, [&] {
+        h->n_done.download(h->done_h.p, 1, s);
+        CBA_HIP(hipStreamSynchronize(s));
+        return h->done_h.p[0] == n_sources;
+    });
     tm.mark(2);
     h->res.download(results, static_cast<size_t>(n_sources), s);
     tm.mark(3);
@@ -345,10 +335,7 @@ void cloud_index_destroy(CloudIndex* h) noexcept { destroy_handle(h); }
 // ---- alignment of many scans (calibba.h: cba_cloud_align) -------------------------------------------------------------------------
 // a scan of the set: its grid and sorted records (it is a target) and its points in original order (it is a source)
 struct AlignScan {
-    CloudGrid g;
-    const int32_t* start;
-    const CloudRec* rec;
-    const double* rec_normal;
+    CloudTarget target;
     int64_t first, count;  // its points are xyz[first .. first + count)
 };
 
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(CLOUD_BLOCK) void k_align_accumulate(AlignArgs a) {
         icp_rotation(qb, Rb);
         align_relative(Ra, ta, Rb, tb, R, t);
     }
-    icp_accumulate_block<METRIC>(B.g, B.start, B.rec, B.rec_normal, a.xyz + 3 * A.first, A.count, R, t, a.o.max_distance, blk,
+    icp_accumulate_block<METRIC>(B.target, a.xyz + 3 * A.first, A.count, R, t, a.o.max_distance, blk,
                                  a.slab + (static_cast<int64_t>(e) * ICP_BLOCKS + blk) * ICP_ROW, part);
 }
 
@@ -415,11 +402,7 @@ __global__ __launch_bounds__(ALIGN_BLOCK) void k_align_step(AlignArgs a) {
     // 1. entry c of edge e: its slab rows in workgroup order; a scan's adjoint
     for (int it = tid; it < E * ICP_ROW; it += ALIGN_BLOCK) {
         const int e = it / ICP_ROW, c = it - e * ICP_ROW;
-        const double* row = a.slab + static_cast<int64_t>(e) * ICP_BLOCKS * ICP_ROW + c;
-        double v = row[0];
-#pragma unroll 4
-        for (int b = 1; b < ICP_BLOCKS; ++b) v += row[static_cast<int64_t>(b) * ICP_ROW];
-        a.sums[it] = v;
+        a.sums[it] = icp_slab_entry(a.slab + static_cast<int64_t>(e) * ICP_BLOCKS * ICP_ROW, c);
     }
     for (int p = tid; p < N; p += ALIGN_BLOCK) {
         const double* pose = a.pose + 7 * p;
@@ -595,7 +578,7 @@ CloudSet* cloud_set_create(int n_scans, const int64_t* offset, const double* xyz
         AlignScan& t = table[k];
         t.first = offset[k];
         t.count = offset[k + 1] - offset[k];
-        if (cloud_plan_grid(t.count, xyz + 3 * t.first, cell_size, &t.g, &extent, &cells[k], &fit) != 0)
+        if (cloud_plan_grid(t.count, xyz + 3 * t.first, cell_size, &t.target.g, &extent, &cells[k], &fit) != 0)
             throw std::invalid_argument("no grid for these points");
         h->extent = std::max(h->extent, extent);
         start_at[k] = n_start;
@@ -617,19 +600,8 @@ CloudSet* cloud_set_create(int n_scans, const int64_t* offset, const double* xyz
     h->st_h.reserve(1);
     for (int k = 0; k < n_scans; ++k) {
         AlignScan& t = table[k];
-        int32_t* start = h->start.p + start_at[k];
-        CloudRec* rec = h->rec.p + t.first;
-        double* rec_normal = normals ? h->rec_normal.p + 3 * t.first : nullptr;
-        const double* pts = h->xyz.p + 3 * t.first;
-        const dim3 grid(launch_grid(t.count, CLOUD_BLOCK, CLOUD_GRID));
-        hipLaunchKernelGGL(k_cloud_count, grid, dim3(CLOUD_BLOCK), 0, s, t.count, pts, t.g, cell_of.p, start + 1);
-        scan_exclusive(s, start + 1, cells[k], tmp.p);
-        hipLaunchKernelGGL(k_cloud_scatter, grid, dim3(CLOUD_BLOCK), 0, s, t.count, pts, normals ? nrm.p + 3 * t.first : nullptr, cell_of.p,
-                           start + 1, rec, rec_normal);
-        CBA_HIP(hipGetLastError());
-        t.start = start;
-        t.rec = rec;
-        t.rec_normal = rec_normal;
+        t.target = cloud_build_grid(s, t.target.g, cells[k], t.count, h->xyz.p + 3 * t.first, normals ? nrm.p + 3 * t.first : nullptr, cell_of.p, tmp.p,
+                                    h->start.p + start_at[k], h->rec.p + t.first, normals ? h->rec_normal.p + 3 * t.first : nullptr);
     }
     h->scan.assign(table.data(), table.size(), s);
     CBA_HIP(hipStreamSynchronize(s));  // the build's buffers and the host table go out of scope
@@ -667,19 +639,15 @@ void cloud_set_align(CloudSet* h, int n_edges, const int32_t* edges, const cba_i
     a.edge_out = h->edge_out.p; a.adj = h->adj.p; a.blocks = h->blocks.p; a.H = h->H.p;
     a.o = o; a.extent = h->extent; a.n_scans = h->n_scans; a.n_edges = n_edges; a.fixed = fixed;
     const dim3 grid(static_cast<unsigned>(n_edges) * ICP_BLOCKS);
-    for (int round = 0; round <= o.max_iterations; ++round) {
-        if (o.metric == 0)
-            hipLaunchKernelGGL(k_align_accumulate<0>, grid, dim3(CLOUD_BLOCK), 0, s, a);
-        else
-            hipLaunchKernelGGL(k_align_accumulate<1>, grid, dim3(CLOUD_BLOCK), 0, s, a);
+    const auto queue_round = [&] {
+        hipLaunchKernelGGL(o.metric == 0 ? k_align_accumulate<0> : k_align_accumulate<1>, grid, dim3(CLOUD_BLOCK), 0, s, a);
         hipLaunchKernelGGL(k_align_step, dim3(1), dim3(ALIGN_BLOCK), 0, s, a);
-        CBA_HIP(hipGetLastError());
-        if (round % ICP_POLL == ICP_POLL - 1 && round < o.max_iterations) {
-            h->st.download(h->st_h.p, 1, s);
-            CBA_HIP(hipStreamSynchronize(s));
-            if (h->st_h.p[0].phase == ICP_DONE) break;
-        }
-    }
+    };
+    icp_rounds(o.max_iterations, queue_round, [&] {
+        h->st.download(h->st_h.p, 1, s);
+        CBA_HIP(hipStreamSynchronize(s));
+        return h->st_h.p[0].phase == ICP_DONE;
+    });
     tm.mark(2);
     h->pose.download(pose7, 7 * N, s);
     if (edge_out) h->edge_out.download(edge_out, E, s);

@@ -2,6 +2,7 @@
 // tsdf_fusion.hip (edge counts per tile -> the first place of each tile).  Tiles of SCAN_TILE = 1024 entries (256 lanes, 4 entries
 // each, the lanes' sums scanned in LDS); the tile sums are scanned by the same kernels, level after level.  Integers: any order of
 // addition gives the same result.  The kernels are static: each translation unit that includes this gets its own copy.
+// For kernels that count per tile and then place: scan_counts (host) and wave_counts_prefix (a wave among its workgroup's).
 #pragma once
 #include "hip_glue.hpp"
 
@@ -64,6 +65,35 @@ static void scan_exclusive(hipStream_t s, int32_t* v, int64_t n, int32_t* tmp) {
         scan_exclusive(s, tmp, tiles, tmp + tiles);
         hipLaunchKernelGGL(k_scan_add, dim3(static_cast<unsigned>(tiles)), dim3(SCAN_BLOCK), 0, s, n, v, tmp);
     }
+}
+
+// count [n], which a kernel queued on s fills -> its exclusive scan in place and the total: entry n is zeroed and scanned with the
+// counts, so it receives the total.  tmp: scan_tmp_size(n + 1) entries; total_h: one pinned entry.  Ends with s synchronised.
+[[maybe_unused]] static int64_t scan_counts(hipStream_t s, int32_t* count, int64_t n, int32_t* tmp, int32_t* total_h) {
+    CBA_HIP(hipMemsetAsync(count + n, 0, sizeof(int32_t), s));
+    scan_exclusive(s, count, n + 1, tmp);
+    CBA_HIP(hipGetLastError());
+    CBA_HIP(hipMemcpyAsync(total_h, count + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CBA_HIP(hipStreamSynchronize(s));
+    return total_h[0];
+}
+
+// total: the wave's count, taken from lane 0 and exchanged through four entries of LDS.  -> the count of the workgroup (SCAN_BLOCK
+// lanes); *before <- that of the waves before this one.  Two barriers: every lane of the workgroup must reach the call.
+__device__ __forceinline__ int32_t wave_counts_prefix(int32_t total, int lane, int wave, int32_t* before) {
+    __shared__ int32_t wave_total[SCAN_BLOCK / 64];
+    if (lane == 0) wave_total[wave] = total;
+    __syncthreads();
+    int32_t all = 0, b = 0;
+#pragma unroll
+    for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
+        const int32_t t = wave_total[w];
+        b += w < wave ? t : 0;
+        all += t;
+    }
+    __syncthreads();  // the next call writes wave_total again
+    *before = b;
+    return all;
 }
 
 }  // namespace cba

@@ -9,8 +9,8 @@
 //                       LDS, no atomics; no lane reads another's voxel.
 //   k_tsdf_planes       the interleaved rows <-> dense [nz][ny][nx] planes of D and of W (fetch, upload).
 //   k_tsdf_extract<0>   one workgroup per tile of TSDF_EXTRACT_TILE voxels of the dense order, in four rounds of 256 voxels: each lane
-//                       tests the three edges of its voxel; ballots and popcounts give the wave's total, LDS the workgroup's.
-//   k_scan_tiles / k_scan_add   (scan_tiles.hpp) the exclusive scan of the tile counts; one extra entry receives the total.
+//                       tests the three edges of its voxel; ballots and popcounts give the wave's total, wave_counts_prefix the workgroup's.
+//   k_scan_tiles / k_scan_add   (scan_tiles.hpp: scan_counts) the exclusive scan of the tile counts; one extra entry receives the total.
 //   k_tsdf_extract<1>   the same walk again: an edge's place is its tile's start, the rounds and waves before it, and the popcount of
 //                       the ballots below its lane, so the order is the visiting order whatever the arrival order; tsdf_edge_point.
 //   k_tsdf_extract<1,1> the place pass of cba_tsdf_mesh: it also writes, per wave and round, the record {first place, three ballots} of
@@ -45,6 +45,7 @@ constexpr int TSDF_BLOCK = 256;
 constexpr int TSDF_GRID = 8192;  // grid-stride cap of the fill and plane kernels
 static_assert(TSDF_EXTRACT_TILE == 4 * TSDF_BLOCK, "k_tsdf_extract walks a tile in four rounds");
 static_assert(TSDF_BLOCK == 256, "k_tsdf_mesh stages one table word per lane");
+static_assert(TSDF_BLOCK == SCAN_BLOCK, "wave_counts_prefix adds up the waves of a workgroup of SCAN_BLOCK lanes");
 static_assert(TSDF_MESH_GROUP == 64 && TSDF_EXTRACT_TILE % TSDF_MESH_GROUP == 0, "a record is one wave of one round of k_tsdf_extract");
 
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_fill(int64_t n_stored, float2* __restrict__ vol) {
@@ -103,7 +104,6 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_planes(TsdfGrid g, float* _
 template <bool PLACE, bool RECORD = false>
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const float* __restrict__ vol, double min_weight, int32_t* __restrict__ count,
                                                              double* __restrict__ xyz, double* __restrict__ nrm, TsdfEdgeGroup* __restrict__ rec) {
-    __shared__ int32_t wave_total[TSDF_BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
     int32_t base = PLACE ? count[blockIdx.x] : 0;
@@ -112,25 +112,14 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const f
         const int64_t l = static_cast<int64_t>(blockIdx.x) * TSDF_EXTRACT_TILE + round * TSDF_BLOCK + threadIdx.x;
         int i = 0, j = 0, k = 0, mask = 0;
         if (l < n) {
-            const int64_t row = l / g.nx;
-            i = static_cast<int>(l - row * g.nx);
-            k = static_cast<int>(row / g.ny);
-            j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+            tsdf_voxel_of(g, l, &i, &j, &k);
             mask = tsdf_edge_mask(vol, g, i, j, k, min_weight);
         }
         // every lane of the workgroup is here: the ballots and the barriers see all of them
         const uint64_t b0 = __ballot(mask & 1), b1 = __ballot(mask & 2), b2 = __ballot(mask & 4);
         const uint64_t below = (1ull << lane) - 1;
-        if (lane == 0) wave_total[wave] = __popcll(b0) + __popcll(b1) + __popcll(b2);
-        __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TSDF_BLOCK / 64; ++w) {
-            const int32_t t = wave_total[w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        __syncthreads();  // the next round writes wave_total again
+        int32_t before;
+        const int32_t all = wave_counts_prefix(__popcll(b0) + __popcll(b1) + __popcll(b2), lane, wave, &before);
         if (RECORD && lane == 0) {  // l is a multiple of 64 here
             TsdfEdgeGroup r;
             r.ballot[0] = b0; r.ballot[1] = b1; r.ballot[2] = b2;
@@ -167,7 +156,6 @@ template <bool PLACE>
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_mesh(TsdfGrid g, const float* __restrict__ vol, double min_weight,
                                                           const TsdfEdgeGroup* __restrict__ rec, int32_t* __restrict__ count, int32_t* __restrict__ tri) {
     __shared__ uint64_t table[256];
-    __shared__ int32_t wave_total[TSDF_BLOCK / 64];
     table[threadIdx.x] = d_tsdf_mesh_table.w[threadIdx.x];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -179,10 +167,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_mesh(TsdfGrid g, const floa
         int i = 0, j = 0, k = 0, own = 0;
         bool rows = false;
         if (l < n) {
-            const int64_t row = l / g.nx;
-            i = static_cast<int>(l - row * g.nx);
-            k = static_cast<int>(row / g.ny);
-            j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+            tsdf_voxel_of(g, l, &i, &j, &k);
             rows = tsdf_mesh_has_rows(g, j, k);
             if (rows) own = tsdf_mesh_rows(vol, g, i, j, k, min_weight);
         }
@@ -196,16 +181,8 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_mesh(TsdfGrid g, const floa
         const int mine = tsdf_mesh_word_count(word);  // 0 .. 5: three bits
         const uint64_t c0 = __ballot(mine & 1), c1 = __ballot(mine & 2), c2 = __ballot(mine & 4);
         const uint64_t below = (1ull << lane) - 1;
-        if (lane == 0) wave_total[wave] = __popcll(c0) + 2 * __popcll(c1) + 4 * __popcll(c2);
-        __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TSDF_BLOCK / 64; ++w) {
-            const int32_t t = wave_total[w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        __syncthreads();  // the next round writes wave_total again
+        int32_t before;
+        const int32_t all = wave_counts_prefix(__popcll(c0) + 2 * __popcll(c1) + 4 * __popcll(c2), lane, wave, &before);
         if (PLACE && mine) {
             int64_t at = base + before + __popcll(c0 & below) + 2 * __popcll(c1 & below) + 4 * __popcll(c2 & below);
 #pragma unroll 1
@@ -357,10 +334,8 @@ void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_m
     TsdfRule r;
     r.trunc = h->o.truncation; r.max_depth = h->o.max_depth; r.max_weight = h->o.max_weight; r.W = W; r.H = H;
     const dim3 grid(static_cast<unsigned>((h->n_stored / 2 + TSDF_BLOCK - 1) / TSDF_BLOCK));
-    if (model == CAM_SCHEIMPFLUG)
-        hipLaunchKernelGGL(k_tsdf_integrate<CAM_SCHEIMPFLUG>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
-    else
-        hipLaunchKernelGGL(k_tsdf_integrate<CAM_PINHOLE_BC>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
+    hipLaunchKernelGGL(model == CAM_SCHEIMPFLUG ? k_tsdf_integrate<CAM_SCHEIMPFLUG> : k_tsdf_integrate<CAM_PINHOLE_BC>, grid, dim3(TSDF_BLOCK), 0, s, h->g,
+                       h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
     CBA_HIP(hipGetLastError());
     tm.mark(2);
     CBA_HIP(hipStreamSynchronize(s));  // cam and poses go out of scope
@@ -369,10 +344,7 @@ void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_m
 
 static void tsdf_planes(TsdfVolume* h, hipStream_t s, bool to_dense, float* tsdf, float* weight) {
     const dim3 grid(launch_grid(h->n_voxels, TSDF_BLOCK, TSDF_GRID));
-    if (to_dense)
-        hipLaunchKernelGGL(k_tsdf_planes<true>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, tsdf, weight);
-    else
-        hipLaunchKernelGGL(k_tsdf_planes<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, tsdf, weight);
+    hipLaunchKernelGGL(to_dense ? k_tsdf_planes<true> : k_tsdf_planes<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, tsdf, weight);
     CBA_HIP(hipGetLastError());
 }
 
@@ -402,24 +374,15 @@ template <class Timer>
 static int64_t tsdf_extract_run(TsdfVolume* h, hipStream_t s, double min_weight, bool record, Timer& tm) {
     const dim3 grid(static_cast<unsigned>(h->n_tiles));
     tm.mark(0);
-    CBA_HIP(hipMemsetAsync(h->count.p + h->n_tiles, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL((k_tsdf_extract<false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr, nullptr);
-    scan_exclusive(s, h->count.p, h->n_tiles + 1, h->tmp.p);
-    CBA_HIP(hipGetLastError());
-    h->count.download(h->total_h.p, 1, s, static_cast<size_t>(h->n_tiles));
-    CBA_HIP(hipStreamSynchronize(s));
-    const int64_t total = h->total_h.p[0];
+    const int64_t total = scan_counts(s, h->count.p, h->n_tiles, h->tmp.p, h->total_h.p);
     tm.mark(1);
     h->n_points = -1;
     if (total > 0) {
         h->xyz.ensure(3 * static_cast<size_t>(total));
         h->nrm.ensure(3 * static_cast<size_t>(total));
-        if (record)
-            hipLaunchKernelGGL((k_tsdf_extract<true, true>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p,
-                               h->rec.p);
-        else
-            hipLaunchKernelGGL((k_tsdf_extract<true>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p,
-                               nullptr);
+        hipLaunchKernelGGL((record ? k_tsdf_extract<true, true> : k_tsdf_extract<true, false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight,
+                           h->count.p, h->xyz.p, h->nrm.p, record ? h->rec.p : nullptr);
         CBA_HIP(hipGetLastError());
     }
     tm.mark(2);
@@ -448,13 +411,8 @@ void tsdf_volume_mesh(TsdfVolume* h, double min_weight, int64_t* n_points, int64
     int64_t total = 0;
     if (points > 0) {  // a triangle needs three points, and only then were the records written
         const dim3 grid(static_cast<unsigned>(h->n_tiles));
-        CBA_HIP(hipMemsetAsync(h->tcount.p + h->n_tiles, 0, sizeof(int32_t), s));
         hipLaunchKernelGGL(k_tsdf_mesh<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->rec.p, h->tcount.p, nullptr);
-        scan_exclusive(s, h->tcount.p, h->n_tiles + 1, h->tmp.p);
-        CBA_HIP(hipGetLastError());
-        h->tcount.download(h->total_h.p, 1, s, static_cast<size_t>(h->n_tiles));
-        CBA_HIP(hipStreamSynchronize(s));
-        total = h->total_h.p[0];
+        total = scan_counts(s, h->tcount.p, h->n_tiles, h->tmp.p, h->total_h.p);
         tm.mark(3);
         if (total > 0) {
             h->tri.ensure(3 * static_cast<size_t>(total));

@@ -51,6 +51,14 @@ CBA_HD int64_t tsdf_at(const TsdfGrid& g, int i, int j, int k) {
     return 2 * ((static_cast<int64_t>(k) * g.ny + j) * g.pitch + i);
 }
 
+// voxel l of the dense order [nz][ny][nx], x fastest -> (i, j, k)
+CBA_HD void tsdf_voxel_of(const TsdfGrid& g, int64_t l, int* i, int* j, int* k) {
+    const int64_t row = l / g.nx;
+    *i = static_cast<int>(l - row * g.nx);
+    *k = static_cast<int>(row / g.ny);
+    *j = static_cast<int>(row - static_cast<int64_t>(*k) * g.ny);
+}
+
 // One voxel at X through one map (steps 1-6 of calibba.h).  depth: the map [H][W].  Returns whether the voxel was updated.
 template <int MODEL>
 CBA_HD bool tsdf_update(const TsdfCam& c, const TsdfPose& p, const double* depth, const TsdfRule& r, double X0, double X1, double X2, float* D,

@@ -1,7 +1,6 @@
 // align_driver.cpp — TEST-ONLY: extern "C" wrapper of cloud_math.hpp's alignment of many scans for ctypes (tests/test_align_cpu.py).
-// Every scan's grid is built on the host by a counting sort with the header's cell arithmetic (as tests/cloud_cpu does for one
-// target); an edge's sums are added in index order into one accumulator, by the grid search or by brute force over the scan's valid
-// points; the relative pose, the adjoint, the blocks, their places in the system, the width-n Cholesky, the stop tests and the
+// Every scan's grid is built on the host (tests/host_cloud.hpp); an edge's sums are added in index order into one accumulator, by the
+// point rule every lane runs or, its search replaced, by brute force over the scan's valid points; the relative pose, the adjoint, the blocks, their places in the system, the width-n Cholesky, the stop tests and the
 // updates are the functions the device runs.  Built with -DCBA_HOST_DRIVER_MAIN it is a stand-alone program (for the sanitizers):
 // the planted statuses, 2 and 64 scans, 1 and 1024 edges, the last scan fixed, duplicate and two-way edges.  Every buffer is
 // sized exactly.
@@ -10,51 +9,17 @@
 #include <cstring>
 #include <vector>
 
-#include "../../calibration_amd/csrc/cloud_math.hpp"
+#include "../host_cloud.hpp"
 
 using namespace cba;
 
 struct HostScan {
-    CloudGrid g;
-    double extent = 0.0;
-    int64_t n_cells = 0, first = 0, count = 0;
-    std::vector<int32_t> start;
-    std::vector<CloudRec> rec;
-    std::vector<double> nrm;
+    HostCloud cloud;
+    int64_t first = 0, count = 0;
 };
 
-static int host_build(int64_t n, const double* xyz, const double* normals, double cell, HostScan* ix) {
-    double fit;
-    const int plan = cloud_plan_grid(n, xyz, cell, &ix->g, &ix->extent, &ix->n_cells, &fit);
-    if (plan != 0) return plan;
-    ix->start.assign(static_cast<size_t>(ix->n_cells) + 1, 0);
-    std::vector<int32_t> cell_of(static_cast<size_t>(n), -1);
-    int64_t n_valid = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const double* p = xyz + 3 * i;
-        if (!cloud_valid(p[0], p[1], p[2])) continue;
-        cell_of[i] = cloud_point_cell(ix->g, p[0], p[1], p[2]);
-        ++ix->start[static_cast<size_t>(cell_of[i]) + 1];
-        ++n_valid;
-    }
-    for (int64_t c = 0; c < ix->n_cells; ++c) ix->start[c + 1] += ix->start[c];
-    std::vector<int32_t> at(ix->start.begin(), ix->start.end() - 1);
-    ix->rec.resize(static_cast<size_t>(n_valid));
-    if (normals) ix->nrm.resize(3 * static_cast<size_t>(n_valid));
-    for (int64_t i = 0; i < n; ++i) {
-        if (cell_of[i] < 0) continue;
-        const int32_t k = at[cell_of[i]]++;
-        CloudRec r;
-        r.x = xyz[3 * i]; r.y = xyz[3 * i + 1]; r.z = xyz[3 * i + 2]; r.idx = i;
-        ix->rec[k] = r;
-        if (normals)
-            for (int j = 0; j < 3; ++j) ix->nrm[3 * static_cast<size_t>(k) + j] = normals[3 * i + j];
-    }
-    return 0;
-}
-
 // brute force's rule over all valid points of the scan, in the records' order: -> the record's place or -1
-static int32_t brute_nearest(const HostScan& ix, const double* Q, double md2) {
+static int32_t brute_nearest(const HostCloud& ix, const double* Q, double md2) {
     int32_t pos = -1;
     int64_t best = -1;
     double bd = 0.0;
@@ -73,30 +38,23 @@ static int32_t brute_nearest(const HostScan& ix, const double* Q, double md2) {
 }
 
 // the sums of edge (a, b) at the poses: scan a's m points src at (R, t) against scan b
-static void host_edge_sums(const HostScan& b, int64_t m, const double* src, const double* R, const double* t, const cba_icp_options& o,
+template <int METRIC>
+static void host_edge_sums(const HostCloud& b, int64_t m, const double* src, const double* R, const double* t, const cba_icp_options& o,
                            bool brute, double* acc) {
     for (int e = 0; e < ICP_SUMS; ++e) acc[e] = 0.0;
     const double md = o.max_distance, md2 = md * md;
+    const CloudTarget target = b.target();
     for (int64_t i = 0; i < m; ++i) {
         const double* p = src + 3 * i;
-        if (!cloud_valid(p[0], p[1], p[2])) continue;
-        double Q[3], d2;
-        int32_t pos;
-        icp_transform(R, t, p, Q);
-        if (brute)
-            pos = brute_nearest(b, Q, md2);
-        else if (cloud_nearest_point(b.g, b.start.data(), b.rec.data(), Q[0], Q[1], Q[2], md, md2, &pos, &d2) < 0)
-            pos = -1;
-        if (pos < 0) continue;
-        const CloudRec& r = b.rec[pos];
-        const double y[3] = {r.x, r.y, r.z};
-        if (o.metric == 0) {
-            const double* n = &b.nrm[3 * static_cast<size_t>(pos)];
-            if (n[0] != n[0]) continue;
-            icp_add_plane(Q, y, n, acc);
-        } else {
-            icp_add_point(Q, y, acc);
+        if (!brute) {
+            icp_add_source_point<METRIC>(target, R, t, p, md, md2, acc);
+            continue;
         }
+        if (!cloud_valid(p[0], p[1], p[2])) continue;
+        double Q[3];
+        icp_transform(R, t, p, Q);
+        const int32_t pos = brute_nearest(b, Q, md2);
+        if (pos >= 0) icp_add_match<METRIC>(Q, target.rec, target.rec_normal, pos, acc);
     }
 }
 
@@ -116,9 +74,9 @@ int align_host(int n_scans, const int64_t* offset, const double* xyz, const doub
         HostScan& s = scan[k];
         s.first = offset[k];
         s.count = offset[k + 1] - offset[k];
-        const int plan = host_build(s.count, xyz + 3 * s.first, normals ? normals + 3 * s.first : nullptr, cell, &s);
+        const int plan = host_build(s.count, xyz + 3 * s.first, normals ? normals + 3 * s.first : nullptr, cell, &s.cloud);
         if (plan != 0) return 10 + plan;
-        extent = std::max(extent, s.extent);
+        extent = std::max(extent, s.cloud.extent);
     }
     cba_icp_options o;
     o.metric = metric; o.max_distance = max_distance; o.max_iterations = max_iterations; o.step_tolerance = step_tolerance; o.min_pairs = min_pairs;
@@ -151,7 +109,7 @@ int align_host(int n_scans, const int64_t* offset, const double* xyz, const doub
             icp_rotation(pose7 + 7 * a, Ra);
             icp_rotation(pose7 + 7 * b, Rb);
             align_relative(Ra, pose7 + 7 * a + 4, Rb, pose7 + 7 * b + 4, R, t);
-            host_edge_sums(scan[b], scan[a].count, xyz + 3 * scan[a].first, R, t, o, brute != 0, acc);
+            (metric == 0 ? host_edge_sums<0> : host_edge_sums<1>)(scan[b].cloud, scan[a].count, xyz + 3 * scan[a].first, R, t, o, brute != 0, acc);
             double* w = edge_out + static_cast<size_t>(EDGE_OUT) * e;
             icp_mirror(acc, w);
             for (int k = 0; k < 6; ++k) w[36 + k] = acc[21 + k];

@@ -1,6 +1,6 @@
 // cloud_driver.cpp — TEST-ONLY: extern "C" wrapper of cloud_math.hpp for ctypes (tests/test_cloud_cpu.py).  The grid is built on the
-// host by a counting sort with the header's cell arithmetic (points of a cell in index order); the search, the normal, the rows, the
-// Cholesky and the update are the functions every lane runs.  A source's sums are added in index order into one accumulator.  Built
+// host (tests/host_cloud.hpp); the point rule, the search, the normal, the rows, the Cholesky and the update are the functions every
+// lane runs.  A source's sums are added in index order into one accumulator.  Built
 // with -DCBA_HOST_DRIVER_MAIN it is a stand-alone program (for the sanitizers): it checks the grid search against brute force on a
 // scattered cloud with planted ties and invalid points, the normals of a plane, and that both metrics recover a known small motion.
 #include <cstdint>
@@ -8,75 +8,26 @@
 #include <cstring>
 #include <vector>
 
-#include "../../calibration_amd/csrc/cloud_math.hpp"
+#include "../host_cloud.hpp"
 
 using namespace cba;
 
-struct HostIndex {
-    CloudGrid g;
-    double extent = 0.0;
-    int64_t n_cells = 0;
-    std::vector<int32_t> start;
-    std::vector<CloudRec> rec;
-    std::vector<double> nrm;
-};
-
-static int host_build(int64_t n, const double* xyz, const double* normals, double cell, HostIndex* ix) {
-    double fit;
-    const int plan = cloud_plan_grid(n, xyz, cell, &ix->g, &ix->extent, &ix->n_cells, &fit);
-    if (plan != 0) return plan;
-    ix->start.assign(static_cast<size_t>(ix->n_cells) + 1, 0);
-    std::vector<int32_t> cell_of(static_cast<size_t>(n), -1);
-    int64_t n_valid = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const double* p = xyz + 3 * i;
-        if (!cloud_valid(p[0], p[1], p[2])) continue;
-        cell_of[i] = cloud_point_cell(ix->g, p[0], p[1], p[2]);
-        ++ix->start[static_cast<size_t>(cell_of[i]) + 1];
-        ++n_valid;
-    }
-    for (int64_t c = 0; c < ix->n_cells; ++c) ix->start[c + 1] += ix->start[c];
-    std::vector<int32_t> at(ix->start.begin(), ix->start.end() - 1);
-    ix->rec.resize(static_cast<size_t>(n_valid));
-    if (normals) ix->nrm.resize(3 * static_cast<size_t>(n_valid));
-    for (int64_t i = 0; i < n; ++i) {
-        if (cell_of[i] < 0) continue;
-        const int32_t k = at[cell_of[i]]++;
-        CloudRec r;
-        r.x = xyz[3 * i]; r.y = xyz[3 * i + 1]; r.z = xyz[3 * i + 2]; r.idx = i;
-        ix->rec[k] = r;
-        if (normals)
-            for (int j = 0; j < 3; ++j) ix->nrm[3 * static_cast<size_t>(k) + j] = normals[3 * i + j];
-    }
-    return 0;
-}
-
 // the sums of the system of one source at res->pose7
-static void host_system(const HostIndex& ix, int64_t m, const double* src, const cba_icp_options& o, const cba_icp_result& res, double* acc) {
+static void host_system(const HostCloud& ix, int64_t m, const double* src, const cba_icp_options& o, const cba_icp_result& res, double* acc) {
     for (int e = 0; e < ICP_SUMS; ++e) acc[e] = 0.0;
     double R[9];
     icp_rotation(res.pose7, R);
     const double md = o.max_distance, md2 = md * md;
+    const CloudTarget target = ix.target();
     for (int64_t i = 0; i < m; ++i) {
-        const double* p = src + 3 * i;
-        if (!cloud_valid(p[0], p[1], p[2])) continue;
-        double Q[3], d2;
-        int32_t pos;
-        icp_transform(R, res.pose7 + 4, p, Q);
-        if (cloud_nearest_point(ix.g, ix.start.data(), ix.rec.data(), Q[0], Q[1], Q[2], md, md2, &pos, &d2) < 0) continue;
-        const CloudRec& r = ix.rec[pos];
-        const double y[3] = {r.x, r.y, r.z};
-        if (o.metric == 0) {
-            const double* n = &ix.nrm[3 * static_cast<size_t>(pos)];
-            if (n[0] != n[0]) continue;
-            icp_add_plane(Q, y, n, acc);
-        } else {
-            icp_add_point(Q, y, acc);
-        }
+        if (o.metric == 0)
+            icp_add_source_point<0>(target, R, res.pose7 + 4, src + 3 * i, md, md2, acc);
+        else
+            icp_add_source_point<1>(target, R, res.pose7 + 4, src + 3 * i, md, md2, acc);
     }
 }
 
-static void host_register_one(const HostIndex& ix, int64_t m, const double* src, const double* init, const cba_icp_options& o,
+static void host_register_one(const HostCloud& ix, int64_t m, const double* src, const double* init, const cba_icp_options& o,
                               cba_icp_result* res) {
     *res = cba_icp_result{};
     res->pose7[0] = 1.0;
@@ -111,7 +62,7 @@ void cloud_host_normals(int n_maps, int H, int W, const double* xyz, const doubl
 
 // cba_cloud_index_create + cba_cloud_nearest in one call; -> the grid plan's answer (0: done)
 int cloud_host_nearest(int64_t n, const double* xyz, double cell, int64_t m, const double* query, double md, int64_t* index, double* dist2) {
-    HostIndex ix;
+    HostCloud ix;
     const int plan = host_build(n, xyz, nullptr, cell, &ix);
     if (plan != 0) return plan;
     const double md2 = md * md;
@@ -127,7 +78,7 @@ int cloud_host_nearest(int64_t n, const double* xyz, double cell, int64_t m, con
 int cloud_host_register(int64_t n, const double* xyz, const double* normals, double cell, int n_sources, const int64_t* offset,
                         const double* src, const double* init_pose7, int metric, double max_distance, int max_iterations,
                         double step_tolerance, int min_pairs, double* out) {
-    HostIndex ix;
+    HostCloud ix;
     const int plan = host_build(n, xyz, normals, cell, &ix);
     if (plan != 0) return plan;
     cba_icp_options o;

@@ -13,7 +13,7 @@ import numpy as np
 from tests.host_build import ptr
 
 OK, NOT_CONVERGED, TOO_FEW, DEGENERATE = 0, 1, 2, 3
-SCAN_TILE = 1024  # cells per workgroup of the device's scan (cloud_register.hip: CLOUD_SCAN_TILE)
+SCAN_TILE = 1024  # cells per workgroup of the device's scan (scan_tiles.hpp: SCAN_TILE)
 
 
 def valid(p):

@@ -7,36 +7,9 @@
 #include <limits>
 #include <vector>
 
-#include "../../calibration_amd/csrc/tsdf_math.hpp"
+#include "../host_volume.hpp"
 
 using namespace cba;
-
-struct HostVolume {
-    TsdfGrid g;
-    std::vector<float> vol;
-    HostVolume(int nx, int ny, int nz, const double* origin, double vs, const float* D, const float* W) {
-        g.nx = nx; g.ny = ny; g.nz = nz; g.pitch = (nx + 1) & ~1;
-        for (int c = 0; c < 3; ++c) g.o[c] = origin[c];
-        g.vs = vs;
-        vol.assign(2 * static_cast<size_t>(g.pitch) * ny * nz, 0.0f);
-        for (int k = 0; k < nz; ++k)
-            for (int j = 0; j < ny; ++j)
-                for (int i = 0; i < nx; ++i) {
-                    const int64_t l = (static_cast<int64_t>(k) * ny + j) * nx + i;
-                    vol[tsdf_at(g, i, j, k)] = D ? D[l] : 1.0f;
-                    vol[tsdf_at(g, i, j, k) + 1] = W ? W[l] : 0.0f;
-                }
-    }
-    void planes(float* D, float* W) const {
-        for (int k = 0; k < g.nz; ++k)
-            for (int j = 0; j < g.ny; ++j)
-                for (int i = 0; i < g.nx; ++i) {
-                    const int64_t l = (static_cast<int64_t>(k) * g.ny + j) * g.nx + i;
-                    D[l] = vol[tsdf_at(g, i, j, k)];
-                    W[l] = vol[tsdf_at(g, i, j, k) + 1];
-                }
-    }
-};
 
 static void host_integrate(HostVolume& v, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* poses,
                            const TsdfRule& r) {

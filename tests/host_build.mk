@@ -17,7 +17,7 @@ SRC ?= $(wildcard *.cpp)
 CXX ?= g++
 FP_CONTRACT ?= off
 FLAGS := -std=c++17 -Wall -Wextra -Wno-unknown-pragmas -ffp-contract=$(FP_CONTRACT) $(EXTRA)
-HDR := $(wildcard ../../calibration_amd/csrc/*.hpp) ../../include/calibba.h
+HDR := $(wildcard ../../calibration_amd/csrc/*.hpp) $(wildcard ../*.hpp) ../../include/calibba.h
 _build/lib$(NAME).so: $(SRC) $(HDR)
 	@mkdir -p _build
 	$(CXX) -O2 $(FLAGS) -fPIC -shared -Wl,-Bsymbolic -o $@ $(SRC)

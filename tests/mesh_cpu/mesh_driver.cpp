@@ -11,26 +11,9 @@
 #include <vector>
 
 #include "../../calibration_amd/csrc/tsdf_mesh_math.hpp"
+#include "../host_volume.hpp"
 
 using namespace cba;
-
-struct HostVolume {
-    TsdfGrid g;
-    std::vector<float> vol;
-    HostVolume(int nx, int ny, int nz, const float* D, const float* W) {
-        g.nx = nx; g.ny = ny; g.nz = nz; g.pitch = (nx + 1) & ~1;
-        for (int c = 0; c < 3; ++c) g.o[c] = 0.0;
-        g.vs = 1.0;
-        vol.assign(2 * static_cast<size_t>(g.pitch) * ny * nz, 0.0f);
-        for (int k = 0; k < nz; ++k)
-            for (int j = 0; j < ny; ++j)
-                for (int i = 0; i < nx; ++i) {
-                    const int64_t l = (static_cast<int64_t>(k) * ny + j) * nx + i;
-                    vol[tsdf_at(g, i, j, k)] = D[l];
-                    vol[tsdf_at(g, i, j, k) + 1] = W[l];
-                }
-    }
-};
 
 // the records of every group, as k_tsdf_extract's waves write them -> the number of points
 static int64_t host_records(const HostVolume& v, double min_weight, std::vector<TsdfEdgeGroup>& rec) {
@@ -40,8 +23,8 @@ static int64_t host_records(const HostVolume& v, double min_weight, std::vector<
     for (int64_t l = 0; l < n; ++l) {
         TsdfEdgeGroup& r = rec[static_cast<size_t>(l / TSDF_MESH_GROUP)];
         if (l % TSDF_MESH_GROUP == 0) r.start = static_cast<int32_t>(at);
-        const int64_t row = l / v.g.nx;
-        const int i = static_cast<int>(l - row * v.g.nx), k = static_cast<int>(row / v.g.ny), j = static_cast<int>(row - static_cast<int64_t>(k) * v.g.ny);
+        int i, j, k;
+        tsdf_voxel_of(v.g, l, &i, &j, &k);
         const int mask = tsdf_edge_mask(v.vol.data(), v.g, i, j, k, min_weight);
         for (int axis = 0; axis < 3; ++axis)
             if (mask >> axis & 1) {
@@ -82,7 +65,8 @@ void mesh_host_table(uint64_t* words) {
 }
 
 int64_t mesh_host_triangles(int nx, int ny, int nz, const float* D, const float* W, double min_weight, int64_t* n_points, int64_t cap, int32_t* tri) {
-    HostVolume v(nx, ny, nz, D, W);
+    const double origin[3] = {0.0, 0.0, 0.0};
+    HostVolume v(nx, ny, nz, origin, 1.0, D, W);
     return host_triangles(v, min_weight, n_points, cap, tri);
 }
 

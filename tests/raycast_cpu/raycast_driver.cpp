@@ -10,26 +10,9 @@
 #include <vector>
 
 #include "../../calibration_amd/csrc/tsdf_ray_math.hpp"
+#include "../host_volume.hpp"
 
 using namespace cba;
-
-struct HostVolume {
-    TsdfGrid g;
-    std::vector<float> vol;  // exactly the stored volume: a read past it is the sanitizer's to find
-    HostVolume(int nx, int ny, int nz, const double* origin, double vs, const float* D, const float* W) {
-        g.nx = nx; g.ny = ny; g.nz = nz; g.pitch = (nx + 1) & ~1;
-        for (int c = 0; c < 3; ++c) g.o[c] = origin[c];
-        g.vs = vs;
-        vol.assign(2 * static_cast<size_t>(g.pitch) * ny * nz, std::numeric_limits<float>::quiet_NaN());
-        for (int k = 0; k < nz; ++k)
-            for (int j = 0; j < ny; ++j)
-                for (int i = 0; i < nx; ++i) {
-                    const int64_t l = (static_cast<int64_t>(k) * ny + j) * nx + i;
-                    vol[tsdf_at(g, i, j, k)] = D[l];
-                    vol[tsdf_at(g, i, j, k) + 1] = W[l];
-                }
-    }
-};
 
 static TsdfRayRule make_rule(double vs, double trunc, const double* opts) {
     TsdfRayRule r;

@@ -19,7 +19,7 @@ from tests.test_cloud_cpu import CELL, INIT, MD, TRUTH_ERROR, check_sums, normal
 
 pytestmark = pytest.mark.gpu
 
-SCAN_TILE = 1024  # the scan kernel's block of cells (cloud_register.hip: CLOUD_SCAN_TILE); cloud_ref.nearest_cases builds around it
+SCAN_TILE = 1024  # the scan kernel's block of cells (scan_tiles.hpp: SCAN_TILE); cloud_ref.nearest_cases builds around it
 
 
 @pytest.fixture(scope="module")
