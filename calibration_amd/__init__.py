@@ -147,6 +147,7 @@ from .fusion import (  # noqa: F401
     depth_from_xyz,
     fuse,
     read_ply,
+    rgba_maps,
     track,
     write_ply,
 )

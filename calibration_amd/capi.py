@@ -598,6 +598,13 @@ PROTOTYPES = {
     "cba_tsdf_raycast": (
         C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.POINTER(CbaTsdfRaycastOptions)]),
     "cba_tsdf_raycast_fetch": (C.c_int32, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_uint8_p, c_double_p]),
+    "cba_tsdf_integrate_colour": (
+        C.c_int32, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_uint8_p, c_double_p]),
+    "cba_tsdf_has_colour": (C.c_int32, [C.c_void_p, c_int32_p]),
+    "cba_tsdf_colour_fetch": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cba_tsdf_colour_upload": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cba_tsdf_extract_fetch_colour": (C.c_int32, [C.c_void_p, c_uint8_p]),
+    "cba_tsdf_raycast_fetch_colour": (C.c_int32, [C.c_void_p, c_uint8_p]),
     "cba_tsdf_volume_destroy": (None, [C.c_void_p]),
     "cba_stereo_match_options_default": (None, [C.POINTER(CbaStereoMatchOptions)]),
     "cba_stereo_rectify": (

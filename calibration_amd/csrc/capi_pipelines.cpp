@@ -1194,8 +1194,9 @@ cba_status cba_tsdf_volume_create(int32_t nx, int32_t ny, int32_t nz, const doub
     });
 }
 
+// colour: cba_tsdf_integrate_colour, which needs rgba; eager: the experiment builds' kernel that loads every colour word
 static cba_status tsdf_integrate_impl(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_maps, int32_t height, int32_t width,
-                                      const double* depth, const double* c_T_v, double* stage_ms) {
+                                      const double* depth, const uint8_t* rgba, bool colour, const double* c_T_v, bool eager, double* stage_ms) {
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         check_camera(camera_model, intr, 0, nullptr);
@@ -1203,15 +1204,44 @@ static cba_status tsdf_integrate_impl(cba_tsdf_volume* h, int32_t camera_model, 
         if (n_maps < 0) throw std::invalid_argument("n_maps must be >= 0");
         check_sides(width, height);
         if (n_maps == 0) return;
-        if (!depth || !c_T_v) throw std::invalid_argument("null argument");
+        if (!depth || !c_T_v || (colour && !rgba)) throw std::invalid_argument("null argument");
         check_pose_quaternions(c_T_v, n_maps, "c_T_v needs a non-zero finite quaternion");
-        tsdf_volume_integrate(reinterpret_cast<TsdfVolume*>(h), camera_model, intr, n_maps, height, width, depth, c_T_v, stage_ms);
+        tsdf_volume_integrate(reinterpret_cast<TsdfVolume*>(h), camera_model, intr, n_maps, height, width, depth, colour ? rgba : nullptr, c_T_v, eager,
+                              stage_ms);
     });
 }
 
 cba_status cba_tsdf_integrate(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_maps, int32_t height, int32_t width,
                               const double* depth, const double* c_T_v) {
-    return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, c_T_v, nullptr);
+    return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, nullptr, false, c_T_v, false, nullptr);
+}
+
+cba_status cba_tsdf_integrate_colour(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_maps, int32_t height, int32_t width,
+                                     const double* depth, const uint8_t* rgba, const double* c_T_v) {
+    return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, rgba, true, c_T_v, false, nullptr);
+}
+
+cba_status cba_tsdf_has_colour(cba_tsdf_volume* h, int32_t* out) {
+    return guarded([&] {
+        if (!h || !out) throw std::invalid_argument("null argument");
+        *out = tsdf_volume_has_colour(reinterpret_cast<TsdfVolume*>(h)) ? 1 : 0;
+    });
+}
+
+cba_status cba_tsdf_colour_fetch(cba_tsdf_volume* h, float* colour) {
+    return guarded([&] {
+        if (!h || !colour) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (!tsdf_volume_has_colour(v)) throw std::invalid_argument("this volume has no colour");
+        tsdf_volume_colour_fetch(v, colour);
+    });
+}
+
+cba_status cba_tsdf_colour_upload(cba_tsdf_volume* h, const float* colour) {
+    return guarded([&] {
+        if (!h || !colour) throw std::invalid_argument("null argument");
+        tsdf_volume_colour_upload(reinterpret_cast<TsdfVolume*>(h), colour);
+    });
 }
 
 cba_status cba_tsdf_fetch(cba_tsdf_volume* h, float* tsdf, float* weight) {
@@ -1256,6 +1286,18 @@ cba_status cba_tsdf_extract_fetch(cba_tsdf_volume* h, double* xyz, double* norma
     });
 }
 
+cba_status cba_tsdf_extract_fetch_colour(cba_tsdf_volume* h, uint8_t* rgba) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (tsdf_volume_points(v) < 0) throw std::invalid_argument("no extract has run on this volume");
+        if (!tsdf_volume_points_coloured(v)) throw std::invalid_argument("the last extract ran without colour");
+        if (tsdf_volume_points(v) == 0) return;
+        if (!rgba) throw std::invalid_argument("null argument");
+        tsdf_volume_extract_fetch_colour(v, rgba);
+    });
+}
+
 static cba_status tsdf_mesh_impl(cba_tsdf_volume* h, double min_weight, int64_t* n_points, int64_t* n_triangles, double* stage_ms) {
     return guarded([&] {
         if (!h || !n_points || !n_triangles) throw std::invalid_argument("null argument");
@@ -1290,7 +1332,8 @@ void cba_tsdf_raycast_options_default(cba_tsdf_raycast_options* o) {
 
 // wave_w: the width of a wavefront's pixel block (8; the experiment builds compare 64)
 static cba_status tsdf_raycast_impl(cba_tsdf_volume* h, int32_t camera_model, const double* intr, int32_t n_views, int32_t height, int32_t width,
-                                    const double* poses, const cba_tsdf_raycast_options* opts, int wave_w, double* stage_ms) {
+                                    const double* poses, const cba_tsdf_raycast_options* opts, int wave_w, double* stage_ms,
+                                    double* colour_ms = nullptr) {
     return guarded([&] {
         if (!h) throw std::invalid_argument("null argument");
         check_camera(camera_model, intr, 0, nullptr);
@@ -1311,7 +1354,7 @@ static cba_status tsdf_raycast_impl(cba_tsdf_volume* h, int32_t camera_model, co
         if (n_views == 0) return;
         if (!poses) throw std::invalid_argument("null argument");
         check_pose_quaternions(poses, n_views, "poses needs a non-zero finite quaternion");
-        tsdf_volume_raycast(v, camera_model, intr, n_views, height, width, poses, o, wave_w, stage_ms);
+        tsdf_volume_raycast(v, camera_model, intr, n_views, height, width, poses, o, wave_w, stage_ms, colour_ms);
     });
 }
 
@@ -1329,6 +1372,17 @@ cba_status cba_tsdf_raycast_fetch(cba_tsdf_volume* h, double* depth, double* xyz
     });
 }
 
+cba_status cba_tsdf_raycast_fetch_colour(cba_tsdf_volume* h, uint8_t* rgba) {
+    return guarded([&] {
+        if (!h) throw std::invalid_argument("null argument");
+        TsdfVolume* v = reinterpret_cast<TsdfVolume*>(h);
+        if (tsdf_volume_ray_views(v) < 0) throw std::invalid_argument("no ray cast has run on this volume");
+        if (!tsdf_volume_rays_coloured(v)) throw std::invalid_argument("the last ray cast ran without colour");
+        if (!rgba) throw std::invalid_argument("null argument");
+        tsdf_volume_raycast_fetch_colour(v, rgba);
+    });
+}
+
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h) { tsdf_volume_destroy(reinterpret_cast<TsdfVolume*>(h)); }
 
 #ifdef CBA_EXPERIMENTS
@@ -1337,7 +1391,14 @@ void cba_tsdf_volume_destroy(cba_tsdf_volume* h) { tsdf_volume_destroy(reinterpr
 __attribute__((visibility("default"))) cba_status cba_tsdf_integrate_timed(cba_tsdf_volume* h, int32_t camera_model, const double* intr,
                                                                            int32_t n_maps, int32_t height, int32_t width, const double* depth,
                                                                            const double* c_T_v, double* stage_ms) {
-    return timed(stage_ms, [&] { return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, c_T_v, stage_ms); });
+    return timed(stage_ms, [&] { return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, nullptr, false, c_T_v, false, stage_ms); });
+}
+// tools/bench_colour.py: the colour integrate with its stages; eager != 0: the kernel that loads every colour word up front
+__attribute__((visibility("default"))) cba_status cba_tsdf_integrate_colour_timed(cba_tsdf_volume* h, int32_t camera_model, const double* intr,
+                                                                                  int32_t n_maps, int32_t height, int32_t width, const double* depth,
+                                                                                  const uint8_t* rgba, const double* c_T_v, int32_t eager,
+                                                                                  double* stage_ms) {
+    return timed(stage_ms, [&] { return tsdf_integrate_impl(h, camera_model, intr, n_maps, height, width, depth, rgba, true, c_T_v, eager != 0, stage_ms); });
 }
 __attribute__((visibility("default"))) cba_status cba_tsdf_extract_timed(cba_tsdf_volume* h, double min_weight, int64_t* n_points,
                                                                          double* stage_ms) {
@@ -1354,6 +1415,12 @@ __attribute__((visibility("default"))) cba_status cba_tsdf_raycast_timed(cba_tsd
                                                                          const cba_tsdf_raycast_options* opts, int32_t wave_w, double* stage_ms) {
     if (wave_w != 8 && wave_w != 64) return CBA_ERR_INVALID_ARGUMENT;
     return timed(stage_ms, [&] { return tsdf_raycast_impl(h, camera_model, intr, n_views, height, width, poses, opts, wave_w, stage_ms); });
+}
+// tools/bench_colour.py: stage_ms [3] = upload and the rays table, the cast, the colour pass
+__attribute__((visibility("default"))) cba_status cba_tsdf_raycast_colour_timed(cba_tsdf_volume* h, int32_t camera_model, const double* intr,
+                                                                                int32_t n_views, int32_t height, int32_t width, const double* poses,
+                                                                                const cba_tsdf_raycast_options* opts, double* stage_ms) {
+    return timed(stage_ms, [&] { return tsdf_raycast_impl(h, camera_model, intr, n_views, height, width, poses, opts, 8, stage_ms, stage_ms + 2); });
 }
 #endif
 

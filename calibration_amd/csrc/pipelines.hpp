@@ -141,8 +141,9 @@ TsdfVolume* tsdf_volume_create(int nx, int ny, int nz, const double* origin, con
 int64_t tsdf_volume_points(const TsdfVolume* h);
 double tsdf_volume_voxel_size(const TsdfVolume* h);
 void tsdf_volume_reset(TsdfVolume* h);
-void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
-                           double* stage_ms);
+// rgba: uint8 [n_maps][H][W][4] (cba_tsdf_integrate_colour) or NULL (cba_tsdf_integrate); eager: the experiment builds' colour kernel
+void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const uint8_t* rgba,
+                           const double* c_T_v, bool eager, double* stage_ms);
 void tsdf_volume_fetch(TsdfVolume* h, float* tsdf, float* weight);
 void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight);
 void tsdf_volume_extract(TsdfVolume* h, double min_weight, int64_t* n_points, double* stage_ms);
@@ -153,8 +154,16 @@ void tsdf_volume_mesh_fetch(TsdfVolume* h, int32_t* triangles);
 // the ray cast: the views of the last one (-1: none yet); stage_ms [2] optional: upload and the rays table, the cast
 int64_t tsdf_volume_ray_views(const TsdfVolume* h);
 void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_views, int H, int W, const double* c_T_v,
-                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms);
+                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms, double* colour_ms);
 void tsdf_volume_raycast_fetch(TsdfVolume* h, double* depth, double* xyz, double* normals, uint8_t* status, double* rays);
+// colour: whether the handle has a colour volume, and whether the last extract (or mesh) and the last ray cast ran with one
+bool tsdf_volume_has_colour(const TsdfVolume* h);
+bool tsdf_volume_points_coloured(const TsdfVolume* h);
+bool tsdf_volume_rays_coloured(const TsdfVolume* h);
+void tsdf_volume_colour_fetch(TsdfVolume* h, float* colour);
+void tsdf_volume_colour_upload(TsdfVolume* h, const float* colour);
+void tsdf_volume_extract_fetch_colour(TsdfVolume* h, uint8_t* rgba);
+void tsdf_volume_raycast_fetch_colour(TsdfVolume* h, uint8_t* rgba);
 void tsdf_volume_destroy(TsdfVolume* h) noexcept;
 // stereo_match.hip: cba_stereo_points and the cba_stereo_matcher handle (checked by the caller).  geom and pose7 optional at create;
 // disparity, cost, xyz optional; stage_ms [3] optional: upload, kernels, download

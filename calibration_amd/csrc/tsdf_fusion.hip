@@ -1,5 +1,5 @@
-// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, tsdf_mesh_math.hpp, tsdf_ray_math.hpp, calibba.h: cba_tsdf_volume,
-// cba_tsdf_integrate, cba_tsdf_extract, cba_tsdf_mesh, cba_tsdf_raycast).
+// tsdf_fusion.hip — scan fusion on the GPU (tsdf_math.hpp, tsdf_mesh_math.hpp, tsdf_ray_math.hpp, tsdf_colour_math.hpp, calibba.h:
+// cba_tsdf_volume, cba_tsdf_integrate, cba_tsdf_integrate_colour, cba_tsdf_extract, cba_tsdf_mesh, cba_tsdf_raycast).
 //   k_tsdf_fill         D = 1, W = 0 in every stored voxel (create, reset).
 //   k_tsdf_integrate    one launch per call.  A lane owns two adjacent x voxels, one aligned 16-byte {D, W, D, W} word that it loads
 //                       once, keeps in registers while it walks the call's maps in order, and stores once: the whole word when both
@@ -7,7 +7,12 @@
 //                       indexed by wave-uniform values alone (scalar loads, as in k_triangulate).  Per voxel and map: tsdf_update,
 //                       one fp64 projection and one 8-byte gather from the map; neighbouring voxels gather neighbouring pixels.  No
 //                       LDS, no atomics; no lane reads another's voxel.
+//   k_tsdf_integrate_colour   the same ownership and the same steps 1 to 6 (tsdf_update_at), with the {R, G, B, Wc} words of the lane's two
+//                       voxels beside them.  A voxel's colour word is loaded at its first step-7 update and stored once at the end, and
+//                       only then: the voxels outside the band, nearly all of them, cost no colour traffic.  The colour sample is one
+//                       4-byte gather at the pixel index of the depth gather.
 //   k_tsdf_planes       the interleaved rows <-> dense [nz][ny][nx] planes of D and of W (fetch, upload).
+//   k_tsdf_colour_planes   the colour rows <-> dense [nz][ny][nx][4] records, one 16-byte word per lane and step.
 //   k_tsdf_extract<0>   one workgroup per tile of TSDF_EXTRACT_TILE voxels of the dense order, in four rounds of 256 voxels: each lane
 //                       tests the three edges of its voxel; ballots and popcounts give the wave's total, wave_counts_prefix the workgroup's.
 //   k_scan_tiles / k_scan_add   (scan_tiles.hpp: scan_counts) the exclusive scan of the tile counts; one extra entry receives the total.
@@ -15,6 +20,8 @@
 //                       the ballots below its lane, so the order is the visiting order whatever the arrival order; tsdf_edge_point.
 //   k_tsdf_extract<1,1> the place pass of cba_tsdf_mesh: it also writes, per wave and round, the record {first place, three ballots} of
 //                       its 64 voxels (tsdf_mesh_math.hpp: TsdfEdgeGroup), from which an edge's place follows by popcounts.
+//   k_tsdf_extract<1,R,1>   the place pass on a handle with colour: it also writes the colour of each point (tsdf_colour_edge), one
+//                       4-byte store.  A handle without colour launches the instantiations above.
 //   k_tsdf_mesh<0/1>    the same tiles: a lane owns the cell at its voxel.  It loads the {D, W} words of its voxel in the four rows
 //                       (j, k) .. (j + 1, k + 1), forms sign and weight bits and takes the +x neighbour's from the next lane (the last lane
 //                       of a wave loads its own): four 8-byte loads per cell.  The table of triangles per case (2 KiB, generated from
@@ -27,6 +34,8 @@
 //                       per row where the cell's x is even, two 8-byte loads where it is odd; every decision in fp64.  The loop has
 //                       the rule's exits and no other (hit, behind, past the range, no progress, the sample cap).  No LDS, no
 //                       atomics, no scratch; a lane writes its own pixel only.
+//   k_tsdf_raycast_colour   after k_tsdf_raycast on a handle with colour: one lane per pixel reads its status, depth and ray and the view,
+//                       and stores the hit's colour (tsdf_colour_hit: eight 16-byte loads for a hit, none otherwise), one 4-byte store.
 // The handle owns one stream and every buffer; a call grows a buffer that is too small and allocates nothing else; every call ends
 // with the stream synchronised.  No float atomics, and no integer ones either.
 #include <memory>
@@ -35,6 +44,7 @@
 
 #include "pipelines.hpp"
 #include "scan_tiles.hpp"
+#include "tsdf_colour_math.hpp"
 #include "tsdf_math.hpp"
 #include "tsdf_mesh_math.hpp"
 #include "tsdf_ray_math.hpp"
@@ -82,6 +92,76 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_integrate(TsdfGrid g, const
         *(reinterpret_cast<float2*>(at) + 1) = make_float2(q.z, q.w);
 }
 
+// EAGER: both colour words loaded up front (instantiated by the experiment builds: what the lazy load is worth)
+template <int MODEL, bool EAGER = false>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_integrate_colour(TsdfGrid g, const TsdfCam* __restrict__ cam, const TsdfPose* __restrict__ poses,
+                                                                      const double* __restrict__ depth, const uint32_t* __restrict__ rgba, int n_maps,
+                                                                      TsdfRule r, float* __restrict__ vol, float* __restrict__ col) {
+    const int64_t pair = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x;
+    const int half = g.pitch >> 1;
+    const int64_t row = pair / half;
+    if (row >= static_cast<int64_t>(g.ny) * g.nz) return;
+    const int i = 2 * static_cast<int>(pair - row * half), k = static_cast<int>(row / g.ny), j = static_cast<int>(row - static_cast<int64_t>(k) * g.ny);
+    float4* at = reinterpret_cast<float4*>(vol) + pair;
+    float4* cat = reinterpret_cast<float4*>(col) + 2 * pair;  // a voxel's colour word has the number of its voxel
+    float4 q = *at;
+    const double xa = tsdf_coord(g.o[0], i, g.vs), xb = tsdf_coord(g.o[0], i + 1, g.vs);
+    const double y = tsdf_coord(g.o[1], j, g.vs), z = tsdf_coord(g.o[2], k, g.vs);
+    const bool second = i + 1 < g.nx;
+    const int64_t plane = static_cast<int64_t>(r.W) * r.H;
+    bool ca = false, cb = false;
+    float Ca[4] = {0.0f, 0.0f, 0.0f, 0.0f}, Cb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool have_a = false, have_b = false;  // the word is in registers
+    bool took_a = false, took_b = false;  // and step 7 changed it
+    if (EAGER) {
+        const float4 wa = cat[0], wb = cat[1];  // the padding voxel's word exists: rows are pitch words long
+        Ca[0] = wa.x; Ca[1] = wa.y; Ca[2] = wa.z; Ca[3] = wa.w;
+        Cb[0] = wb.x; Cb[1] = wb.y; Cb[2] = wb.z; Cb[3] = wb.w;
+        have_a = have_b = true;
+    }
+#pragma unroll 1
+    for (int m = 0; m < n_maps; ++m) {
+        const double* map = depth + m * plane;
+        const uint32_t* image = rgba + m * plane;
+        int64_t px;
+        double s;
+        if (tsdf_update_at<MODEL>(*cam, poses[m], map, r, xa, y, z, &q.x, &q.y, &px, &s)) {
+            ca = true;
+            const uint32_t c = image[px];
+            if (tsdf_colour_takes(s, r.trunc, c)) {
+                if (!have_a) {
+                    const float4 w = cat[0];
+                    Ca[0] = w.x; Ca[1] = w.y; Ca[2] = w.z; Ca[3] = w.w;
+                    have_a = true;
+                }
+                tsdf_colour_blend(Ca, c, r.max_weight);
+                took_a = true;
+            }
+        }
+        if (second && tsdf_update_at<MODEL>(*cam, poses[m], map, r, xb, y, z, &q.z, &q.w, &px, &s)) {
+            cb = true;
+            const uint32_t c = image[px];
+            if (tsdf_colour_takes(s, r.trunc, c)) {
+                if (!have_b) {
+                    const float4 w = cat[1];
+                    Cb[0] = w.x; Cb[1] = w.y; Cb[2] = w.z; Cb[3] = w.w;
+                    have_b = true;
+                }
+                tsdf_colour_blend(Cb, c, r.max_weight);
+                took_b = true;
+            }
+        }
+    }
+    if (ca && cb)
+        *at = q;
+    else if (ca)
+        *reinterpret_cast<float2*>(at) = make_float2(q.x, q.y);
+    else if (cb)
+        *(reinterpret_cast<float2*>(at) + 1) = make_float2(q.z, q.w);
+    if (took_a) cat[0] = make_float4(Ca[0], Ca[1], Ca[2], Ca[3]);
+    if (took_b) cat[1] = make_float4(Cb[0], Cb[1], Cb[2], Cb[3]);
+}
+
 // TO_DENSE: tsdf [n], weight [n] <- the volume; else the volume <- the planes.  Either plane may be NULL.
 template <bool TO_DENSE>
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_planes(TsdfGrid g, float* __restrict__ vol, float* __restrict__ tsdf, float* __restrict__ weight) {
@@ -99,11 +179,27 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_planes(TsdfGrid g, float* _
     }
 }
 
+// TO_DENSE: dense [n] <- the colour rows; else the colour rows <- dense: {R, G, B, Wc} records as they are
+template <bool TO_DENSE>
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_colour_planes(TsdfGrid g, float4* __restrict__ col, float4* __restrict__ dense) {
+    const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
+    for (int64_t l = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x; l < n; l += static_cast<int64_t>(gridDim.x) * TSDF_BLOCK) {
+        const int64_t row = l / g.nx;
+        float4* v = col + (row * g.pitch + (l - row * g.nx));
+        if (TO_DENSE)
+            dense[l] = *v;
+        else
+            *v = dense[l];
+    }
+}
+
 // PLACE false: count [tile] <- the tile's qualifying edges.  PLACE true: count holds the scanned starts; xyz, nrm [n_points][3] written.
-// RECORD (with PLACE): rec [tiles * TSDF_EXTRACT_TILE / 64] written, one per wave and round.
-template <bool PLACE, bool RECORD = false>
+// RECORD (with PLACE): rec [tiles * TSDF_EXTRACT_TILE / 64] written, one per wave and round.  COLOUR (with PLACE): rgba [n_points]
+// written from the colour rows col.
+template <bool PLACE, bool RECORD = false, bool COLOUR = false>
 __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const float* __restrict__ vol, double min_weight, int32_t* __restrict__ count,
-                                                             double* __restrict__ xyz, double* __restrict__ nrm, TsdfEdgeGroup* __restrict__ rec) {
+                                                             double* __restrict__ xyz, double* __restrict__ nrm, TsdfEdgeGroup* __restrict__ rec,
+                                                             const float* __restrict__ col, uint32_t* __restrict__ rgba) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = static_cast<int64_t>(g.nx) * g.ny * g.nz;
     int32_t base = PLACE ? count[blockIdx.x] : 0;
@@ -140,6 +236,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_extract(TsdfGrid g, const f
                     xyz[3 * at + c] = pt[c];
                     nrm[3 * at + c] = nn[c];
                 }
+                if (COLOUR) rgba[at] = tsdf_colour_edge(col, g, i, j, k, axis, Da, Db);
                 ++at;
             }
         }
@@ -243,6 +340,18 @@ __global__ __launch_bounds__(TSDF_RAY_BLOCK) void k_tsdf_raycast(TsdfGrid g, con
     status[at] = static_cast<uint8_t>(o.status);
 }
 
+// rgba [n_views][H][W] <- tsdf_colour_hit of the stored outputs of k_tsdf_raycast
+__global__ __launch_bounds__(TSDF_BLOCK) void k_tsdf_raycast_colour(TsdfGrid g, const float* __restrict__ col, const TsdfRayView* __restrict__ views,
+                                                                    const double* __restrict__ rays, int64_t plane, int64_t n_px,
+                                                                    const double* __restrict__ depth, const uint8_t* __restrict__ status,
+                                                                    uint32_t* __restrict__ rgba) {
+    const int64_t at = blockIdx.x * static_cast<int64_t>(TSDF_BLOCK) + threadIdx.x;
+    if (at >= n_px) return;
+    const int64_t view = at / plane;
+    const double2 ray = reinterpret_cast<const double2*>(rays)[at - view * plane];
+    rgba[at] = tsdf_colour_hit(col, g, views[view], status[at], depth[at], ray.x, ray.y);
+}
+
 struct TsdfVolume : DeviceHandle {
     using DeviceHandle::DeviceHandle;
     TsdfGrid g{};
@@ -268,6 +377,14 @@ struct TsdfVolume : DeviceHandle {
     DevBuf<double> rays;             // [ray_H][ray_W][2]
     DevBuf<double> rdepth, rxyz, rnrm;  // [ray_views][ray_H][ray_W] ([3])
     DevBuf<uint8_t> rstatus;
+    // colour: nothing below is allocated before the first cba_tsdf_integrate_colour or cba_tsdf_colour_upload
+    bool has_colour = false;
+    DevBuf<float> col;        // [nz][ny][pitch][4], zeros at first
+    DevBuf<float> cplanes;    // [n_voxels][4]: the staging of the colour fetch and upload
+    DevBuf<uint32_t> image;   // [n_maps][H][W] of a call
+    DevBuf<uint32_t> prgba;   // [n_points] of the last extract, when it ran with colour
+    DevBuf<uint32_t> rrgba;   // [ray_views][ray_H][ray_W] of the last ray cast, when it ran with colour
+    bool points_coloured = false, rays_coloured = false;
 };
 static_assert(!std::is_copy_constructible_v<TsdfVolume> && !std::is_copy_assignable_v<TsdfVolume>, "a handle owns its stream and buffers");
 
@@ -301,16 +418,30 @@ void tsdf_volume_reset(TsdfVolume* h) {
     const hipStream_t s = h->begin();
     h->n_triangles = -1;
     tsdf_fill(h, s);
+    if (h->has_colour) h->col.zero(s);
     CBA_HIP(hipStreamSynchronize(s));
 }
+
+// The colour volume of a handle that has none yet, all zeros.  An allocation failure throws with the handle as it was: without colour.
+static void tsdf_colour_ensure(TsdfVolume* h, hipStream_t s) {
+    if (h->has_colour) return;
+    h->col.alloc(4 * static_cast<size_t>(h->n_stored));
+    h->col.zero(s);
+    h->has_colour = true;
+}
+
+bool tsdf_volume_has_colour(const TsdfVolume* h) { return h->has_colour; }
+bool tsdf_volume_points_coloured(const TsdfVolume* h) { return h->points_coloured; }
+bool tsdf_volume_rays_coloured(const TsdfVolume* h) { return h->rays_coloured; }
 
 int64_t tsdf_volume_points(const TsdfVolume* h) { return h->n_points; }
 double tsdf_volume_voxel_size(const TsdfVolume* h) { return h->g.vs; }
 int64_t tsdf_volume_triangles(const TsdfVolume* h) { return h->n_triangles; }
 
-// stage_ms [2] optional: upload, kernel
-void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const double* c_T_v,
-                           double* stage_ms) {
+// rgba: uint8 [n_maps][H][W][4] for cba_tsdf_integrate_colour (the first such call allocates the colour volume), NULL for
+// cba_tsdf_integrate.  eager: the experiment builds' kernel that loads every colour word.  stage_ms [2] optional: upload, kernel
+void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_maps, int H, int W, const double* depth, const uint8_t* rgba,
+                           const double* c_T_v, bool eager, double* stage_ms) {
     const hipStream_t s = h->begin();
     h->n_triangles = -1;
     TsdfCam cam;
@@ -326,16 +457,30 @@ void tsdf_volume_integrate(TsdfVolume* h, int model, const double* intr, int n_m
     StageTimer<3> tm(s, stage_ms != nullptr);
     h->poses.ensure(static_cast<size_t>(n_maps));
     h->depth.ensure(n_px);
+    if (rgba) {
+        h->image.ensure(n_px);
+        tsdf_colour_ensure(h, s);  // last: a buffer that could not grow leaves the handle without colour, as it was
+    }
     tm.mark(0);
     h->cam.upload(&cam, 1, s);
     h->poses.upload(poses.data(), static_cast<size_t>(n_maps), s);
     h->depth.upload(depth, n_px, s);
+    if (rgba) h->image.upload(reinterpret_cast<const uint32_t*>(rgba), n_px, s);  // hipMemcpyAsync takes any alignment
     tm.mark(1);
     TsdfRule r;
     r.trunc = h->o.truncation; r.max_depth = h->o.max_depth; r.max_weight = h->o.max_weight; r.W = W; r.H = H;
     const dim3 grid(static_cast<unsigned>((h->n_stored / 2 + TSDF_BLOCK - 1) / TSDF_BLOCK));
-    hipLaunchKernelGGL(model == CAM_SCHEIMPFLUG ? k_tsdf_integrate<CAM_SCHEIMPFLUG> : k_tsdf_integrate<CAM_PINHOLE_BC>, grid, dim3(TSDF_BLOCK), 0, s, h->g,
-                       h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
+    if (!rgba)
+        hipLaunchKernelGGL(model == CAM_SCHEIMPFLUG ? k_tsdf_integrate<CAM_SCHEIMPFLUG> : k_tsdf_integrate<CAM_PINHOLE_BC>, grid, dim3(TSDF_BLOCK), 0, s,
+                           h->g, h->cam.p, h->poses.p, h->depth.p, n_maps, r, h->vol.p);
+#ifdef CBA_EXPERIMENTS
+    else if (eager)
+        hipLaunchKernelGGL((model == CAM_SCHEIMPFLUG ? k_tsdf_integrate_colour<CAM_SCHEIMPFLUG, true> : k_tsdf_integrate_colour<CAM_PINHOLE_BC, true>), grid,
+                           dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, h->image.p, n_maps, r, h->vol.p, h->col.p);
+#endif
+    else
+        hipLaunchKernelGGL((model == CAM_SCHEIMPFLUG ? k_tsdf_integrate_colour<CAM_SCHEIMPFLUG> : k_tsdf_integrate_colour<CAM_PINHOLE_BC>), grid,
+                           dim3(TSDF_BLOCK), 0, s, h->g, h->cam.p, h->poses.p, h->depth.p, h->image.p, n_maps, r, h->vol.p, h->col.p);
     CBA_HIP(hipGetLastError());
     tm.mark(2);
     CBA_HIP(hipStreamSynchronize(s));  // cam and poses go out of scope
@@ -369,25 +514,63 @@ void tsdf_volume_upload(TsdfVolume* h, const float* tsdf, const float* weight) {
     CBA_HIP(hipStreamSynchronize(s));
 }
 
+static void tsdf_colour_planes(TsdfVolume* h, hipStream_t s, bool to_dense) {
+    const dim3 grid(launch_grid(h->n_voxels, TSDF_BLOCK, TSDF_GRID));
+    hipLaunchKernelGGL(to_dense ? k_tsdf_colour_planes<true> : k_tsdf_colour_planes<false>, grid, dim3(TSDF_BLOCK), 0, s, h->g,
+                       reinterpret_cast<float4*>(h->col.p), reinterpret_cast<float4*>(h->cplanes.p));
+    CBA_HIP(hipGetLastError());
+}
+
+// colour [nz][ny][nx][4]; the handle has colour (checked by the caller)
+void tsdf_volume_colour_fetch(TsdfVolume* h, float* colour) {
+    const hipStream_t s = h->begin();
+    const size_t n = 4 * static_cast<size_t>(h->n_voxels);
+    h->cplanes.ensure(n);
+    tsdf_colour_planes(h, s, true);
+    h->cplanes.download(colour, n, s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+void tsdf_volume_colour_upload(TsdfVolume* h, const float* colour) {
+    const hipStream_t s = h->begin();
+    h->n_triangles = -1;
+    const size_t n = 4 * static_cast<size_t>(h->n_voxels);
+    h->cplanes.ensure(n);
+    tsdf_colour_ensure(h, s);  // after the staging: an allocation failure leaves the handle without colour, as it was
+    h->cplanes.upload(colour, n, s);
+    tsdf_colour_planes(h, s, false);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
 // The extract on s, ending synchronised; tm marks 0, 1, 2 around count and scan, and place.  record: the place pass also writes h->rec.
 template <class Timer>
 static int64_t tsdf_extract_run(TsdfVolume* h, hipStream_t s, double min_weight, bool record, Timer& tm) {
     const dim3 grid(static_cast<unsigned>(h->n_tiles));
     tm.mark(0);
-    hipLaunchKernelGGL((k_tsdf_extract<false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((k_tsdf_extract<false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight, h->count.p, nullptr, nullptr, nullptr, nullptr,
+                       nullptr);
     const int64_t total = scan_counts(s, h->count.p, h->n_tiles, h->tmp.p, h->total_h.p);
     tm.mark(1);
     h->n_points = -1;
+    h->points_coloured = false;
+    const bool colour = h->has_colour;  // a handle without colour launches what it always has
     if (total > 0) {
         h->xyz.ensure(3 * static_cast<size_t>(total));
         h->nrm.ensure(3 * static_cast<size_t>(total));
-        hipLaunchKernelGGL((record ? k_tsdf_extract<true, true> : k_tsdf_extract<true, false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p, min_weight,
-                           h->count.p, h->xyz.p, h->nrm.p, record ? h->rec.p : nullptr);
+        if (colour) {
+            h->prgba.ensure(static_cast<size_t>(total));
+            hipLaunchKernelGGL((record ? k_tsdf_extract<true, true, true> : k_tsdf_extract<true, false, true>), grid, dim3(TSDF_BLOCK), 0, s, h->g,
+                               h->vol.p, min_weight, h->count.p, h->xyz.p, h->nrm.p, record ? h->rec.p : nullptr, h->col.p, h->prgba.p);
+        } else {
+            hipLaunchKernelGGL((record ? k_tsdf_extract<true, true> : k_tsdf_extract<true, false>), grid, dim3(TSDF_BLOCK), 0, s, h->g, h->vol.p,
+                               min_weight, h->count.p, h->xyz.p, h->nrm.p, record ? h->rec.p : nullptr, nullptr, nullptr);
+        }
         CBA_HIP(hipGetLastError());
     }
     tm.mark(2);
     CBA_HIP(hipStreamSynchronize(s));
     h->n_points = total;
+    h->points_coloured = colour;
     return total;
 }
 
@@ -434,6 +617,13 @@ void tsdf_volume_mesh_fetch(TsdfVolume* h, int32_t* triangles) {
     CBA_HIP(hipStreamSynchronize(s));
 }
 
+// rgba uint8 [n_points][4]; the last extract ran with colour and gave points (checked by the caller)
+void tsdf_volume_extract_fetch_colour(TsdfVolume* h, uint8_t* rgba) {
+    const hipStream_t s = h->begin();
+    h->prgba.download(reinterpret_cast<uint32_t*>(rgba), static_cast<size_t>(h->n_points), s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
 void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals) {
     const hipStream_t s = h->begin();
     const size_t n = 3 * static_cast<size_t>(h->n_points);
@@ -445,9 +635,10 @@ void tsdf_volume_extract_fetch(TsdfVolume* h, double* xyz, double* normals) {
 int64_t tsdf_volume_ray_views(const TsdfVolume* h) { return h->ray_views; }
 
 // The ray cast reads the volume and writes only its own buffers: the extract's points and the mesh stay as they are.
-// wave_w: TSDF_RAY_WAVE_W; the experiment builds also take 64 for the comparison.  stage_ms [2] optional: upload and the rays table, the cast
+// wave_w: TSDF_RAY_WAVE_W; the experiment builds also take 64 for the comparison.  stage_ms [2] optional: upload and the rays table, the cast;
+// colour_ms optional, with stage_ms: the colour pass (0 on a handle without colour)
 void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_views, int H, int W, const double* c_T_v,
-                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms) {
+                         const cba_tsdf_raycast_options& o, int wave_w, double* stage_ms, double* colour_ms) {
     const hipStream_t s = h->begin();
     LsCamera cam;
     ls_fill_camera(model, intr, 0, nullptr, &cam);
@@ -457,7 +648,7 @@ void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_vie
     r.step = o.step > 0.0 ? o.step : 0.5 * h->g.vs;
     r.skip = o.skip; r.near_depth = o.near_depth; r.far_depth = o.far_depth; r.min_weight = o.min_weight; r.trunc = h->o.truncation;
     const size_t plane = static_cast<size_t>(H) * W, n_px = plane * n_views;
-    StageTimer<3> tm(s, stage_ms != nullptr);
+    StageTimer<4> tm(s, stage_ms != nullptr);
     h->ray_views = -1;  // a buffer that grows loses its contents: an allocation failure leaves the handle without a ray cast
     h->views.ensure(static_cast<size_t>(n_views));
     h->rays.ensure(2 * plane);
@@ -465,6 +656,9 @@ void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_vie
     h->rxyz.ensure(3 * n_px);
     h->rnrm.ensure(3 * n_px);
     h->rstatus.ensure(n_px);
+    const bool colour = h->has_colour;
+    h->rays_coloured = false;
+    if (colour) h->rrgba.ensure(n_px);
     tm.mark(0);
     h->views.upload(views.data(), static_cast<size_t>(n_views), s);
     hipLaunchKernelGGL(k_tsdf_rays, dim3(launch_grid(static_cast<int64_t>(plane), TSDF_BLOCK, TSDF_GRID)), dim3(TSDF_BLOCK), 0, s, H, W, h->rays.p, cam);
@@ -483,11 +677,22 @@ void tsdf_volume_raycast(TsdfVolume* h, int model, const double* intr, int n_vie
                            h->rdepth.p, h->rxyz.p, h->rnrm.p, h->rstatus.p);
     CBA_HIP(hipGetLastError());
     tm.mark(2);
+    if (colour) {  // a function of the cast's stored outputs and the colour volume alone: a pass of its own is exact
+        hipLaunchKernelGGL(k_tsdf_raycast_colour, dim3(static_cast<unsigned>((n_px + TSDF_BLOCK - 1) / TSDF_BLOCK)), dim3(TSDF_BLOCK), 0, s, h->g, h->col.p,
+                           h->views.p, h->rays.p, static_cast<int64_t>(plane), static_cast<int64_t>(n_px), h->rdepth.p, h->rstatus.p, h->rrgba.p);
+        CBA_HIP(hipGetLastError());
+    }
+    tm.mark(3);
     CBA_HIP(hipStreamSynchronize(s));  // views goes out of scope
+    h->rays_coloured = colour;
     h->ray_views = n_views;
     h->ray_H = H;
     h->ray_W = W;
-    tm.report(stage_ms);
+    if (stage_ms) {
+        stage_ms[0] = tm.ms(0, 1);
+        stage_ms[1] = tm.ms(1, 2);
+        if (colour_ms) *colour_ms = tm.ms(2, 3);
+    }
 }
 
 // each pointer may be NULL
@@ -499,6 +704,13 @@ void tsdf_volume_raycast_fetch(TsdfVolume* h, double* depth, double* xyz, double
     if (normals) h->rnrm.download(normals, 3 * n, s);
     if (status) h->rstatus.download(status, n, s);
     if (rays) h->rays.download(rays, 2 * plane, s);
+    CBA_HIP(hipStreamSynchronize(s));
+}
+
+// rgba uint8 [ray_views][ray_H][ray_W][4]; the last ray cast ran with colour (checked by the caller)
+void tsdf_volume_raycast_fetch_colour(TsdfVolume* h, uint8_t* rgba) {
+    const hipStream_t s = h->begin();
+    h->rrgba.download(reinterpret_cast<uint32_t*>(rgba), static_cast<size_t>(h->ray_H) * h->ray_W * static_cast<size_t>(h->ray_views), s);
     CBA_HIP(hipStreamSynchronize(s));
 }
 

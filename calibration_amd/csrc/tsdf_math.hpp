@@ -59,10 +59,11 @@ CBA_HD void tsdf_voxel_of(const TsdfGrid& g, int64_t l, int* i, int* j, int* k) 
     *j = static_cast<int>(row - static_cast<int64_t>(*k) * g.ny);
 }
 
-// One voxel at X through one map (steps 1-6 of calibba.h).  depth: the map [H][W].  Returns whether the voxel was updated.
+// One voxel at X through one map (steps 1-6 of calibba.h).  depth: the map [H][W].  Returns whether the voxel was updated, and then
+// *pixel = py W + px, the place of step 4's sample in the map, and *s of step 5 (what step 7 of tsdf_colour_math.hpp goes on from).
 template <int MODEL>
-CBA_HD bool tsdf_update(const TsdfCam& c, const TsdfPose& p, const double* depth, const TsdfRule& r, double X0, double X1, double X2, float* D,
-                        float* Wt) {
+CBA_HD bool tsdf_update_at(const TsdfCam& c, const TsdfPose& p, const double* depth, const TsdfRule& r, double X0, double X1, double X2, float* D,
+                           float* Wt, int64_t* pixel, double* s_out) {
     CBA_NO_CONTRACT
     const double P0 = ((p.R[0] * X0 + p.R[1] * X1) + p.R[2] * X2) + p.t[0];
     const double P1 = ((p.R[3] * X0 + p.R[4] * X1) + p.R[5] * X2) + p.t[1];
@@ -72,7 +73,8 @@ CBA_HD bool tsdf_update(const TsdfCam& c, const TsdfPose& p, const double* depth
     cam_project<MODEL>(c.intr, c.sd, P0, P1, P2, &u, &v);
     const double px = floor(u + 0.5), py = floor(v + 0.5);
     if (!(px >= 0.0 && px <= static_cast<double>(r.W - 1) && py >= 0.0 && py <= static_cast<double>(r.H - 1))) return false;  // false for NaN
-    const double d = depth[static_cast<int64_t>(static_cast<int>(py)) * r.W + static_cast<int>(px)];
+    const int64_t at = static_cast<int64_t>(static_cast<int>(py)) * r.W + static_cast<int>(px);
+    const double d = depth[at];
     if (!(tsdf_finite(d) && d > 0.0 && d <= r.max_depth)) return false;
     const double s = d - P2;
     if (s < -r.trunc) return false;
@@ -82,7 +84,17 @@ CBA_HD bool tsdf_update(const TsdfCam& c, const TsdfPose& p, const double* depth
     const double w1 = w + 1.0;
     *D = static_cast<float>((w * static_cast<double>(*D) + f) / w1);
     *Wt = static_cast<float>(w1 < r.max_weight ? w1 : r.max_weight);
+    *pixel = at;
+    *s_out = s;
     return true;
+}
+
+template <int MODEL>
+CBA_HD bool tsdf_update(const TsdfCam& c, const TsdfPose& p, const double* depth, const TsdfRule& r, double X0, double X1, double X2, float* D,
+                        float* Wt) {
+    int64_t pixel;
+    double s;
+    return tsdf_update_at<MODEL>(c, p, depth, r, X0, X1, X2, D, Wt, &pixel, &s);
 }
 
 // The edge from voxel a = (i, j, k) along +axis: whether it exists and qualifies; Da, Db: its two distances

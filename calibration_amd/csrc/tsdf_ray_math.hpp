@@ -74,8 +74,8 @@ CBA_HD void tsdf_ray_row(const float* vol, const TsdfGrid& g, int i, int j, int 
 #endif
 }
 
-// One sample at p (volume frame): false when p is outside the lattice or a voxel of its cell has W < min_weight; else *F
-CBA_HD bool tsdf_ray_sample(const float* vol, const TsdfGrid& g, double p0, double p1, double p2, double min_weight, double* F) {
+// The cell of p (volume frame) and p's place in it ("Sample at z"): false when p is outside the lattice; else cell [3] = (i, j, k), f [3]
+CBA_HD bool tsdf_ray_cell(const TsdfGrid& g, double p0, double p1, double p2, int* cell, double* f) {
     CBA_NO_CONTRACT
     const double g0 = (p0 - g.o[0]) / g.vs, g1 = (p1 - g.o[1]) / g.vs, g2 = (p2 - g.o[2]) / g.vs;
     // false for NaN, and decided before any conversion to an integer
@@ -86,7 +86,19 @@ CBA_HD bool tsdf_ray_sample(const float* vol, const TsdfGrid& g, double p0, doub
     i = i < g.nx - 2 ? i : g.nx - 2;
     j = j < g.ny - 2 ? j : g.ny - 2;
     k = k < g.nz - 2 ? k : g.nz - 2;
-    const double f0 = g0 - static_cast<double>(i), f1 = g1 - static_cast<double>(j), f2 = g2 - static_cast<double>(k);
+    cell[0] = i; cell[1] = j; cell[2] = k;
+    f[0] = g0 - static_cast<double>(i); f[1] = g1 - static_cast<double>(j); f[2] = g2 - static_cast<double>(k);
+    return true;
+}
+
+// One sample at p (volume frame): false when p is outside the lattice or a voxel of its cell has W < min_weight; else *F
+CBA_HD bool tsdf_ray_sample(const float* vol, const TsdfGrid& g, double p0, double p1, double p2, double min_weight, double* F) {
+    CBA_NO_CONTRACT
+    int cell[3];
+    double f[3];
+    if (!tsdf_ray_cell(g, p0, p1, p2, cell, f)) return false;
+    const int i = cell[0], j = cell[1], k = cell[2];
+    const double f0 = f[0], f1 = f[1], f2 = f[2];
     double c[4];
     bool heavy = true;
 #pragma unroll

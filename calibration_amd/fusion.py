@@ -1,7 +1,8 @@
 """Scan fusion on the GPU (``cba_tsdf_volume``, ``cba_tsdf_integrate``, ``cba_tsdf_extract``, ``cba_tsdf_mesh``, ``cba_tsdf_raycast``):
 depth maps of one object, each with its pose, are merged into a truncated signed distance volume, and the surface is read off it as
 points with normals on the lattice edges, as triangles over those points, and as what a camera at a given pose sees of it (depth,
-points and normals per pixel), by the rules calibba.h states.  ``track`` registers a new scan against the model's ray cast.  The
+points and normals per pixel), by the rules calibba.h states.  With the cameras' images behind the depth maps
+(``cba_tsdf_integrate_colour``) the volume also keeps a colour per voxel, and the points, the mesh and the ray cast carry it.  ``track`` registers a new scan against the model's ray cast.  The
 reference has no counterpart.  The mesh statistics, the PLY files and the clouds of a ray cast are host work in numpy.
 """
 from __future__ import annotations
@@ -64,6 +65,25 @@ class RayCastOptions:
 MISS, HIT, BEHIND, NO_RAY = capi.TSDF_RAY_MISS, capi.TSDF_RAY_HIT, capi.TSDF_RAY_BEHIND, capi.TSDF_RAY_NO_RAY
 
 
+def rgba_maps(colour, shape: Tuple[int, int, int]) -> np.ndarray:
+    """The images behind depth maps of shape = (n_maps, height, width) as uint8 [n_maps][height][width][4]: grey [n][H][W] is
+    replicated, and grey and [n][H][W][3] get A = 255; [n][H][W][4] is taken as it is (A == 0: the pixel has no colour).  One image
+    may be given for one map.  Host work."""
+    c = np.asarray(colour)
+    if c.dtype != np.uint8:
+        raise ValueError(f"colour must be uint8, got {c.dtype}")
+    n, H, W = shape
+    if n == 1 and c.shape in ((H, W), (H, W, 3), (H, W, 4)) and c.shape[:3] != (n, H, W):
+        c = c[None]
+    if c.shape == (n, H, W):
+        c = np.repeat(c[..., None], 3, axis=-1)
+    if c.shape == (n, H, W, 3):
+        c = np.concatenate([c, np.full((n, H, W, 1), 255, np.uint8)], axis=-1)
+    if c.shape != (n, H, W, 4):
+        raise ValueError(f"colour must be [{n}][{H}][{W}], [..][3] or [..][4], got {c.shape}")
+    return np.ascontiguousarray(c)
+
+
 def _rigid(pose7) -> Tuple[np.ndarray, np.ndarray]:
     """R, t of a rigid pose7 (the quaternion normalised)"""
     p = np.asarray(pose7, dtype=np.float64).reshape(7)
@@ -81,12 +101,14 @@ def pose_inverse(pose7) -> np.ndarray:
 class RayCast:
     """What cameras at n_views poses see of a volume: depth [n_views][height][width], xyz and normals [..][3] in each camera's frame
     (organised maps, NaN where a pixel is no hit; a hit's normal is NaN where there is none), status uint8 [..] (MISS, HIT, BEHIND,
-    NO_RAY) and the rays table [height][width][2]."""
+    NO_RAY) and the rays table [height][width][2]; rgba uint8 [n_views][height][width][4] when the volume has colour (A = 255 where
+    a hit has a colour, all four 0 elsewhere)."""
     depth: np.ndarray
     xyz: np.ndarray
     normals: np.ndarray
     status: np.ndarray
     rays: np.ndarray
+    rgba: Optional[np.ndarray] = None
 
     @property
     def hits(self) -> np.ndarray:
@@ -103,10 +125,12 @@ class RayCast:
 @dataclass
 class Mesh:
     """Indexed triangles over surface points: xyz [n][3], normals [n][3] (NaN where a point has none), triangles int32 [m][3].
-    (p1 - p0) x (p2 - p0) of a triangle points into positive D: out of the scanned object."""
+    (p1 - p0) x (p2 - p0) of a triangle points into positive D: out of the scanned object.  colours: uint8 [n][4] = R, G, B, A of the
+    points when the volume has colour (A = 0: the point has none)."""
     xyz: np.ndarray
     normals: np.ndarray
     triangles: np.ndarray
+    colours: Optional[np.ndarray] = None
 
     def _corners(self) -> np.ndarray:
         return self.xyz[self.triangles.astype(np.int64)]
@@ -138,30 +162,36 @@ class Mesh:
         used = np.zeros(len(self.xyz), bool)
         used[self.triangles.ravel()] = True
         new = (np.cumsum(used) - 1).astype(np.int32)
-        return Mesh(self.xyz[used], self.normals[used], new[self.triangles.astype(np.int64)].reshape(-1, 3))
+        return Mesh(self.xyz[used], self.normals[used], new[self.triangles.astype(np.int64)].reshape(-1, 3),
+                    None if self.colours is None else self.colours[used])
 
 
 _PLY_XYZ = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
 _PLY_NORMAL = [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+_PLY_COLOUR = [("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")]
 _PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
 def write_ply(path, mesh: Mesh, normals: Optional[bool] = None) -> None:
     """A binary little-endian PLY file: vertices as float64 x y z, then nx ny nz when ``normals`` is True or, by default, when every
-    normal is finite; faces as ``list uchar int``."""
+    normal is finite, then uchar red green blue alpha when ``mesh.colours`` is set; faces as ``list uchar int``."""
     if normals is None:
         normals = bool(np.isfinite(mesh.normals).all())
-    fields = _PLY_XYZ + (_PLY_NORMAL if normals else [])
+    colours = mesh.colours is not None
+    fields = _PLY_XYZ + (_PLY_NORMAL if normals else []) + (_PLY_COLOUR if colours else [])
     v = np.empty(len(mesh.xyz), np.dtype(fields))
     for c, (name, _) in enumerate(_PLY_XYZ):
         v[name] = mesh.xyz[:, c]
     if normals:
         for c, (name, _) in enumerate(_PLY_NORMAL):
             v[name] = mesh.normals[:, c]
+    if colours:
+        for c, (name, _) in enumerate(_PLY_COLOUR):
+            v[name] = mesh.colours[:, c]
     f = np.empty(len(mesh.triangles), _PLY_FACE)
     f["n"], f["v"] = 3, mesh.triangles
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
-    head += [f"property double {name}" for name, _ in fields]
+    head += [f"property {'uchar' if kind == 'u1' else 'double'} {name}" for name, kind in fields]
     head += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as out:
         out.write(("\n".join(head) + "\n").encode("ascii"))
@@ -170,28 +200,33 @@ def write_ply(path, mesh: Mesh, normals: Optional[bool] = None) -> None:
 
 
 def read_ply(path) -> Mesh:
-    """What ``write_ply`` wrote, and only that dialect; normals are NaN when the file has none."""
+    """What ``write_ply`` wrote, and only that dialect; normals are NaN and colours None when the file has none."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     head = data[:end].decode("ascii").split("\n")
     if head[:2] != ["ply", "format binary_little_endian 1.0"]:
         raise ValueError("not a binary little-endian PLY file")
-    names, n_vertex, n_face = [], None, None
+    names, kinds, n_vertex, n_face = [], [], None, None
     for line in head[2:]:
         w = line.split()
         if w[:2] == ["element", "vertex"]:
             n_vertex = int(w[2])
         elif w[:2] == ["element", "face"]:
             n_face = int(w[2])
-        elif w[:2] == ["property", "double"] and n_face is None:
+        elif w[:2] in (["property", "double"], ["property", "uchar"]) and len(w) == 3 and n_face is None:
             names.append(w[2])
+            kinds.append(w[1])
         elif w and w != ["end_header"] and w != ["property", "list", "uchar", "int", "vertex_indices"]:
             raise ValueError(f"not the dialect write_ply writes: {line!r}")
-    with_normals = names == [n for n, _ in _PLY_XYZ + _PLY_NORMAL]
-    if n_vertex is None or n_face is None or not (with_normals or names == [n for n, _ in _PLY_XYZ]):
+    with_colours = names[-4:] == [n for n, _ in _PLY_COLOUR]
+    geometry = names[:-4] if with_colours else names
+    with_normals = geometry == [n for n, _ in _PLY_XYZ + _PLY_NORMAL]
+    fields = _PLY_XYZ + (_PLY_NORMAL if with_normals else []) + (_PLY_COLOUR if with_colours else [])
+    if n_vertex is None or n_face is None or not (with_normals or geometry == [n for n, _ in _PLY_XYZ]) or \
+            kinds != ["uchar" if kind == "u1" else "double" for _, kind in fields]:
         raise ValueError("not the dialect write_ply writes")
-    vt = np.dtype(_PLY_XYZ + (_PLY_NORMAL if with_normals else []))
+    vt = np.dtype(fields)
     if len(data) != end + n_vertex * vt.itemsize + n_face * _PLY_FACE.itemsize:
         raise ValueError("the file's length does not match its header")
     v = np.frombuffer(data, vt, n_vertex, end)
@@ -200,7 +235,8 @@ def read_ply(path) -> Mesh:
         raise ValueError("a face is not a triangle")
     xyz = np.stack([v[n] for n, _ in _PLY_XYZ], axis=1) if n_vertex else np.zeros((0, 3))
     nrm = np.stack([v[n] for n, _ in _PLY_NORMAL], axis=1) if with_normals and n_vertex else np.full((n_vertex, 3), np.nan)
-    return Mesh(np.ascontiguousarray(xyz), np.ascontiguousarray(nrm), np.ascontiguousarray(f["v"]).reshape(-1, 3))
+    colours = np.stack([v[n] for n, _ in _PLY_COLOUR], axis=1).reshape(-1, 4) if with_colours else None
+    return Mesh(np.ascontiguousarray(xyz), np.ascontiguousarray(nrm), np.ascontiguousarray(f["v"]).reshape(-1, 3), colours)
 
 
 class TsdfVolume(capi.Handle):
@@ -217,9 +253,10 @@ class TsdfVolume(capi.Handle):
         co = opts._c()
         capi.check(self._lib, self._lib.cba_tsdf_volume_create(nx, ny, nz, dptr(self.origin), C.byref(co), int(device), out))
 
-    def integrate(self, camera_model: int, intr, poses, depth=None, xyz=None) -> None:
+    def integrate(self, camera_model: int, intr, poses, depth=None, xyz=None, colour=None) -> None:
         """Apply depth maps [n_maps][height][width] (or one [height][width]) in order; poses [n_maps][7]: volume frame -> camera.
-        ``xyz``: organised point maps in the camera's frame instead (``depth_from_xyz``)."""
+        ``xyz``: organised point maps in the camera's frame instead (``depth_from_xyz``).  ``colour``: the camera's images on the
+        maps' pixel grid, uint8 [n_maps][height][width], [..][3] or [..][4] (``rgba_maps``): the volume takes colour too."""
         h = self._require_open("the volume is closed")
         if (depth is None) == (xyz is None):
             raise ValueError("give depth or xyz, one of them")
@@ -235,7 +272,40 @@ class TsdfVolume(capi.Handle):
         k = np.ascontiguousarray(np.asarray(intr, dtype=np.float64).reshape(-1))
         if k.size != (12 if camera_model == 1 else 10):
             raise ValueError(f"intr has {k.size} entries")
-        capi.check(self._lib, self._lib.cba_tsdf_integrate(h, int(camera_model), dptr(k), d.shape[0], d.shape[1], d.shape[2], dptr(d), dptr(pose)))
+        if colour is None:
+            capi.check(self._lib, self._lib.cba_tsdf_integrate(h, int(camera_model), dptr(k), d.shape[0], d.shape[1], d.shape[2], dptr(d), dptr(pose)))
+            return
+        rgba = rgba_maps(colour, d.shape)
+        capi.check(self._lib, self._lib.cba_tsdf_integrate_colour(h, int(camera_model), dptr(k), d.shape[0], d.shape[1], d.shape[2], dptr(d),
+                                                                  u8ptr(rgba), dptr(pose)))
+
+    @property
+    def has_colour(self) -> bool:
+        out = np.zeros(1, np.int32)
+        capi.check(self._lib, self._lib.cba_tsdf_has_colour(self._require_open("the volume is closed"), i32ptr(out)))
+        return bool(out[0])
+
+    def fetch_colour(self) -> np.ndarray:
+        """-> the {R, G, B, Wc} records, float32 [nz][ny][nx][4]; the volume must have colour"""
+        h = self._require_open("the volume is closed")
+        nx, ny, nz = self.shape
+        colour = np.empty((nz, ny, nx, 4), np.float32)
+        capi.check(self._lib, self._lib.cba_tsdf_colour_fetch(h, _fptr(colour)))
+        return colour
+
+    def upload_colour(self, colour) -> None:
+        """Write records [nz][ny][nx][4] that ``fetch_colour`` returned; a volume without colour has it afterwards."""
+        h = self._require_open("the volume is closed")
+        nx, ny, nz = self.shape
+        a = np.ascontiguousarray(np.asarray(colour, dtype=np.float32))
+        if a.shape != (nz, ny, nx, 4):
+            raise ValueError(f"colour must be [{nz}][{ny}][{nx}][4], got {a.shape}")
+        capi.check(self._lib, self._lib.cba_tsdf_colour_upload(h, _fptr(a)))
+
+    def _point_colours(self, h, n: int) -> np.ndarray:
+        rgba = np.empty((n, 4), np.uint8)
+        capi.check(self._lib, self._lib.cba_tsdf_extract_fetch_colour(h, u8ptr(rgba)))
+        return rgba
 
     def fetch(self) -> Tuple[np.ndarray, np.ndarray]:
         """-> (tsdf, weight), float32 [nz][ny][nx]"""
@@ -258,14 +328,15 @@ class TsdfVolume(capi.Handle):
             planes.append(a)
         capi.check(self._lib, self._lib.cba_tsdf_upload(h, _fptr(planes[0]), _fptr(planes[1])))
 
-    def extract(self, min_weight: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
-        """-> (xyz [n][3], normals [n][3]): the zero crossings on lattice edges in visiting order; a normal is NaN where there is none"""
+    def extract(self, min_weight: float = 1.0, colour: bool = False):
+        """-> (xyz [n][3], normals [n][3]): the zero crossings on lattice edges in visiting order; a normal is NaN where there is none.
+        ``colour``: -> (xyz, normals, rgba uint8 [n][4]); the volume must have colour"""
         h = self._require_open("the volume is closed")
         n = np.zeros(1, np.int64)
         capi.check(self._lib, self._lib.cba_tsdf_extract(h, float(min_weight), i64ptr(n)))
         xyz, normals = np.empty((int(n[0]), 3)), np.empty((int(n[0]), 3))
         capi.check(self._lib, self._lib.cba_tsdf_extract_fetch(h, dptr(xyz), dptr(normals)))
-        return xyz, normals
+        return (xyz, normals, self._point_colours(h, int(n[0]))) if colour else (xyz, normals)
 
     def mesh(self, min_weight: float = 1.0, compact: bool = False) -> Mesh:
         """The surface as triangles over the points ``extract(min_weight)`` gives: a cell of eight voxels that all have W >= min_weight
@@ -276,7 +347,7 @@ class TsdfVolume(capi.Handle):
         xyz, normals, tri = np.empty((int(n[0]), 3)), np.empty((int(n[0]), 3)), np.empty((int(m[0]), 3), np.int32)
         capi.check(self._lib, self._lib.cba_tsdf_extract_fetch(h, dptr(xyz), dptr(normals)))
         capi.check(self._lib, self._lib.cba_tsdf_mesh_fetch(h, i32ptr(tri)))
-        out = Mesh(xyz, normals, tri)
+        out = Mesh(xyz, normals, tri, self._point_colours(h, int(n[0])) if self.has_colour else None)
         return out.compact() if compact else out
 
     def raycast(self, camera_model: int, intr, poses, shape: Tuple[int, int], opts: Optional[RayCastOptions] = None) -> RayCast:
@@ -294,6 +365,9 @@ class TsdfVolume(capi.Handle):
         if n > 0:
             capi.check(self._lib, self._lib.cba_tsdf_raycast_fetch(h, dptr(out.depth), dptr(out.xyz), dptr(out.normals), u8ptr(out.status),
                                                                    dptr(out.rays)))
+            if self.has_colour:
+                out.rgba = np.empty((n, H, W, 4), np.uint8)
+                capi.check(self._lib, self._lib.cba_tsdf_raycast_fetch_colour(h, u8ptr(out.rgba)))
         else:
             out.rays[:] = np.nan  # no work was done: there is no table
         return out
@@ -303,11 +377,18 @@ class TsdfVolume(capi.Handle):
 
 
 def fuse(shape, origin, opts: TsdfOptions, camera_model: int, intr, poses, depth=None, xyz=None, min_weight: float = 1.0, device: int = 0,
-         mesh: bool = False) -> Union[Tuple[np.ndarray, np.ndarray], Mesh]:
-    """One volume, one integrate, one extract: -> (xyz [n][3], normals [n][3]); with ``mesh=True`` one mesh instead: -> Mesh"""
+         mesh: bool = False, colour=None) -> Union[Tuple[np.ndarray, ...], Mesh]:
+    """One volume, one integrate, one extract: -> (xyz [n][3], normals [n][3]); with ``mesh=True`` one mesh instead: -> Mesh.
+    ``colour``: the images behind the maps (``TsdfVolume.integrate``): -> (xyz, normals, rgba uint8 [n][4]), or a Mesh with colours"""
     with TsdfVolume(shape, origin, opts, device) as vol:
-        vol.integrate(camera_model, intr, poses, depth=depth, xyz=xyz)
-        return vol.mesh(min_weight) if mesh else vol.extract(min_weight)
+        vol.integrate(camera_model, intr, poses, depth=depth, xyz=xyz, colour=colour)
+        if mesh:
+            return vol.mesh(min_weight)
+        if colour is None:
+            return vol.extract(min_weight)
+        if not vol.has_colour:  # no maps: no work was done and nothing was allocated; there are no points either
+            return vol.extract(min_weight) + (np.zeros((0, 4), np.uint8),)
+        return vol.extract(min_weight, colour=True)
 
 
 def track(vol: TsdfVolume, camera_model: int, intr, init_pose7, depth=None, xyz=None, icp=None, opts: Optional[RayCastOptions] = None):

@@ -1343,6 +1343,46 @@ void cba_cloud_set_destroy(cba_cloud_set* h);
  *    buffers: it does not invalidate the handle's extract or mesh, and a later integrate, upload, reset, extract or mesh does not
  *    invalidate its results.  n_views == 0 is no work and leaves earlier results as they are, as does every argument error.
  *
+ * Colour.  Every voxel has a second record {R, G, B, Wc}: four float32, all zeros at first, in a volume of its own that the first
+ * cba_tsdf_integrate_colour or cba_tsdf_colour_upload on a handle allocates.  A handle that makes neither call allocates nothing for
+ * colour and behaves in every call as stated above; an allocation failure leaves the handle usable and without colour.  Channels
+ * are kept as running means of byte values, so a mean of mixed exposures stays a mean: no gamma, no clamping before the output.
+ *
+ * 6. cba_tsdf_integrate_colour(h, camera_model, intr, n_maps, height, width, depth, rgba, c_T_v): rule 2 with the camera's image
+ *    behind each depth map.  rgba is uint8 [n_maps][height][width][4] = {R, G, B, A} on the depth map's pixel grid; A == 0 means
+ *    "this pixel has no colour" (every other A counts alike).  Steps 1 to 6 of rule 2 run unchanged: D and W after the call are,
+ *    to the bit, those of cba_tsdf_integrate with the same depth and poses.  Then, only for a voxel that step 6 updated through
+ *    map m:
+ *      7. Skip unless s <= truncation (the s of step 5) and A(m, py, px) != 0.  Otherwise, with c = double(byte) per channel and
+ *         the Wc from before this step, C <- float32((double(Wc) double(C) + c) / (double(Wc) + 1)) for R, G and B; then
+ *         Wc <- float32(min(double(Wc) + 1, max_weight)).
+ *    s <= truncation keeps the colour of a voxel that lies in observed free space in front of the band: what a pixel shows there
+ *    is the surface behind the voxel, seen from one side only.  Voxels with s < -truncation never reach step 7.  Inside the band
+ *    the mean is the plain one up to max_weight samples and a moving one after, as D's is.  A voxel's colour depends only on its
+ *    position and the maps in order: not on the batch, the launch or the other voxels.  cba_tsdf_integrate on a handle with
+ *    colour leaves the colour volume as it is.
+ *
+ * 7. The colour of an extract's point: cba_tsdf_extract and cba_tsdf_mesh on a handle that has colour at the time of the call also
+ *    give every point a colour, uint8 [n_points][4] in the order of the points.  With a, b and t of rule 3: when Wc_a > 0 and
+ *    Wc_b > 0, C = C_a + t (C_b - C_a) per channel (the product rounded, then the sum); when one end alone has Wc > 0, that end's
+ *    C; otherwise the point has no colour.  A channel's byte is q = floor(C + 0.5), 0 when q < 0 or C is NaN, 255 when q > 255.
+ *    A = 255 where there is a colour; where there is none, R = G = B = A = 0.  cba_tsdf_extract_fetch_colour(h, rgba) copies them
+ *    out; it fails when the last extract or mesh ran on a handle without colour.
+ *
+ * 8. The colour of a ray cast's hit: cba_tsdf_raycast on a handle that has colour at the time of the call also gives every pixel
+ *    a colour, uint8 [n_views][height][width][4].  For a pixel with status HIT: p_hit = c + z_hit d from the stored depth, the
+ *    rays table and the pose by rule 5's "View" arithmetic; g_a, i_a and f_a of p_hit by rule 5's "Sample at z".  There is a colour
+ *    only when every g_a is in range and all eight voxels of cell i have Wc > 0 (the weight W is not asked again); then each
+ *    channel is the trilinear value in rule 5's lerp order, made a byte as in rule 7, and A = 255.  Every other pixel is
+ *    {0, 0, 0, 0}.  The result is a function of the ray cast's stored outputs and the colour volume alone.
+ *    cba_tsdf_raycast_fetch_colour(h, rgba) copies it out; it fails when the last ray cast ran on a handle without colour.
+ *
+ * cba_tsdf_has_colour(h, &out) gives 1 or 0.  cba_tsdf_colour_fetch(h, colour [nz][ny][nx][4]) copies the records out (an error on a
+ * handle without colour) and cba_tsdf_colour_upload writes them, allocating the colour volume where there is none (a saved volume
+ * restored; the values are taken as they are); like cba_tsdf_upload it invalidates the handle's mesh.  cba_tsdf_reset also zeroes
+ * an existing colour volume.  cba_tsdf_integrate_colour has the argument errors of cba_tsdf_integrate and NULL rgba for n_maps > 0;
+ * n_maps == 0 is no work and allocates nothing.
+ *
  * cba_tsdf_fetch copies the dense [nz][ny][nx] planes of D and W out and cba_tsdf_upload writes them (a saved volume restored; the
  * values are taken as they are); either pointer may be NULL.  cba_tsdf_reset restores D = 1 and W = 0.  The handle owns one stream
  * and all of its device buffers; every call ends synchronised.  Float atomics are used nowhere.
@@ -1393,6 +1433,14 @@ cba_status cba_tsdf_raycast(cba_tsdf_volume* h, int32_t camera_model, const doub
                             int32_t width, const double* poses /*[n_views][7]*/, const cba_tsdf_raycast_options* opts /*NULL: defaults*/);
 cba_status cba_tsdf_raycast_fetch(cba_tsdf_volume* h, double* depth /*[n_views][height][width]*/, double* xyz /*[..][3]*/,
                                   double* normals /*[..][3]*/, uint8_t* status /*[..]*/, double* rays /*[height][width][2]*/);
+cba_status cba_tsdf_integrate_colour(cba_tsdf_volume* h, int32_t camera_model, const double* intr /*[10 | 12]*/, int32_t n_maps, int32_t height,
+                                     int32_t width, const double* depth /*[n_maps][height][width]*/,
+                                     const uint8_t* rgba /*[n_maps][height][width][4]*/, const double* c_T_v /*[n_maps][7]*/);
+cba_status cba_tsdf_has_colour(cba_tsdf_volume* h, int32_t* out);
+cba_status cba_tsdf_colour_fetch(cba_tsdf_volume* h, float* colour /*[nz][ny][nx][4]*/);
+cba_status cba_tsdf_colour_upload(cba_tsdf_volume* h, const float* colour /*[nz][ny][nx][4]*/);
+cba_status cba_tsdf_extract_fetch_colour(cba_tsdf_volume* h, uint8_t* rgba /*[n_points][4]*/);
+cba_status cba_tsdf_raycast_fetch_colour(cba_tsdf_volume* h, uint8_t* rgba /*[n_views][height][width][4]*/);
 void cba_tsdf_volume_destroy(cba_tsdf_volume* h);
 
 /* ---- stereo depth: rectification, block matching, disparity to 3D (no counterpart in the reference) -------------------------
